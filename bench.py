@@ -15,15 +15,19 @@ Default handle = ``eagle_default_config``: key-point network in EAGLE_PREC_F32S 
 per product — fp32-grade: heat-map maxima / key-points / H equal the fp32 oracle's on every test frame, floats to a few 1e-6), detector in the EXACT
 fp32 family (boxes, confidences, classes, NMS order and detection-index ids bit-identical to the fp32 oracle: tests/test_gpu_pipeline.py::
 test_default_handle_dense_detector_is_exception_free_*).  ``parity_counters`` counts integer-field differences against the exact family's records on
-the distinct frames of the clip (GPU against GPU; the exact family is the one that equals the oracle bit for bit).  Also in the line:
+the distinct frames of the clip (GPU against GPU; the exact family is the one that equals the oracle bit for bit).
+
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) does only what the headline needs: set-up, W warm-up steps, the K timed steps, then
+``--dump-outputs DIR`` if given (the records of the last timed step, one ``.npy`` per field) and the line: ``value``, ``ms_per_step``, ``config``,
+``saturation`` (clipped f32s stores: 0 in a healthy run).  ``--full`` adds everything else: ``resident``, ``host_sources``, ``parity_counters``,
 ``fast_family`` (fp16), ``exact_family`` (fp32), ``split_detector`` (both networks in f32s: round 3's headline), ``cfg3`` (BASELINE configs[2]:
-1000 frames 1920x1080, yolov8l@960), ``roofline`` (MFMA, the convolution family of the key-point precision, with ``dominant_kernel``),
-``roofline_conv_layers``, ``roofline_hbm``, ``saturation`` (clipped f32s stores: 0 in a healthy run), ``cpu_baseline``.
+1000 frames 1920x1080, yolov8l@960), ``realistic``, ``latency``, ``camera_motion_ecc``, ``roofline`` (MFMA, the convolution family of the key-point
+precision, with ``dominant_kernel``), ``roofline_conv_layers``, ``roofline_hbm``, ``detector_convs``, ``cpu_baseline``.
 
 Multi-GPU (driver launches one rank per GPU through torch.distributed.run): frames shard by contiguous chunk, weights replicated, no data-path
 collective; ONE all-gather of the fixed-size records at the end (inside the timed region); value = total frames of all ranks / max-over-ranks time
 ("scaling": "weak").  torch is imported only there, and BEFORE the HIP library is loaded (one ROCm runtime per process: eagle_amd/lib.py::
-require_torch_first); at N = 1 the process that touches the GPU never imports torch — the CPU baseline runs first, in a child process.
+require_torch_first); at N = 1 the process that touches the GPU never imports torch — with --full the CPU baseline runs first, in a child process.
 
 Prints ONE JSON line on rank 0.  The CPU oracle appears here only as the timed ``cpu_baseline`` leg."""
 import argparse
@@ -103,6 +107,32 @@ def cpu_baseline_subprocess(a):
         return json.loads(r.stdout.strip().splitlines()[-1])
     except Exception as e:                                # reported, never silent
         return {"value": None, "unit": "frames/s", "cores": 0, "kind": "port", "sample": f"cpu baseline child failed: {e!r}"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(rec, d):
+    """--dump-outputs: the records a caller of the timed path receives, one array per leaf field of RESULT_DTYPE (``H.npy``, ``hm_idx.npy``, ``det_x1.npy``,
+    ``kp_score.npy`` ...; padding bytes left out), first axis = frame.  fp32 fields stay fp32, every other field is written as fp64 (exact for int32 / uint8 / fp64).
+    Above DUMP_MAX_BYTES in all, a fixed seeded sample of the frames (ascending order) is written instead."""
+    leaves = []
+    for name in rec.dtype.names:
+        sub = rec.dtype[name].base
+        if sub.names is None:
+            leaves.append((name, rec[name]))
+        else:
+            leaves += [(f"{name}_{f}", rec[name][f]) for f in sub.names]
+    leaves = [(n, v) for n, v in leaves if not n.endswith("pad")]
+    as_float = lambda v: v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+    per_frame = sum(as_float(v[:1]).nbytes for _, v in leaves)
+    keep = np.arange(len(rec))
+    if per_frame * len(rec) > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(rec), DUMP_MAX_BYTES // per_frame, replace=False))
+    os.makedirs(d, exist_ok=True)
+    for n, v in leaves:
+        np.save(os.path.join(d, n + ".npy"), as_float(v[keep]))
+    log(f"outputs of the last timed step: {len(leaves)} arrays of {len(keep)} of {len(rec)} frames ({per_frame * len(keep) / 1e6:.1f} MB) -> {d}")
 
 
 def latency_table(lib, weights, hs, ys, a, dev_index, frames, calls, batches=(1, 2, 4, 8), modes=None):
@@ -211,6 +241,10 @@ def main():
                     help="family of the detector. default: the library's (exact fp32 next to f32s key-points, otherwise the key-point family)")
     ap.add_argument("--distinct", type=int, default=200, help="distinct synthetic frames generated per rank (tiled to the clip): 200 since round 5 — the data-dependent stages "
                     "(NMS candidate counts, RANSAC iteration counts, key-point dedup) see 200 different frames, and parity_counters compares all of them with the exact family")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: cpu_baseline (child process), roofline / roofline_conv_layers / roofline_hbm / "
+                    "detector_convs (a profiling pass), and unless --no-extras resident / host_sources / latency / camera_motion_ecc / the other families / parity_counters / cfg3 / "
+                    "realistic.  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records of the last timed step (every rank's) as DIR/<field>.npy, float32 / float64")
     ap.add_argument("--cpu-frames", type=int, default=40)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) time the CPU restatement and print its JSON object")
@@ -261,7 +295,7 @@ def main():
     multi = world > 1 or a.force_multirank_path
 
     cpu_base = None
-    if not multi and not a.no_cpu_baseline:                # rank 0 at N = 1 only (the measurement contract); before the GPU is touched, in a child
+    if a.full and not multi and not a.no_cpu_baseline:     # rank 0 at N = 1 only (the measurement contract); before the GPU is touched, in a child
         cpu_base = cpu_baseline_subprocess(a)
         log(f"cpu_baseline: {cpu_base}")
 
@@ -368,9 +402,11 @@ def main():
     saturation = {"sat_events": int(tm.sat_events), "sat_frames": int(tm.sat_frames),
                   "note": "f32s activation stores clipped at +-4094 during the timed call (EagleTimings; a non-zero count makes the call return EAGLE_E_RANGE)"}
     log(f"timed region {dt:.3f} s -> {total_frames / dt:.1f} frames/s (host frames)")
+    if a.dump_outputs and rank == 0:                  # the last timed step of every rank (allrec is rank-major)
+        dump_outputs(allrec.reshape(world, n_local)[:, n_local - B:].reshape(-1), a.dump_outputs)
 
-    extras = not multi and not a.no_extras
-    d_clip = h.upload(clip)                           # the clip resident in HBM: resident rate, profiling, family runs
+    extras = a.full and not multi and not a.no_extras
+    d_clip = h.upload(clip) if a.full or a.cadence > 0 else None      # the clip resident in HBM: resident rate, profiling, family runs, cadence
     resident = hostsrc = None
     if extras:
         o2 = np.zeros(n_local, lib.RESULT_DTYPE)
@@ -452,7 +488,9 @@ def main():
         kt = hh.kernel_times()
         hh.set_profiling(0)
         return ms, flop, nc, kt, prof_steps
-    _, _, _, ktimes, prof_steps = profile(h, d_clip, B)
+    ktimes, prof_steps = [], 1
+    if a.full:
+        _, _, _, ktimes, prof_steps = profile(h, d_clip, B)
     # The handle may run its two networks in two families (default: detector in exact fp32).  `roofline` is the KEY-POINT network's family (98.6 % of
     # the FLOP); the detector's launches (labels end in " d") are reported separately against their own family's peak (`detector_convs`).
     conv_ms = conv_flop = 0.0; n_conv = 0; conv_bytes = 0.0
@@ -619,7 +657,7 @@ def main():
 
     traffic = traffic_src = None
     tf = os.path.join(ROOT, "profiles", "conv_hbm_traffic.json" if a.precision == "f16" else f"conv_hbm_traffic_{a.precision}.json")     # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.py)
-    if os.path.exists(tf):
+    if a.full and os.path.exists(tf):
         tj = json.load(open(tf))
         if tj.get("batch") == B and tj.get("detector") == a.detector and tj.get("precision") == a.precision:
             traffic = tj["conv_family"]["hbm_bytes_per_launch"]
@@ -638,20 +676,21 @@ def main():
                        "keypoint_precision": a.precision, "detector_precision": det_prec_name,
                        "gather": "none" if not multi else gather_used, "hip_graph": bool(h.cfg.use_graph == 1 or (h.cfg.use_graph == 2 and K >= 3)), "graph_priming_steps": priming, "cpu_binding_rank0": cpu_binding, "timed_region_parts_rank0": parts,
                        "runtime": "torch-bundled ROCm (torch imported before libeagle_hip.so)" if multi else "/opt/rocm (torch-free process)"},
-            "roofline": {"bound": "mfma", "kernel": f"{CONV_KERNEL[a.precision]} (the {n_conv // prof_steps} convolution launches per step of the key-point network's family)",
-                         "achieved": round(achieved, 2), "peak": round(PEAK[a.precision], 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK[a.precision], 4),
-                         "flop_per_frame": conv_flop / (prof_steps * B), "avg_launch_us": round(conv_ms * 1e3 / max(n_conv, 1), 2),
-                         "conv_ms_per_step": round(conv_ms / prof_steps, 3),
-                         "algorithmic_bytes_per_launch": round(conv_bytes / max(n_conv, 1)),
-                         "dominant_kernel": None if dom is None else {"name": f"conv_f16_kernel / conv_split_ad_kernel instance of layer '{dom['layer']}'" if a.precision == "f32s" else dom["layer"],
-                                                                      "layer": dom["layer"], "launches_per_step": dom["launches_per_step"], "avg_us": dom["avg_us"],
-                                                                      "frac": dom["frac_mfma"], "ms_per_step": dom["ms_per_step"]},
-                         "traffic": traffic, "traffic_source": traffic_src},
             "value_is": "frames/s with the clip in PAGEABLE HOST memory when the timed region starts (SURVEY §8d: H2D -> networks -> geometry -> records on the host); "
                         "resident.value is the same path with the clip already in HBM",
             "saturation": saturation,
         }
+        if a.full:
+            res["roofline"] = {"bound": "mfma", "kernel": f"{CONV_KERNEL[a.precision]} (the {n_conv // prof_steps} convolution launches per step of the key-point network's family)",
+                               "achieved": round(achieved, 2), "peak": round(PEAK[a.precision], 1), "unit": "TFLOP/s",
+                               "frac": round(achieved / PEAK[a.precision], 4),
+                               "flop_per_frame": conv_flop / (prof_steps * B), "avg_launch_us": round(conv_ms * 1e3 / max(n_conv, 1), 2),
+                               "conv_ms_per_step": round(conv_ms / prof_steps, 3),
+                               "algorithmic_bytes_per_launch": round(conv_bytes / max(n_conv, 1)),
+                               "dominant_kernel": None if dom is None else {"name": f"conv_f16_kernel / conv_split_ad_kernel instance of layer '{dom['layer']}'" if a.precision == "f32s" else dom["layer"],
+                                                                            "layer": dom["layer"], "launches_per_step": dom["launches_per_step"], "avg_us": dom["avg_us"],
+                                                                            "frac": dom["frac_mfma"], "ms_per_step": dom["ms_per_step"]},
+                               "traffic": traffic, "traffic_source": traffic_src}
         if det_prec_name != a.precision and det_ms > 0:
             res["detector_convs"] = {"family": det_prec_name, "launches_per_step": n_det_conv // prof_steps, "ms_per_step_serialised": round(det_ms / prof_steps, 3),
                                      "achieved": round(det_flop / (det_ms * 1e-3) / 1e12, 2), "peak": PEAK[det_prec_name], "unit": "TFLOP/s",
@@ -685,7 +724,8 @@ def main():
             res["camera_motion_ecc"] = cmc
         if cpu_base is not None:
             res["cpu_baseline"] = cpu_base
-    h.free(d_clip)
+    if d_clip is not None:
+        h.free(d_clip)
     h.close()
     if dist is not None:
         dist.barrier()

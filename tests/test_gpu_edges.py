@@ -355,14 +355,14 @@ def test_default_handle_parity_on_the_runtime_the_multirank_bench_uses():
 
 
 def test_bench_default_line_carries_the_measurement_contract():
-    """`python bench.py` at N = 1 (small sizes): ONE JSON line with the contract's fields — value from host frames, `roofline` with frac = achieved / peak and
+    """`python bench.py --full` at N = 1 (small sizes): ONE JSON line with the contract's fields — value from host frames, `roofline` with frac = achieved / peak and
     the dominant kernel named, `cpu_baseline` from the child process, `parity_counters.default` all zero, `saturation` 0 / 0 — and the process never imported
     torch (the child did)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4", "--distinct", "4", "--cpu-frames", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "4", "--distinct", "4", "--cpu-frames", "1",
                         "--exact-frames", "8", "--fast-frames", "8", "--cfg3-frames", "0"], capture_output=True, text=True, timeout=900, cwd=root,
                        env=dict(os.environ, OMP_NUM_THREADS="8"))
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
@@ -379,6 +379,38 @@ def test_bench_default_line_carries_the_measurement_contract():
     assert all(pc[k] == 0 for k in ("hm_idx", "n_kp", "kp_pixels", "n_det", "det_cls", "det_int_box", "det_pitch_int", "det_id", "H_valid", "det_unmatched")) and pc["dets_compared"] > 0
     assert d["saturation"]["sat_events"] == 0 and d["saturation"]["sat_frames"] == 0
     assert d["detector_convs"]["family"] == "f32" and d["exact_family"]["value"] > 0 and d["fast_family"]["value"] > 0 and d["split_detector"]["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline fields only (no cpu_baseline, roofline or extras), `steps` timed steps, and --dump-outputs DIR holds the
+    records of the last timed step, one float32 / float64 array per field, equal to what a fresh default handle returns for the same four frames."""
+    import json
+    import subprocess
+    import sys
+    from eagle_amd import lib, synth, weights
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--distinct", "12",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=root, env=dict(os.environ, OMP_NUM_THREADS="8"))
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["config"]["frames_total"] == 12 and res["ms_per_step"] > 0 and res["unit"] == "frames/s"
+    assert abs(res["value"] - 12 / (3 * res["ms_per_step"] * 1e-3)) < 0.01 * res["value"]
+    assert not {"cpu_baseline", "roofline", "resident", "parity_counters", "exact_family", "latency"} & set(res), sorted(res)
+    got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+    assert {"n_det", "H_valid", "H", "hm_idx", "hm_score", "kp_x", "det_x1", "det_cls"} <= set(got) and not [k for k in got if k.endswith("pad")]
+    assert all(v.dtype in (np.float32, np.float64) and v.shape[0] == 4 for v in got.values())
+    h = lib.Handle(device=0, frame_h=720, frame_w=1280, det_variant="n", det_imgsz=640, batch=4, precision=lib.PRECISIONS["f32s"], use_graph=lib.AUTO)   # bench.py's handle
+    weights.load_into(h, [weights.make_hrnet_state_dict(0), weights.make_yolo_state_dict("n", 0)])
+    ref = h.process(synth.clip(seed=0, n=12)[8:12])
+    h.close()
+    for k in ("n_det", "n_kp", "H_valid", "hm_idx"):
+        assert np.array_equal(got[k], ref[k].astype(np.float64)), k
+    assert np.array_equal(got["hm_score"], ref["hm_score"])
+    for i, n in enumerate(ref["n_det"]):
+        assert np.array_equal(got["det_cls"][i, :n], ref["det"]["cls"][i, :n]) and np.array_equal(got["det_x1"][i, :n], ref["det"]["x1"][i, :n])
 
 
 def test_torch_after_the_first_handle_is_refused():

@@ -4,8 +4,8 @@
 tag=${1:-ab}; envn=${2:-EAGLE_CONV_AD}; shift; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$tag; mkdir -p $O; cd $R
 for i in 1 2; do
-  env $envn=0 timeout 600 python bench.py --no-cpu-baseline --no-extras "$@" > $O/bench_off$i.json 2>> $O/bench.err
-  timeout 600 python bench.py --no-cpu-baseline --no-extras "$@" > $O/bench_on$i.json 2>> $O/bench.err
+  env $envn=0 timeout 600 python bench.py --full --no-cpu-baseline --no-extras "$@" > $O/bench_off$i.json 2>> $O/bench.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-extras "$@" > $O/bench_on$i.json 2>> $O/bench.err
 done
 python - <<PY
 import json,glob,os

@@ -5,7 +5,7 @@ tag=${1:-x}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$tag; mkdir -p $O
 cd $R
 if [ -z "$2" ]; then timeout 2400 python -m pytest tests -m gpu -q > $O/gpu_tests.log 2>&1; grep -E "passed|failed" $O/gpu_tests.log | tail -1; fi
-timeout 1800 python bench.py --cadence 25 > $O/bench.json 2> $O/bench.err; wc -l $O/bench.json; tail -c 300 $O/bench.json; grep -v parity $O/bench.err | tail -4
+timeout 1800 python bench.py --full --cadence 25 > $O/bench.json 2> $O/bench.err; wc -l $O/bench.json; tail -c 300 $O/bench.json; grep -v parity $O/bench.err | tail -4
 timeout 600 python bench.py --force-multirank-path --backend nccl --gather rccl --no-cpu-baseline > $O/bench_multirank_world1.json 2> $O/bench_multirank_world1.err; wc -l $O/bench_multirank_world1.json; grep -o 'timed region.*' $O/bench_multirank_world1.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-extras > $O/prof.log 2>&1

@@ -28,7 +28,7 @@ for step in "$@"; do
     tests) timeout 2400 python -m pytest tests -m gpu -q > $O/gpu_tests.log 2>&1; grep -E "passed|failed" $O/gpu_tests.log | tail -1 ;;
     tests:*) timeout 2400 python -m pytest tests -m gpu -q -k "${step#tests:}" > $O/gpu_tests_k.log 2>&1; grep -E "passed|failed" $O/gpu_tests_k.log | tail -1 ;;
     smoke) python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log ;;
-    bench) timeout 1800 python bench.py > $O/bench_default_1gpu.json 2> $O/bench_default_1gpu.err; wc -c $O/bench_default_1gpu.json ;;
+    bench) timeout 1800 python bench.py --full > $O/bench_default_1gpu.json 2> $O/bench_default_1gpu.err; wc -c $O/bench_default_1gpu.json ;;
     bench:*) timeout 1800 python bench.py ${step#bench:} > $O/bench_custom.json 2> $O/bench_custom.err; tail -c 400 $O/bench_custom.json ;;
     multirank) timeout 900 python bench.py --force-multirank-path --backend nccl --gather rccl --no-cpu-baseline --no-extras > $O/bench_multirank_world1.json 2> $O/bench_multirank_world1.err; tail -c 300 $O/bench_multirank_world1.json ;;
     selflaunch) timeout 900 python bench.py --gpus 2 --shared-gpu --backend gloo --no-cpu-baseline --no-extras --steps 4 --warmup 1 --batch 8 > $O/bench_selflaunch_2ranks_1gpu.json 2> $O/bench_selflaunch_2ranks_1gpu.err; tail -c 300 $O/bench_selflaunch_2ranks_1gpu.json ;;
@@ -43,16 +43,16 @@ for step in "$@"; do
            for p1 in ring direct; do for f in 0 1; do echo "phase 1 $p1, form $f:" >> $L; EAGLE_BNECK_P1=$p1 EAGLE_BNECK_FORM=$f timeout 300 python tools/probes/bneck_probe.py 50 20 256,64 >> $L 2>&1; done; done; cat $L ;;
     bneck_ab) L=$O/bneck_pipeline_ab.log; : > $L
            for rep in 1 2 3; do for f in 0 1; do echo "EAGLE_BNECK_FUSED=$f rep $rep" >> $L
-             EAGLE_BNECK_FUSED=$f timeout 600 python bench.py --no-extras --no-cpu-baseline --latency-calls 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'frames/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['conv_ms_per_step'], 'ms, frac', d['roofline']['frac'])" >> $L 2>&1
+             EAGLE_BNECK_FUSED=$f timeout 600 python bench.py --full --no-extras --no-cpu-baseline --latency-calls 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'frames/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['conv_ms_per_step'], 'ms, frac', d['roofline']['frac'])" >> $L 2>&1
            done; done; cat $L ;;
     bneck_ds_ab) L=$O/bneck_ds_pipeline_ab.log; : > $L
            for rep in 1 2 3; do for f in 0 1; do echo "EAGLE_BNECK_DS=$f rep $rep" >> $L
-             EAGLE_BNECK_DS=$f timeout 600 python bench.py --no-extras --no-cpu-baseline --latency-calls 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'frames/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['conv_ms_per_step'], 'ms, frac', d['roofline']['frac'])" >> $L 2>&1
+             EAGLE_BNECK_DS=$f timeout 600 python bench.py --full --no-extras --no-cpu-baseline --latency-calls 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'frames/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['conv_ms_per_step'], 'ms, frac', d['roofline']['frac'])" >> $L 2>&1
            done; done; cat $L ;;
     bneck_ds) timeout 600 python tools/probes/bneck_ds_probe.py > $O/bneck_ds_probe.log 2>&1; timeout 600 python tools/probes/bneck_ds_pipeline_probe.py > $O/bneck_ds_pipeline_probe.log 2>&1; tail -4 $O/bneck_ds_probe.log $O/bneck_ds_pipeline_probe.log ;;
     env_ab:*) L=$O/env_ab.log; kv=${step#env_ab:}
            for rep in 1 2 3; do for f in 0 1; do if [ $f = 0 ]; then echo "unset rep $rep" >> $L; pre=""; else echo "$kv rep $rep" >> $L; pre="$kv"; fi
-             env $pre timeout 600 python bench.py --no-extras --no-cpu-baseline --latency-calls 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'frames/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['conv_ms_per_step'], 'ms, frac', d['roofline']['frac'])" >> $L 2>&1
+             env $pre timeout 600 python bench.py --full --no-extras --no-cpu-baseline --latency-calls 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'frames/s', d['ms_per_step'], 'ms/step; conv family', d['roofline']['conv_ms_per_step'], 'ms, frac', d['roofline']['frac'])" >> $L 2>&1
            done; done; cat $L ;;
     lat_ab:*) bash tools/probes/latency_env_ab.sh $tag ${step#lat_ab:} ;;
     b1trace) (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $O/b1trace -- python3 $R/tools/probes/latency_b1_trace.py run > $O/b1trace.log 2>&1)

@@ -7,7 +7,7 @@ hipcc's hazard recognizer covers the case with an immediate soffset only; this s
     python tools/isa_store_hazard.py --sources  # compiles eagle_amd/csrc/*.hip to assembly under /tmp and scans that instead (minutes)
 Exit status 1 on a finding.  tests/test_isa_lint.py runs the first form in the CPU suite.
 """
-import glob, os, re, subprocess, sys
+import glob, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = "--offload-arch=gfx950 -O3 -fno-slp-vectorize -std=c++17 -fPIC -ffp-contract=off -S --cuda-device-only".split()
@@ -61,12 +61,12 @@ def scan(path):
     return stores, found
 
 
-def code_objects(so):
+def code_objects(so, tmp):
     """the gfx950 code objects of every translation unit: .hip_fatbin is a sequence of clang offload bundles (magic, u64 count, {u64 offset, u64 size, u64 len, triple})"""
     import struct
     objcopy = "/opt/rocm/lib/llvm/bin/llvm-objcopy"
-    fat = "/tmp/isa_lint/fatbin"
-    subprocess.check_call([objcopy, "--dump-section", ".hip_fatbin=" + fat, so, "/tmp/isa_lint/discard.so"])
+    fat = os.path.join(tmp, "fatbin")
+    subprocess.check_call([objcopy, "--dump-section", ".hip_fatbin=" + fat, so, os.path.join(tmp, "discard.so")])
     blob = open(fat, "rb").read()
     magic, out, pos = b"__CLANG_OFFLOAD_BUNDLE__", [], 0
     while True:
@@ -86,12 +86,15 @@ def code_objects(so):
 
 
 def main():
-    out = "/tmp/isa_lint"
-    os.makedirs(out, exist_ok=True)
+    with tempfile.TemporaryDirectory(prefix="isa_lint_") as out:       # private to this run: a fixed /tmp path clashes between users
+        return lint(out)
+
+
+def lint(out):
     total, bad = 0, 0
     if "--sources" not in sys.argv:
         so = os.path.join(ROOT, "eagle_amd", "libeagle_hip.so")
-        objs = code_objects(so)
+        objs = code_objects(so, out)
         for k, co in enumerate(objs):
             path = os.path.join(out, f"co{k}.o")
             open(path, "wb").write(co)
