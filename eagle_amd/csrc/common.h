@@ -51,7 +51,7 @@ struct ConvConfig {          // tile configuration chosen per layer at graph-bui
     int nt = 0;              // 16-wide Cout tiles per workgroup (BN = 16*nt)
     int wx = 2;              // 16-pixel sub-tiles per tile row; tile = (16/wx) rows x (16*wx) cols, 4 per wave
     int cin = 0, cout_pad = 0;
-    int variant = 0;         // fp16 only: 0 = register-staged, 1 = persistent LDS-DMA pipeline
+    int variant = 0;         // kernel form within the family (conv.hip, g_forms)
 };
 struct ArgmaxPart { float score; int idx; };
 struct ConvLaunch {
@@ -71,7 +71,7 @@ struct ConvLaunch {
     unsigned* const* sat_slot = nullptr;
 };
 // output tiles per frame of a convolution with this configuration (the number of partials per channel the fused arg-max writes)
-int conv_tiles_per_frame(const ConvConfig& cfg, int ho, int wo);
+int conv_tiles_per_frame(int precision, const ConvConfig& cfg, int ho, int wo);
 // returns false when no kernel instance exists for cfg
 bool conv_supported(int precision, const ConvConfig& cfg);
 void conv_launch(int precision, const ConvLaunch& L, hipStream_t s);
@@ -84,7 +84,7 @@ void conv_tile_weights(int precision, const ConvConfig& cfg, const float* w_hwio
 inline int prec_tensor_fmt(int precision) { return precision == EAGLE_PREC_F32 ? 1 : precision == EAGLE_PREC_F32S ? 2 : 0; }
 inline bool prec_is_f16_kernels(int precision) { return precision == EAGLE_PREC_F16 || precision == EAGLE_PREC_F32S; }
 // plain_epilogue: pre_act none, post_act none/ReLU, at most one residual, fp16 output (what the weight-stationary kernel implements)
-ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_pad, int wo, bool plain_epilogue = false, bool second_residual = false, bool any_residual = true);
+ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_pad, int wo, bool plain_epilogue = false, bool second_residual = false);
 
 // ---- fused Bottleneck (bneck.hip; EAGLE_PREC_F32S): conv1 1x1 Cin->64 + ReLU, conv2 3x3 64->64 + ReLU, conv3 1x1 64->256 + residual + ReLU in one launch ----
 struct BneckLaunch {

@@ -25,110 +25,123 @@
 namespace eagle {
 
 // ------------------------------------------------------------------------------------------------------------
-// host side: geometry, instance table, weight tiling
+// host side: form table, geometry, choice, weight tiling
 // ------------------------------------------------------------------------------------------------------------
 static int f16_ps(int kc) { const int g = kc / 8; return kc * 2 + ((g % 2 == 0) ? 16 : 0); }
 static int f16_ni(int ks, int kc) { return (ks * ks * (kc / 8) + 3) / 4; }
 
-static int conv_pw(const ConvConfig& c) { return (c.variant == 3 || c.variant == 7) ? 2 : c.variant == 4 ? 1 : c.variant == 18 ? 6 : 4; }
-static bool conv_ws(const ConvConfig& c) { return c.variant == 6 || c.variant == 7; }
-static bool conv_ad_m32(const ConvConfig& c) { return c.variant >= 21 && c.variant <= 24; }      // split family on v_mfma_f32_32x32x16_f16 (conv_ad_split32.inc): 21 = BN 192, tile 4 x 32; 22 = BN 96, tile 8 x 32; 23 = BN 192, tile 2 x 64; 24 = BN 96, tile 4 x 64
-static int conv_ad_tw(const ConvConfig& c) { return (c.variant == 23 || c.variant == 24) ? 64 : 32; }      // output columns of an A-direct tile
-static bool conv_ad(const ConvConfig& c) { return (c.variant >= 8 && c.variant <= 15) || c.variant == 19 || conv_ad_m32(c); }
-static bool conv_ad_s2t(const ConvConfig& c) { return c.variant == 14 || c.variant == 15; }      // TRUE stride 2 on a column-plane halo (14: BN 192; 15: BN 96, K split over wave pairs)
-static bool conv_ad_s2d(const ConvConfig& c) { return c.variant == 10 || c.variant == 11; }      // stride 2 over the space-to-depth image (variants 14 / 15: true stride 2, the stride-1 weight image)
-static int conv_ad_rows(const ConvConfig& c) { return c.variant == 23 ? 2 : (c.variant == 8 || c.variant == 10 || c.variant == 21 || c.variant == 24 || conv_ad_s2t(c)) ? 4 : (c.variant == 13 || c.variant == 19) ? 16 : 8; }      // output rows of an A-direct tile      // A-direct: 8 = 4 Cout groups x 1 pixel group (BN 192), 9 = 2 x 2 (BN 96); 10 / 11 = the same for stride 2
-static bool conv_ad_wide(const ConvConfig& c) { return c.variant == 8 || c.variant == 10 || c.variant == 14 || c.variant == 21 || c.variant == 23; }
+// Every kernel form the library instantiates, keyed by (family, ConvConfig::variant): the ids are those of the tuned tables, tools/autotune_*.py and the
+// parity tests' EAGLE_CONV_FORCE strings.  Generic and weight-stationary forms have one instance per (ks, stride, kc, nt) in conv_inst_*.hip; an A-direct
+// form is one kernel (per residual count and ring depth) for 3x3 layers of the row's stride, kc and nt.
+enum FormKind { GENERIC, WSTAT, ADIRECT };                  // implicit GEMM; weight-stationary persistent; A-direct (weights straight into MFMA registers)
+enum StrideForm { S1, S2D, S2T };                           // A-direct: stride 1; stride 2 over the space-to-depth image; TRUE stride 2 on a column-plane halo
+enum WeightImage { W_F32, W_F16, W_F16_S2D, W_SPLIT, W_SPLIT_AD, W_SPLIT_S2D, W_SPLIT_M32 };    // layout written by conv_tile_weights
+struct Form {
+    int prec, variant, kind;
+    int pw;                  // generic / weight-stationary: 16-pixel sub-tiles per wave (tile = 4 pw / wx rows x 16 wx columns)
+    int sform, rows, cols;   // A-direct: stride handling and output tile
+    int kc, nt, halo_bufs;   // A-direct: the instance's chunk and Cout tiles (BN = 16 nt); halo buffers in LDS
+    int wimage;
+    int grid_cap;            // A-direct: at most this many workgroups per launch (0: one per item)
+    ConvKernelGetter get;    // A-direct
+};
+static constexpr Form gen(int prec, int variant, int pw, int wimage, int kind = GENERIC) { return {prec, variant, kind, pw, S1, 0, 0, 0, 0, 0, wimage, 0, nullptr}; }
+static constexpr Form ad(int prec, int variant, int sform, int rows, int cols, int nt, int halo_bufs, int wimage, ConvKernelGetter get, int grid_cap = 0)
+{
+    return {prec, variant, ADIRECT, 0, sform, rows, cols, prec == EAGLE_PREC_F16 ? 32 : 16, nt, halo_bufs, wimage, grid_cap, get};
+}
+static constexpr int F16 = EAGLE_PREC_F16, F32 = EAGLE_PREC_F32, F32S = EAGLE_PREC_F32S;
+static constexpr Form g_forms[] = {
+    // exact fp32 family: full (0), half (3) and quarter (4) tiles
+    gen(F32, 0, 4, W_F32), gen(F32, 3, 2, W_F32), gen(F32, 4, 1, W_F32),
+    // fp16: register-staged full tiles (0), chunk-pipelined staging (2), half (3) and quarter (4) tiles; weight-stationary 3x3 kernels, kc = Cin (6: 4 sub-tiles per wave, 7: 2)
+    gen(F16, 0, 4, W_F16), gen(F16, 2, 4, W_F16), gen(F16, 3, 2, W_F16), gen(F16, 4, 1, W_F16), gen(F16, 6, 4, W_F16, WSTAT), gen(F16, 7, 2, W_F16, WSTAT),
+    // fp16 A-direct (conv_ad_kernel.inc), kc = 32: BN 192, tile 4 x 32 (8) / BN 96, tile 8 x 32 (9); the same for stride 2 (10 / 11)
+    ad(F16, 8, S1, 4, 32, 12, 2, W_F16, conv_ad_kernel_s1_bn192), ad(F16, 9, S1, 8, 32, 6, 2, W_F16, conv_ad_kernel_s1_bn96),
+    ad(F16, 10, S2D, 4, 32, 12, 2, W_F16_S2D, conv_ad_kernel_s2_bn192), ad(F16, 11, S2D, 8, 32, 6, 2, W_F16_S2D, conv_ad_kernel_s2_bn96),
+    // split family, generic kernel: full (0) and half (3) tiles, 8 x 48 tiles (18: six sub-tiles per wave, wx = 3)
+    gen(F32S, 0, 4, W_SPLIT), gen(F32S, 3, 2, W_SPLIT), gen(F32S, 18, 6, W_SPLIT),
+    // split family, A-direct on 16x16x32 MFMA (conv_ad_split.inc), chunks of 16 logical channels: stride 1 (8 / 9), space-to-depth stride 2 (10 / 11)
+    ad(F32S, 8, S1, 4, 32, 12, 2, W_SPLIT_AD, conv_ad_split_kernel_bn192), ad(F32S, 9, S1, 8, 32, 6, 2, W_SPLIT_AD, conv_ad_split_kernel_bn96),
+    ad(F32S, 10, S2D, 4, 32, 12, 2, W_SPLIT_S2D, conv_ad_split_kernel_s2_bn192), ad(F32S, 11, S2D, 8, 32, 6, 2, W_SPLIT_S2D, conv_ad_split_kernel_s2_bn96),
+    // ... Cout = 48: tile 8 x 32 with the K dimension split over wave pairs (12); 16 x 32 with one halo buffer (13); 16 x 32 with the two-deep halo ring, whose
+    // 130 KB of LDS leave one workgroup per CU: persistent, so that the ring's prefetch runs on from item to item (19)
+    ad(F32S, 12, S1, 8, 32, 3, 2, W_SPLIT_AD, conv_ad_split_kernel48), ad(F32S, 13, S1, 16, 32, 3, 1, W_SPLIT_AD, conv_ad_split_kernel48sb),
+    ad(F32S, 19, S1, 16, 32, 3, 2, W_SPLIT_AD, conv_ad_split_kernel48ring, 256),
+    // ... TRUE stride 2 on an even / odd column-plane halo with the stride-1 weight image, one halo buffer: BN 192 (14); BN 96, K split over wave pairs (15)
+    ad(F32S, 14, S2T, 4, 32, 12, 1, W_SPLIT_AD, conv_ad_split_kernel_s2t_bn192), ad(F32S, 15, S2T, 4, 32, 6, 1, W_SPLIT_AD, conv_ad_split_kernel_s2t_bn96),
+    // split family, A-direct on 32x32x16 MFMA (conv_ad_split32.inc): tiles 4 x 32 (21) / 8 x 32 (22); the wave's two pixel blocks side by side (23 / 24)
+    ad(F32S, 21, S1, 4, 32, 12, 2, W_SPLIT_M32, conv_ad_split32_kernel_bn192), ad(F32S, 22, S1, 8, 32, 6, 2, W_SPLIT_M32, conv_ad_split32_kernel_bn96),
+    ad(F32S, 23, S1, 2, 64, 12, 2, W_SPLIT_M32, conv_ad_split32_kernel_w64_bn192), ad(F32S, 24, S1, 4, 64, 6, 2, W_SPLIT_M32, conv_ad_split32_kernel_w64_bn96)};
+
+static const Form* find_form(int precision, int variant)
+{
+    for (const Form& f : g_forms)
+        if (f.prec == precision && f.variant == variant) return &f;
+    return nullptr;
+}
+static const Form& form_of(int precision, const ConvConfig& c)
+{
+    const Form* f = find_form(precision, c.variant);
+    if (!f) fail(EAGLE_E_NOKERNEL, "no conv kernel form: prec=%d variant=%d", precision, c.variant);
+    return *f;
+}
+static int kind_of(int precision, const ConvConfig& c) { const Form* f = find_form(precision, c.variant); return f ? f->kind : -1; }
 
 static size_t lds_bytes(int precision, const ConvConfig& c)
 {
-    const int th = 4 * conv_pw(c) / c.wx, tw = 16 * c.wx;
+    const Form& f = form_of(precision, c);
+    if (f.kind == ADIRECT) {                                // halo buffers of 1-KiB slabs (a multiple of four) + the output strips
+        int hpix, rec, strips;
+        if (precision == EAGLE_PREC_F16) { hpix = f.sform == S2D ? (f.rows + 1) * 33 : (f.rows + 2) * 34; rec = 96; strips = 4 * 32 * 112; }
+        else if (f.wimage == W_SPLIT_M32) { hpix = (f.rows + 2) * (f.cols + 2); rec = 80; strips = 4 * 32 * 128; }      // 80-byte halo records; strips of 32 pixels x 32 channels x 4 bytes, 128-byte records swizzled by the pixel
+        else { hpix = f.sform == S2T ? (2 * f.rows + 1) * 66 : (f.rows + 2) * 34; rec = 96; strips = 4 * 16 * 208; }   // 16 logical channels = the 96-byte record (S2T: 2 rows + 1 x (33 even + 33 odd columns)); strips of 16 pixels x 48 channels x 4 bytes
+        const int slabs = ((hpix * rec + 1023) / 1024 + 3) / 4 * 4;
+        return (size_t)f.halo_bufs * slabs * 1024 + strips;
+    }
+    const int th = 4 * f.pw / c.wx, tw = 16 * c.wx;
     const int hw = (tw - 1) * c.stride + c.ks, hh = (th - 1) * c.stride + c.ks;
     const int bn = c.nt * 16;
-    if (precision == EAGLE_PREC_F16 && conv_ad(c)) {
-        const int pgn = conv_ad_wide(c) ? 1 : 2, slabs = (((c.stride == 2 ? (4 * pgn + 1) * 33 : (4 * pgn + 2) * 34) * 96 + 1023) / 1024 + 3) / 4 * 4;
-        return (size_t)2 * slabs * 1024 + 4 * 32 * 112;
-    }
     if (precision == EAGLE_PREC_F16) {
         const size_t operands = (size_t)f16_ni(c.ks, c.kc) * 4 * bn * 16 + (size_t)hh * hw * f16_ps(c.kc);
-        const size_t strips = (size_t)4 * conv_pw(c) * 16 * (bn * 2 + 16);        // output transpose, one strip per wave
-        return conv_ws(c) ? operands + strips + 16 : std::max(operands + 16, strips);
-    }
-    if (precision == EAGLE_PREC_F32S && conv_ad_m32(c)) {  // 80-byte halo records, two-deep ring, strips of 32 pixels x 32 channels x 4 bytes
-        const int slabs = (((conv_ad_rows(c) + 2) * (conv_ad_tw(c) + 2) * 80 + 1023) / 1024 + 3) / 4 * 4;
-        return (size_t)2 * slabs * 1024 + 4 * 32 * 128;       // strips: 128-byte records, units swizzled by the pixel
-    }
-    if (precision == EAGLE_PREC_F32S && conv_ad(c)) {      // same halo ring as the fp16 kernel (16 logical channels = the 96-byte record), strips of 16 pixels x 48 channels x 4 bytes
-        const int hpix = conv_ad_s2t(c) ? (2 * conv_ad_rows(c) + 1) * 66 : (conv_ad_rows(c) + 2) * 34;      // variants 14 / 15: 9 rows x (33 even + 33 odd columns)
-        const int slabs = ((hpix * 96 + 1023) / 1024 + 3) / 4 * 4;
-        return (size_t)((c.variant == 13 || conv_ad_s2t(c)) ? 1 : 2) * slabs * 1024 + 4 * 16 * 208;       // variants 13 - 15: one halo buffer
+        const size_t strips = (size_t)4 * f.pw * 16 * (bn * 2 + 16);        // output transpose, one strip per wave
+        return f.kind == WSTAT ? operands + strips + 16 : std::max(operands + 16, strips);
     }
     if (precision == EAGLE_PREC_F32S) {                    // hi and lo fragment blocks per K-step; 2 * kc fp16 values per staged pixel; 4-byte outputs
         const size_t operands = (size_t)f16_ni(c.ks, c.kc) * 2 * 4 * bn * 16 + (size_t)hh * hw * f16_ps(2 * c.kc);
-        const size_t strips = (size_t)4 * conv_pw(c) * 16 * (bn * 4 + 16);
+        const size_t strips = (size_t)4 * f.pw * 16 * (bn * 4 + 16);
         return std::max(operands + 16, strips);
     }
     return (size_t)c.ks * c.ks * (c.kc / 4) * 4 * bn * 4 + (size_t)hh * hw * (c.kc + 1) * 4;
 }
 
 size_t conv_lds_bytes(int precision, const ConvConfig& c) { return lds_bytes(precision, c); }
-int conv_tiles_per_frame(const ConvConfig& c, int ho, int wo)
+int conv_tiles_per_frame(int precision, const ConvConfig& c, int ho, int wo)
 {
-    if (conv_ad(c)) return ((wo + conv_ad_tw(c) - 1) / conv_ad_tw(c)) * ((ho + conv_ad_rows(c) - 1) / conv_ad_rows(c));
-    const int th = 4 * conv_pw(c) / c.wx, tw = 16 * c.wx;
+    const Form& f = form_of(precision, c);
+    const int th = f.kind == ADIRECT ? f.rows : 4 * f.pw / c.wx, tw = f.kind == ADIRECT ? f.cols : 16 * c.wx;
     return ((wo + tw - 1) / tw) * ((ho + th - 1) / th);
 }
 
-// The kernel instances live in four translation units (conv_inst_0..3.hip) so that a clean build compiles them in parallel; the A-direct
-// kernels in conv_ad_s1.hip / conv_ad_s2.hip.
-static const Inst g_ad_inst[] = {
-    // A-direct 3x3 kernels (variant 8: BN = 192, tile 4 x 32; 9: BN = 96, tile 8 x 32; 10 / 11: the same for stride 2); kc = 32
-    {EAGLE_PREC_F16, 3, 1, 32, 12, 8, nullptr}, {EAGLE_PREC_F16, 3, 1, 32, 6, 9, nullptr}, {EAGLE_PREC_F16, 3, 2, 32, 12, 10, nullptr}, {EAGLE_PREC_F16, 3, 2, 32, 6, 11, nullptr},
-    // split family: chunks of 16 logical channels (conv_ad_split.inc)
-    {EAGLE_PREC_F32S, 3, 1, 16, 12, 8, nullptr}, {EAGLE_PREC_F32S, 3, 1, 16, 6, 9, nullptr},
-    // split family, Cout = 48 per workgroup: tile 8 x 32, the K dimension split over wave pairs (variant 12)
-    {EAGLE_PREC_F32S, 3, 1, 16, 3, 12, nullptr},
-    // the same Cout with four pixel groups (16 x 32 tile) and a single halo buffer (variant 13)
-    {EAGLE_PREC_F32S, 3, 1, 16, 3, 13, nullptr},
-    // ... and with the two-deep halo ring: 130 KB of LDS, ONE persistent workgroup per CU whose ring runs on across its items (variant 19, round 4)
-    {EAGLE_PREC_F32S, 3, 1, 16, 3, 19, nullptr},
-    // split family, stride 2 over the space-to-depth image (variants 10 / 11)
-    {EAGLE_PREC_F32S, 3, 2, 16, 12, 10, nullptr}, {EAGLE_PREC_F32S, 3, 2, 16, 6, 11, nullptr},
-    // split family, TRUE stride 2 on an even / odd column-plane halo, the stride-1 weight image (variant 14: BN = 192, tile 4 x 32, one halo buffer)
-    {EAGLE_PREC_F32S, 3, 2, 16, 12, 14, nullptr},
-    // the same with BN = 96: two Cout groups, the K dimension split over wave pairs (variant 15)
-    {EAGLE_PREC_F32S, 3, 2, 16, 6, 15, nullptr},
-    // split family, stride 1, on v_mfma_f32_32x32x16_f16 (round 5, conv_ad_split32.inc): BN = 192 (variant 21) / BN = 96 (variant 22)
-    {EAGLE_PREC_F32S, 3, 1, 16, 12, 21, nullptr}, {EAGLE_PREC_F32S, 3, 1, 16, 6, 22, nullptr},
-    // ... with the wave's two pixel blocks side by side (tiles 2 x 64 / 4 x 64: 34- and 68-row maps without a row remainder): variants 23 / 24
-    {EAGLE_PREC_F32S, 3, 1, 16, 12, 23, nullptr}, {EAGLE_PREC_F32S, 3, 1, 16, 6, 24, nullptr}};
-
-const Inst* conv_inst_part(int part, int* n)
+// The generic instances live in conv_inst_0..3.hip / conv_inst_s0..2.hip so that a clean build compiles them in parallel; the A-direct kernels in
+// conv_ad_s1.hip / conv_ad_s2.hip / conv_ad_split.hip / conv_ad_split32.hip.
+static const Inst* generic_inst(int precision, const ConvConfig& c)
 {
-    return part == 0 ? conv_inst_part0(n) : part == 1 ? conv_inst_part1(n) : part == 2 ? conv_inst_part2(n) : conv_inst_part3(n);
-}
-
-static const Inst* find_inst(int precision, const ConvConfig& c)
-{
-    auto match = [&](const Inst& i) { return i.prec == precision && i.ks == c.ks && i.s == c.stride && i.kc == c.kc && i.nt == c.nt && i.variant == c.variant; };
-    for (const Inst& i : g_ad_inst)
-        if (match(i)) return &i;
-    for (int part = 0; part < 7; ++part) {
+    for (auto part : {conv_inst_part0, conv_inst_part1, conv_inst_part2, conv_inst_part3, conv_inst_split0, conv_inst_split1, conv_inst_split2}) {
         int n = 0;
-        const Inst* t = part < 4 ? conv_inst_part(part, &n) : part == 4 ? conv_inst_split0(&n) : part == 5 ? conv_inst_split1(&n) : conv_inst_split2(&n);
+        const Inst* t = part(&n);
         for (int k = 0; k < n; ++k)
-            if (match(t[k])) return &t[k];
+            if (t[k].prec == precision && t[k].ks == c.ks && t[k].s == c.stride && t[k].kc == c.kc && t[k].nt == c.nt && t[k].variant == c.variant) return &t[k];
     }
     return nullptr;
 }
-bool conv_supported(int precision, const ConvConfig& c) { return find_inst(precision, c) != nullptr; }
+bool conv_supported(int precision, const ConvConfig& c)
+{
+    const Form* f = find_form(precision, c.variant);
+    if (f && f->kind == ADIRECT) return c.ks == 3 && c.stride == (f->sform == S1 ? 1 : 2) && c.kc == f->kc && c.nt == f->nt;
+    return f && generic_inst(precision, c);
+}
 
-// Default form of the split family's 3x3 stride-1 layers with Cout = 96 k (EAGLE_CONV_M32 overrides; 0 = the 16x16x32 A-direct forms of rounds 3 / 4).
-// 6 since round 5: the 32x32x16 kernels, 4 x 32 tiles for BN = 192 and 4 x 64 tiles for BN = 96 on maps wider than 32 columns — same box, three alternating
-// pairs through the whole pipeline: 750.0 / 751.0 / 753.4 -> 761.3 / 761.5 / 761.8 frames/s with the tile per map (mode 4; +1.4 %), 96->96 @68x120 208.5 -> 193.5 us.
-#ifndef EAGLE_CONV_M32_DEFAULT
-#define EAGLE_CONV_M32_DEFAULT 6
-#endif
 struct Tuned { int ks, s, cin, cout, wo, kc, nt, wx, variant; };
 static const Tuned g_tuned[] = {
 #include "conv_tuned.inc"
@@ -139,153 +152,120 @@ static const Tuned g_tuned_f32[] = {         // EAGLE_PREC_F32: tile shape only 
 static const Tuned g_tuned_split[] = {       // EAGLE_PREC_F32S (tools/autotune_split.py); rows of one shape are ordered best first
 #include "conv_tuned_split.inc"
     {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-
-ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_pad, int wo, bool plain_epilogue, bool second_residual, bool any_residual)
+static bool tuned_match(const Tuned& t, const ConvConfig& c, int wo, ConvConfig* q)
 {
-    // plain_epilogue: no activation before the residual adds, none / ReLU after them, fp16 output.  The weight-stationary kernels also need
-    // at most one residual; the A-direct kernels take two.
-    const bool plain_one = plain_epilogue && !second_residual;
-    ConvConfig c;
-    c.ks = ks; c.stride = stride; c.cin = cin_pad; c.cout_pad = cout_pad;
-    c.wx = (wo > 16) ? 2 : 1;
-    static const int nts[] = {6, 4, 3, 2, 1};
-    if (precision == EAGLE_PREC_F32) {
-        if (const char* f = getenv("EAGLE_F32_FORCE")) {    // "nt,wx,variant": parity tests of the tilings (every tiling gives the same bits)
-            ConvConfig q = c; q.kc = (cin_pad < 16) ? 4 : 16;
-            if (sscanf(f, "%d,%d,%d", &q.nt, &q.wx, &q.variant) == 3 && (q.wx == 1 || q.wx == 2) && q.nt >= 1 && cout_pad % (16 * q.nt) == 0 && find_inst(precision, q) && lds_bytes(precision, q) <= 160 * 1024) return q;
-        }
-        static const bool tuned32 = !(getenv("EAGLE_CONV_TUNED") && atoi(getenv("EAGLE_CONV_TUNED")) == 0);
-        if (tuned32)
-            for (const Tuned& t : g_tuned_f32)
-                if (t.ks == ks && t.s == stride && t.cin == cin_pad && t.cout == cout_pad && t.wo == wo) {
-                    ConvConfig q = c; q.kc = t.kc; q.nt = t.nt; q.wx = t.wx; q.variant = t.variant;      // variant: 0 full, 3 half, 4 quarter tiles
-                    if (find_inst(precision, q)) return q;
-                }
-        c.nt = 1;
-        for (int nt : nts)
-            if (cout_pad % (16 * nt) == 0) { c.nt = nt; break; }
-        c.kc = (cin_pad < 16) ? 4 : 16;
-        if (stride == 2 && ks == 3) {                       // the halo of a stride-2 tile is four times the tile: half tiles keep two workgroups on a CU
-            ConvConfig q = c; q.variant = 3;
-            if (find_inst(precision, q)) return q;
-        }
-        return c;
+    if (t.ks != c.ks || t.s != c.stride || t.cin != c.cin || t.cout != c.cout_pad || t.wo != wo) return false;
+    *q = c; q->kc = t.kc; q->nt = t.nt; q->wx = t.wx; q->variant = t.variant;
+    return true;
+}
+
+// The developer switches, read on every call (the parity tests set them between calls):
+//   EAGLE_CONV_FORCE="kc,nt,variant" (fp16 and split families) / EAGLE_F32_FORCE="nt,wx,variant" (exact family): this form for every layer it is valid for;
+//   EAGLE_CONV_M32=0: the split family's 3x3 stride-1 layers with Cout = 96 k on the 16x16x32 A-direct forms instead of the 32x32x16 ones;
+//   EAGLE_F32_STACK=0: no row stacking in the exact family (conv_launch).
+static bool env_force(const char* name, int* a, int* b, int* c) { const char* f = getenv(name); return f && sscanf(f, "%d,%d,%d", a, b, c) == 3; }
+static bool env_off(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
+
+static const int g_nts[] = {6, 4, 3, 2, 1};
+static ConvConfig with_ad(ConvConfig c, int kc, int v192, int v96)      // an A-direct form: BN = 192 where Cout allows it, else BN = 96
+{
+    c.kc = kc;
+    if (c.cout_pad % 192 == 0) { c.nt = 12; c.variant = v192; } else { c.nt = 6; c.variant = v96; }
+    return c;
+}
+
+static ConvConfig choose_f32(ConvConfig c, int wo)
+{
+    ConvConfig q = c; q.kc = (c.cin < 16) ? 4 : 16;          // parity tests of the tilings (every tiling gives the same bits)
+    if (env_force("EAGLE_F32_FORCE", &q.nt, &q.wx, &q.variant) && (q.wx == 1 || q.wx == 2) && q.nt >= 1 && c.cout_pad % (16 * q.nt) == 0 &&
+        conv_supported(EAGLE_PREC_F32, q) && lds_bytes(EAGLE_PREC_F32, q) <= 160 * 1024)
+        return q;
+    for (const Tuned& t : g_tuned_f32)                       // variant: 0 full, 3 half, 4 quarter tiles
+        if (tuned_match(t, c, wo, &q) && conv_supported(EAGLE_PREC_F32, q)) return q;
+    c.nt = 1;
+    for (int nt : g_nts)
+        if (c.cout_pad % (16 * nt) == 0) { c.nt = nt; break; }
+    c.kc = (c.cin < 16) ? 4 : 16;
+    if (c.stride == 2 && c.ks == 3) {                       // the halo of a stride-2 tile is four times the tile: half tiles keep two workgroups on a CU
+        q = c; q.variant = 3;
+        if (conv_supported(EAGLE_PREC_F32, q)) return q;
     }
-    if (precision == EAGLE_PREC_F32S) {
-        // split family: generic kernel, full (variant 0) or half (variant 3) tiles; the (NT, KC) pair with the most MFMA work per staged byte
-        // whose LDS footprint lets two workgroups share a CU.  EAGLE_CONV_FORCE applies as below.
-        if (const char* f = getenv("EAGLE_CONV_FORCE")) {
-            ConvConfig q = c;
-            if (sscanf(f, "%d,%d,%d", &q.kc, &q.nt, &q.variant) == 3 && cin_pad % q.kc == 0 && cout_pad % (16 * q.nt) == 0 && find_inst(precision, q)) {
-                if (q.variant == 18) q.wx = 3;              // the 8 x 48 tile
-                if (lds_bytes(precision, q) <= 160 * 1024) return q;
+    return c;
+}
+
+static ConvConfig choose_split(ConvConfig c, int wo, bool plain_epilogue)
+{
+    const int prec = EAGLE_PREC_F32S, cin = c.cin, cout = c.cout_pad;
+    ConvConfig q = c;
+    if (env_force("EAGLE_CONV_FORCE", &q.kc, &q.nt, &q.variant) && cin % q.kc == 0 && cout % (16 * q.nt) == 0 && conv_supported(prec, q)) {
+        if (form_of(prec, q).pw == 6) q.wx = 3;              // six sub-tiles per wave: the 8 x 48 tile
+        if (lds_bytes(prec, q) <= 160 * 1024) return q;
+    }
+    // 3x3 stride 2 with Cin = 48 k, Cout = 96 k (HRNet's transition / fuse down-sampling chains): the TRUE stride-2 A-direct forms.  Same box, all
+    // instances per layer (tools/convbench/split_tune, B = 50, best other form -> this one): 96->192 145 -> 108 us, 48->192 80 -> 62, 192->384
+    // 139 -> 102, 96->384 76 -> 55, 48->384 45 -> 33 (variant 14); 48->96 203 -> 175, 96->96 88 -> 70 (variant 15).
+    if (plain_epilogue && c.ks == 3 && c.stride == 2 && cin % 48 == 0 && cout % 96 == 0) return with_ad(c, 16, 14, 15);
+    // 3x3 stride 1 with Cout = 96 k, any Cin = 16 k: the 32x32x16 A-direct forms (round 5), 4 x 32 tiles for BN = 192 (2 x 64 measured 1.5 % slower on 34 x 60),
+    // 4 x 64 tiles for BN = 96 on maps wider than 32 columns, else 8 x 32 — same box, three alternating pairs through the whole pipeline against the 16x16x32
+    // forms: 750.0 / 751.0 / 753.4 -> 761.3 / 761.5 / 761.8 frames/s (+1.4 %), 96->96 @68x120 208.5 -> 193.5 us.
+    if (!env_off("EAGLE_CONV_M32") && plain_epilogue && c.ks == 3 && c.stride == 1 && cin % 16 == 0 && cout % 96 == 0) return with_ad(c, 16, 21, wo > 32 ? 24 : 22);
+    for (const Tuned& t : g_tuned_split)
+        if (tuned_match(t, c, wo, &q)) {
+            const Form* f = find_form(prec, q.variant);      // the A-direct kernels: ReLU / none after at most two residual adds, three chunks per loop body
+            if (kind_of(prec, q) == ADIRECT && !(plain_epilogue && cin % (f->sform == S2D ? 16 : 48) == 0)) continue;
+            if (conv_supported(prec, q) && lds_bytes(prec, q) <= 160 * 1024) return q;
+        }
+    if (plain_epilogue && c.ks == 3 && c.stride == 1 && cin % 48 == 0 && cout % 96 == 0) return with_ad(c, 16, 8, 9);      // A-direct, split form (three 16-channel chunks per loop body)
+    // generic kernel, full (variant 0) or half (variant 3) tiles: the (NT, KC) pair with the most MFMA work per staged byte whose LDS footprint lets two
+    // workgroups share a CU
+    static const int skcs[] = {32, 16, 8};
+    long best = -1;
+    c.nt = 1; c.kc = 8; c.variant = 0;
+    for (int variant : {0, 3})
+        for (int nt : g_nts) {
+            if (cout % (16 * nt)) continue;
+            for (int kc : skcs) {
+                if (cin % kc) continue;
+                ConvConfig t = c; t.nt = nt; t.kc = kc; t.variant = variant;
+                if (!conv_supported(prec, t)) continue;
+                if (lds_bytes(prec, t) > 80 * 1024) continue;
+                const int pw = form_of(prec, t).pw;
+                if (nt * pw > 12) continue;                        // registers: 4 accumulator VGPRs per (NT, PW) pair next to twice the fragments of the fp16 kernel
+                const long score = (long)nt * pw * 1000 + kc * 10 + (variant == 0 ? 1 : 0);
+                if (score > best) { best = score; c.nt = nt; c.kc = kc; c.variant = variant; }
             }
         }
-        static const bool sad_on = !(getenv("EAGLE_CONV_AD") && atoi(getenv("EAGLE_CONV_AD")) == 0);
-        static const bool tuned_on = !(getenv("EAGLE_CONV_TUNED") && atoi(getenv("EAGLE_CONV_TUNED")) == 0);
-        // (measured on MI355X: 48->48@135x240 305 / 551 us without / with residual against 273 / 322 us of the generic kernel — an 8 x 32 x 48 item is
-        //  21 K-steps per wave, too little work against the exchange, the epilogue and three barriers; kept for the tuner, off by default)
-        const bool kq_on = getenv("EAGLE_CONV_KQ") && atoi(getenv("EAGLE_CONV_KQ")) != 0;      // (read per call: the parity test switches it on)
-        // EAGLE_CONV_48NR=1 (measured, round 4): the Cout = 48 layers WITHOUT a residual operand (conv1 of every BasicBlock of HRNet's widest branch) on the
-        // 16 x 32 single-buffer A-direct form (variant 13), which is 6 % ahead of the 8 x 48 generic tile on that case in isolation (251 vs 268 us)
-        const bool nr48 = getenv("EAGLE_CONV_48NR") && atoi(getenv("EAGLE_CONV_48NR")) != 0;
-        if (sad_on && nr48 && !any_residual && plain_epilogue && ks == 3 && stride == 1 && cin_pad == 48 && cout_pad == 48 && wo > 64) {
-            ConvConfig q = c; q.kc = 16; q.nt = 3; q.variant = 13;
-            return q;
-        }
-        if (sad_on && kq_on && plain_epilogue && ks == 3 && stride == 1 && cin_pad % 48 == 0 && cout_pad % 48 == 0 && cout_pad % 96 != 0) {      // Cout = 48 (144, ...): K split over wave pairs
-            ConvConfig q = c; q.kc = 16; q.nt = 3; q.variant = atoi(getenv("EAGLE_CONV_KQ")) == 13 ? 13 : atoi(getenv("EAGLE_CONV_KQ")) == 19 ? 19 : 12;
-            return q;
-        }
-        // 3x3 stride 2 with Cin = 48 k, Cout = 96 k (HRNet's transition / fuse down-sampling chains): the TRUE stride-2 A-direct forms.  Same box, all
-        // instances per layer (tools/convbench/split_tune, B = 50, best other form -> this one): 96->192 145 -> 108 us, 48->192 80 -> 62, 192->384
-        // 139 -> 102, 96->384 76 -> 55, 48->384 45 -> 33 (variant 14); 48->96 203 -> 175, 96->96 88 -> 70 (variant 15).  EAGLE_CONV_S2T=0: off.
-        static const bool s2t_on = !(getenv("EAGLE_CONV_S2T") && atoi(getenv("EAGLE_CONV_S2T")) == 0);
-        if (sad_on && s2t_on && plain_epilogue && ks == 3 && stride == 2 && cin_pad % 48 == 0 && cout_pad % 96 == 0) {
-            ConvConfig q = c; q.kc = 16;
-            if (cout_pad % 192 == 0) { q.nt = 12; q.variant = 14; } else { q.nt = 6; q.variant = 15; }
-            return q;
-        }
-        // round 5: the 32x32x16 form of the A-direct kernel (variants 21 - 24) for the 3x3 stride-1 layers with Cout = 96 k; any Cin = 16 k.  EAGLE_CONV_M32: 0 off,
-        // 1 the 4 x 32 / 8 x 32 tiles (variants 21 / 22), 2 only BN = 192 (variant 21), 3 only BN = 96 (variant 22), 4: the tile per map — 2 x 64 / 4 x 64 (variants 23 / 24)
-        // where the map is wider than 32 columns and its rows then divide without a larger remainder (34 x 60, 68 x 120), otherwise 21 / 22
-        const int m32 = getenv("EAGLE_CONV_M32") ? atoi(getenv("EAGLE_CONV_M32")) : EAGLE_CONV_M32_DEFAULT;      // (read per call: the parity tests switch it)
-        if (sad_on && m32 && plain_epilogue && ks == 3 && stride == 1 && cin_pad % 16 == 0 && cout_pad % 96 == 0) {
-            ConvConfig q = c; q.kc = 16;
-            if (cout_pad % 192 == 0) { q.nt = 12; q.variant = 21; } else { q.nt = 6; q.variant = 22; }
-            if (m32 == 4 && wo > 32) q.variant += 2;
-            if (m32 == 6) q.variant = q.variant == 21 ? 21 : (wo > 32 ? 24 : 22);      // 6: 4 x 32 tiles for BN = 192 (2 x 64 measured 1.5 % slower on 34 x 60), 4 x 64 for BN = 96 on wide maps
-            if (m32 >= 4 || (q.variant == 21 && m32 != 3) || (q.variant == 22 && m32 != 2)) return q;
-        }
-        if (tuned_on)
-            for (const Tuned& t : g_tuned_split)
-                if (t.ks == ks && t.s == stride && t.cin == cin_pad && t.cout == cout_pad && t.wo == wo) {
-                    ConvConfig q = c; q.kc = t.kc; q.nt = t.nt; q.wx = t.wx; q.variant = t.variant;
-                    if (conv_ad(q) && !(sad_on && plain_epilogue && (conv_ad_s2d(q) ? cin_pad % 16 == 0 : cin_pad % 48 == 0))) continue;       // the A-direct kernels: ReLU / none after at most two residual adds, three chunks per loop body
-                    if (find_inst(precision, q) && lds_bytes(precision, q) <= 160 * 1024) return q;
-                }
-        if (sad_on && plain_epilogue && ks == 3 && stride == 1 && cin_pad % 48 == 0 && cout_pad % 96 == 0) {      // A-direct, split form (three 16-channel chunks per loop body)
-            ConvConfig q = c; q.kc = 16;
-            if (cout_pad % 192 == 0) { q.nt = 12; q.variant = 8; } else { q.nt = 6; q.variant = 9; }
-            return q;
-        }
-        static const int skcs[] = {32, 16, 8};
-        long best = -1;
-        c.nt = 1; c.kc = 8; c.variant = 0;
-        for (int variant : {0, 3})
-            for (int nt : nts) {
-                if (cout_pad % (16 * nt)) continue;
-                for (int kc : skcs) {
-                    if (cin_pad % kc) continue;
-                    ConvConfig t = c; t.nt = nt; t.kc = kc; t.variant = variant;
-                    if (!find_inst(precision, t)) continue;
-                    if (lds_bytes(precision, t) > 80 * 1024) continue;
-                    if (nt * conv_pw(t) > 12) continue;                    // registers: 4 accumulator VGPRs per (NT, PW) pair next to twice the fragments of the fp16 kernel
-                    const long score = (long)nt * conv_pw(t) * 1000 + kc * 10 + (variant == 0 ? 1 : 0);
-                    if (score > best) { best = score; c.nt = nt; c.kc = kc; c.variant = variant; }
-                }
-            }
-        return c;
-    }
-    // developer override (parity tests of a specific kernel variant): EAGLE_CONV_FORCE="kc,nt,variant"
-    if (const char* f = getenv("EAGLE_CONV_FORCE")) {
-        ConvConfig q = c;
-        if (sscanf(f, "%d,%d,%d", &q.kc, &q.nt, &q.variant) == 3 && cin_pad % q.kc == 0 && cout_pad % (16 * q.nt) == 0 &&
-            find_inst(precision, q) && lds_bytes(precision, q) <= 160 * 1024 && (conv_ws(q) ? plain_one : conv_ad(q) ? plain_epilogue : true))
-            return q;
-    }
-    // 3x3 stride-1 layers whose Cout is a multiple of 96 (HRNet's 96 / 192 / 384-channel branches): the A-direct kernel (EAGLE_CONV_AD=0: off)
-    static const bool ad_on = !(getenv("EAGLE_CONV_AD") && atoi(getenv("EAGLE_CONV_AD")) == 0);
-    if (ad_on && plain_epilogue && ks == 3 && stride == 1 && cin_pad % 32 == 0 && cout_pad % 96 == 0) {
-        ConvConfig q = c; q.kc = 32;
-        if (cout_pad % 192 == 0) { q.nt = 12; q.variant = 8; } else { q.nt = 6; q.variant = 9; }
+    return c;
+}
+
+static ConvConfig choose_f16(ConvConfig c, int wo, bool plain_epilogue, bool plain_one)
+{
+    const int prec = EAGLE_PREC_F16, cin = c.cin, cout = c.cout_pad;
+    ConvConfig q = c;
+    if (env_force("EAGLE_CONV_FORCE", &q.kc, &q.nt, &q.variant) && cin % q.kc == 0 && cout % (16 * q.nt) == 0 && conv_supported(prec, q) &&
+        lds_bytes(prec, q) <= 160 * 1024 && (kind_of(prec, q) == WSTAT ? plain_one : kind_of(prec, q) == ADIRECT ? plain_epilogue : true))
         return q;
-    }
-    // 3x3 stride-2 layers with the same Cout: the A-direct kernel over the space-to-depth image (EAGLE_CONV_AD2=0: off)
-    static const bool ad2_on = !(getenv("EAGLE_CONV_AD2") && atoi(getenv("EAGLE_CONV_AD2")) == 0);
-    if (ad_on && ad2_on && plain_epilogue && ks == 3 && stride == 2 && cin_pad % 8 == 0 && cin_pad >= 32 && cout_pad % 96 == 0) {
-        ConvConfig q = c; q.kc = 32;
-        if (cout_pad % 192 == 0) { q.nt = 12; q.variant = 10; } else { q.nt = 6; q.variant = 11; }
-        return q;
-    }
-    // fp16: per-layer table measured on MI355X (tools/autotune_conv.py); shapes not in the table use the heuristic below
+    // 3x3 stride-1 layers whose Cout is a multiple of 96 (HRNet's 96 / 192 / 384-channel branches): the A-direct kernel
+    if (plain_epilogue && c.ks == 3 && c.stride == 1 && cin % 32 == 0 && cout % 96 == 0) return with_ad(c, 32, 8, 9);
+    // 3x3 stride-2 layers with the same Cout: the A-direct kernel over the space-to-depth image
+    if (plain_epilogue && c.ks == 3 && c.stride == 2 && cin % 8 == 0 && cin >= 32 && cout % 96 == 0) return with_ad(c, 32, 10, 11);
+    // per-layer table measured on MI355X (tools/autotune_conv.py); shapes not in the table use the heuristic below
     for (const Tuned& t : g_tuned)
-        if (t.ks == ks && t.s == stride && t.cin == cin_pad && t.cout == cout_pad && t.wo == wo) {
-            ConvConfig q = c; q.kc = t.kc; q.nt = t.nt; q.wx = t.wx; q.variant = t.variant;
-            if (conv_ws(q) && !plain_one) continue;   // the weight-stationary kernel has no SiLU / second-residual / fp32-output epilogue
-            if (find_inst(precision, q) && lds_bytes(precision, q) <= 160 * 1024) return q;
+        if (tuned_match(t, c, wo, &q)) {
+            if (kind_of(prec, q) == WSTAT && !plain_one) continue;   // the weight-stationary kernel has no SiLU / second-residual / fp32-output epilogue
+            if (conv_supported(prec, q) && lds_bytes(prec, q) <= 160 * 1024) return q;
         }
     // heuristic: the (NT, KC) pair with the most work per staged item whose LDS footprint still lets two workgroups share a CU
     static const int kcs[] = {64, 48, 32, 16, 8};
     long best = -1;
     c.nt = 1; c.kc = 8;
-    for (int nt : nts) {
-        if (cout_pad % (16 * nt)) continue;
+    for (int nt : g_nts) {
+        if (cout % (16 * nt)) continue;
         for (int kc : kcs) {
-            if (cin_pad % kc) continue;
+            if (cin % kc) continue;
             ConvConfig t = c; t.nt = nt; t.kc = kc;
-            if (!find_inst(precision, t)) continue;
-            if (lds_bytes(precision, t) > 80 * 1024) continue;
+            if (!conv_supported(prec, t)) continue;
+            if (lds_bytes(prec, t) > 80 * 1024) continue;
             const long score = (long)kc * nt * 1000 + kc;
             if (score > best) { best = score; c.nt = nt; c.kc = kc; }
         }
@@ -293,21 +273,35 @@ ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_
     return c;
 }
 
+ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_pad, int wo, bool plain_epilogue, bool second_residual)
+{
+    // plain_epilogue: no activation before the residual adds, none / ReLU after them, fp16 output.  The weight-stationary kernels also need
+    // at most one residual; the A-direct kernels take two.
+    ConvConfig c;
+    c.ks = ks; c.stride = stride; c.cin = cin_pad; c.cout_pad = cout_pad;
+    c.wx = (wo > 16) ? 2 : 1;
+    if (precision == EAGLE_PREC_F32) return choose_f32(c, wo);
+    if (precision == EAGLE_PREC_F32S) return choose_split(c, wo, plain_epilogue);
+    return choose_f16(c, wo, plain_epilogue, plain_epilogue && !second_residual);
+}
+
 size_t conv_weight_elems(int precision, const ConvConfig& c)
 {
-    if (precision == EAGLE_PREC_F16 && conv_ad(c) && c.stride == 2) return (size_t)(c.cout_pad / (c.nt * 16)) * (4 * c.cin / 32) * 16 * (c.nt * 16) * 8;
     const int bn = c.nt * 16, nblk = c.cout_pad / bn, nch = c.cin / c.kc;
-    if (precision == EAGLE_PREC_F16) return (size_t)nblk * nch * f16_ni(c.ks, c.kc) * 4 * bn * 8;
-    if (precision == EAGLE_PREC_F32S && conv_ad_s2d(c)) return (size_t)nblk * (4 * c.cin / 16) * 6 * 4 * bn * 8;      // 6 K-steps per 16-channel chunk of the space-to-depth image
-    if (precision == EAGLE_PREC_F32S && conv_ad_m32(c)) return (size_t)nblk * (c.cin / 16) * 18 * (bn / 32) * 512;      // 18 steps (tap, hi | lo) per 16-channel chunk, one 1-KiB fragment per 32 output channels
-    if (precision == EAGLE_PREC_F32S && conv_ad(c)) return (size_t)nblk * (c.cin / 16) * 14 * 4 * bn * 8;   // 14 K-steps per 16-channel chunk
-    if (precision == EAGLE_PREC_F32S) return (size_t)nblk * nch * f16_ni(c.ks, c.kc) * 2 * 4 * bn * 8;      // fp16 elements: a hi and a lo block per K-step
-    return (size_t)nblk * nch * c.ks * c.ks * (c.kc / 4) * 4 * bn;
+    switch (form_of(precision, c).wimage) {
+    case W_F16_S2D: return (size_t)nblk * (4 * c.cin / 32) * 16 * bn * 8;
+    case W_F16: return (size_t)nblk * nch * f16_ni(c.ks, c.kc) * 4 * bn * 8;
+    case W_SPLIT_S2D: return (size_t)nblk * (4 * c.cin / 16) * 6 * 4 * bn * 8;      // 6 K-steps per 16-channel chunk of the space-to-depth image
+    case W_SPLIT_M32: return (size_t)nblk * (c.cin / 16) * 18 * (bn / 32) * 512;    // 18 steps (tap, hi | lo) per 16-channel chunk, one 1-KiB fragment per 32 output channels
+    case W_SPLIT_AD: return (size_t)nblk * (c.cin / 16) * 14 * 4 * bn * 8;          // 14 K-steps per 16-channel chunk
+    case W_SPLIT: return (size_t)nblk * nch * f16_ni(c.ks, c.kc) * 2 * 4 * bn * 8;  // fp16 elements: a hi and a lo block per K-step
+    default: return (size_t)nblk * nch * c.ks * c.ks * (c.kc / 4) * 4 * bn;
+    }
 }
 
 void conv_tile_weights(int precision, const ConvConfig& c, const float* w, int cin_real, int cout_real, void* dst, float* descale)
 {
-    const int bn = c.nt * 16, nblk = c.cout_pad / bn, nch = c.cin / c.kc, taps = c.ks * c.ks;
+    const int bn = c.nt * 16, nblk = c.cout_pad / bn, nch = c.cin / c.kc, taps = c.ks * c.ks, wimage = form_of(precision, c).wimage;
     auto W = [&](int tap, int ci, int co) -> float {
         return (ci < cin_real && co < cout_real) ? w[((size_t)tap * cin_real + ci) * cout_real + co] : 0.0f;
     };
@@ -322,7 +316,7 @@ void conv_tile_weights(int precision, const ConvConfig& c, const float* w, int c
         const float scale = std::ldexp(1.0f, sw);
         if (descale) *descale = std::ldexp(1.0f, -(sw + 4));
         _Float16* d = (_Float16*)dst;
-        if (conv_ad_s2d(c)) {
+        if (wimage == W_SPLIT_S2D) {
             // stride 2: [Cout block][s2d chunk][K-step 0..5][q][BN][8].  s2d chunk -> (phase (ry, rx), 16 real channels); K-steps 0..3 = the taps' (tyy, txx)
             // of the 2x2 kernel over the space-to-depth image, lane groups (hi g0, hi g1, hi g0, hi g1); K-steps 4, 5 = the tap' pairs (0|1), (2|3), lane
             // groups (lo g0, lo g1 | lo g0, lo g1).  tap' row 0 is the s2d row above: only its odd phase contributes (ky = 0); row 1: ky = 1 (even phase), 2 (odd).
@@ -343,7 +337,7 @@ void conv_tile_weights(int precision, const ConvConfig& c, const float* w, int c
                                 }
             return;
         }
-        if (conv_ad_m32(c)) {
+        if (wimage == W_SPLIT_M32) {
             // 32x32x16 form: [Cout block][16-channel chunk][tap 0..8][hi | lo][BN / 32 blocks][lane 0..63][8]: lane l of a block's A fragment holds output
             // channel (l & 31) of the block and the chunk's 8-channel group (l >> 5)
             for (int b = 0; b < nblk; ++b)
@@ -359,7 +353,7 @@ void conv_tile_weights(int precision, const ConvConfig& c, const float* w, int c
                                     }
             return;
         }
-        if (conv_ad(c)) {
+        if (wimage == W_SPLIT_AD) {
             // A-direct form: [Cout block][16-channel chunk][K-step 0..13][q][BN][8].  K-steps 0..8 = taps, lane groups (hi g0, hi g1, hi g0, hi g1):
             // against the record slots (hi g0, hi g1, lo g0, lo g1) that is hi*hi + hi*lo.  K-steps 9..13 = tap pairs (0|1, 2|3, 4|5, 6|7, 8|-),
             // lane groups (lo g0, lo g1 at the first tap | lo g0, lo g1 at the second): lo*hi.
@@ -393,7 +387,7 @@ void conv_tile_weights(int precision, const ConvConfig& c, const float* w, int c
                                 }
         return;
     }
-    if (precision == EAGLE_PREC_F16 && conv_ad(c) && c.stride == 2) {
+    if (wimage == W_F16_S2D) {
         // space-to-depth form: [Cout block][chunk of 32 s2d channels][tap' (2x2) * 4 + channel group][BN][8]; s2d channel = phase * Cin + channel,
         // phase = 2 * ry + rx; tap' row 0 is the s2d row above (only its odd phase contributes: ky = 0), tap' row 1 the same row (ky = 1, 2)
         _Float16* d = (_Float16*)dst;
@@ -460,8 +454,8 @@ static void* conv_trash_page()
 void conv_launch(int precision, const ConvLaunch& L, hipStream_t s)
 {
     const ConvConfig& c = L.cfg;
-    const Inst* inst = find_inst(precision, c);
-    if (!inst) fail(EAGLE_E_NOKERNEL, "no conv kernel instance: prec=%d ks=%d s=%d kc=%d nt=%d", precision, c.ks, c.stride, c.kc, c.nt);
+    if (!conv_supported(precision, c)) fail(EAGLE_E_NOKERNEL, "no conv kernel instance: prec=%d ks=%d s=%d kc=%d nt=%d", precision, c.ks, c.stride, c.kc, c.nt);
+    const Form& f = form_of(precision, c);
     ConvArgs a;
     a.x = L.x.p; a.xcs = L.x.cs; a.xoff = L.x.off; a.N = L.x.n; a.H = L.x.h; a.W = L.x.w;
     a.w = L.w; a.bias = L.bias;
@@ -478,27 +472,16 @@ void conv_launch(int precision, const ConvLaunch& L, hipStream_t s)
     if (!a.r1 && a.r2) { a.r1 = a.r2; a.r1cs = a.r2cs; a.r1off = a.r2off; a.r2 = nullptr; }       // a single residual is always operand 1 (IEEE addition is commutative: same bits)
     a.pre_act = L.pre_act; a.post_act = L.post_act; a.out_f32 = L.out_f32 || precision == EAGLE_PREC_F32;
     a.wx = c.wx;
-    const int th = 4 * conv_pw(c) / c.wx, tw = 16 * c.wx;
-    a.tiles_x = (a.Wo + tw - 1) / tw; a.tiles_y = (a.Ho + th - 1) / th;
     a.nchunks = c.cin / c.kc;
     a.zeros = conv_zero_page(); a.trash = conv_trash_page(); a.xcd = 0; a.gy = 1; a.stack = 0;
-    if (precision == EAGLE_PREC_F32) {
-        // row stacking (conv_f32_kernel): stride-1 layers of a batch are tiled as one image of N (Ho + 1) rows
-        const char* se = getenv("EAGLE_F32_STACK");          // (read per launch: the parity test switches it)
-        const bool stack_on = !(se && atoi(se) == 0);
-        if (stack_on && c.stride == 1 && a.N > 1 && a.Ho == a.H) { a.stack = 1; a.tiles_y = (a.N * (a.Ho + 1) + th - 1) / th; }
-        // raw buffer descriptors with 32-bit byte offsets for the activation loads
-        if ((size_t)a.N * a.H * a.W * a.xcs * 4 >= ((size_t)1 << 31)) fail(EAGLE_E_INVALID, "fp32 conv: the input tensor of %d frames reaches 2 GiB; use a smaller device batch", a.N);
-    }
     a.am = L.am_slot ? *L.am_slot : nullptr; a.am_cs = c.cout_pad;
     a.sat = (L.sat_slot && precision == EAGLE_PREC_F32S) ? *L.sat_slot : nullptr;
-    if (conv_ad(c)) {                                       // A-direct: persistent over XCD-contiguous item ranges, two workgroups per CU
-        const bool split = precision == EAGLE_PREC_F32S;
-        if (a.out_f32 || a.pre_act != 0 || a.post_act > 1 || L.am_slot || c.kc != (split ? 16 : 32) || c.ks != 3 || c.stride != ((conv_ad_s2d(c) || conv_ad_s2t(c)) ? 2 : 1) || (split && !conv_ad_s2d(c) && !conv_ad_m32(c) && c.cin % 48) || (split && (conv_ad_s2d(c) || conv_ad_m32(c)) && c.cin % 16) || (conv_ad_m32(c) && !split) || (conv_ad_s2t(c) && !split))
-            fail(EAGLE_E_NOKERNEL, "A-direct conv needs 3x3, kc = 32 (16 in the split family, stride 1 only), 2-byte / split output, pre_act none, post_act in {none, ReLU}");
-        if (conv_ad_s2d(c)) a.nchunks = split ? 4 * c.cin / 16 : 4 * c.cin / 32;      // chunks of the space-to-depth image
-        const int thh = conv_ad_rows(c);
-        a.tiles_x = (a.Wo + conv_ad_tw(c) - 1) / conv_ad_tw(c); a.tiles_y = (a.Ho + thh - 1) / thh;
+    if (f.kind == ADIRECT) {
+        // the split forms with 14 K-steps per chunk take three chunks per loop body
+        if (a.out_f32 || a.pre_act != 0 || a.post_act > 1 || L.am_slot || (precision == EAGLE_PREC_F32S && c.cin % (f.wimage == W_SPLIT_AD ? 48 : 16)))
+            fail(EAGLE_E_NOKERNEL, "A-direct conv needs 2-byte / split output, pre_act none, post_act in {none, ReLU} and, in the split family, Cin = 16 k (48 k for variants 8, 9 and 12 - 15)");
+        if (f.sform == S2D) a.nchunks = 4 * c.cin / c.kc;  // chunks of the space-to-depth image
+        a.tiles_x = (a.Wo + f.cols - 1) / f.cols; a.tiles_y = (a.Ho + f.rows - 1) / f.rows;
         a.gy = c.cout_pad / (c.nt * 16);
         const size_t lim = (size_t)1 << 31;
         if ((size_t)a.N * a.H * a.W * a.xcs * 2 >= lim || (size_t)a.N * a.Ho * a.Wo * std::max(std::max(a.ycs, a.r1 ? a.r1cs : 0), a.r2 ? a.r2cs : 0) * 2 >= lim)
@@ -506,18 +489,25 @@ void conv_launch(int precision, const ConvLaunch& L, hipStream_t s)
         const int nres = (a.r1 ? 1 : 0) + (a.r2 ? 1 : 0);
         const int items = a.tiles_x * a.tiles_y * a.N * a.gy;
         const bool deep = items <= 256;                     // at most one workgroup per CU: the deep weight ring (conv_ad_split32.hip)
-        const ConvKernel fn = conv_ad_m32(c) ? (conv_ad_tw(c) == 64 ? conv_ad_split32_kernel_w64(conv_ad_wide(c), nres, deep) : conv_ad_split32_kernel(conv_ad_wide(c), nres, deep)) : (split && conv_ad_s2t(c)) ? conv_ad_split_kernel_s2t(c.variant == 14, nres) : (split && c.stride == 2) ? conv_ad_split_kernel_s2(conv_ad_wide(c), nres) : (split && c.variant == 13) ? conv_ad_split_kernel48sb(nres) : (split && c.variant == 19) ? conv_ad_split_kernel48ring(nres) : (split && c.variant == 12) ? conv_ad_split_kernel48(nres) : split ? conv_ad_split_kernel(conv_ad_wide(c), nres) : c.stride == 2 ? conv_ad_kernel_s2(conv_ad_wide(c), nres) : conv_ad_kernel_s1(conv_ad_wide(c), nres);
-        ensure_max_dynamic_lds((const void*)fn, 160 * 1024);
+        // the attributes of both ring depths: a graph captured at a new frame count may switch depth, and a capture sets no function attribute
+        for (bool d : {false, true}) ensure_max_dynamic_lds((const void*)f.get(nres, d), 160 * 1024);
         // workgroups per launch: one per item (the hardware hands a queued workgroup to whichever CU frees a slot: dynamic balance) rather than 512
         // resident ones walking static item ranges — same box, alternating: 774.4 / 774.5 -> 779.0 / 780.7 frames/s, 96->96 209.9 -> 204.4 us,
-        // 192->192 180.3 -> 177.2 (768 workgroups: 707 frames/s — 1.5 rounds of uneven ranges).  EAGLE_CONV_AD_SLOTS=512 restores the persistent form.
-        static const int slots = getenv("EAGLE_CONV_AD_SLOTS") ? atoi(getenv("EAGLE_CONV_AD_SLOTS")) : (1 << 30);
-        // variant 19 (one workgroup per CU by its LDS footprint): persistent, so that the halo ring's prefetch runs on from item to item
-        hipLaunchKernelGGL(fn, dim3(std::min(items, c.variant == 19 ? 256 : slots)), dim3(256), lds_bytes(precision, c), s, a);
+        // 192->192 180.3 -> 177.2 (768 workgroups: 707 frames/s — 1.5 rounds of uneven ranges).  grid_cap: persistent forms (variant 19).
+        hipLaunchKernelGGL(f.get(nres, deep), dim3(f.grid_cap ? std::min(items, f.grid_cap) : items), dim3(256), lds_bytes(precision, c), s, a);
         HIP_CHECK(hipGetLastError());
         return;
     }
-    if (a.am && (!prec_is_f16_kernels(precision) || conv_ws(c)))
+    const int th = 4 * f.pw / c.wx, tw = 16 * c.wx;
+    a.tiles_x = (a.Wo + tw - 1) / tw; a.tiles_y = (a.Ho + th - 1) / th;
+    if (precision == EAGLE_PREC_F32) {
+        // row stacking (conv_f32_kernel): stride-1 layers of a batch are tiled as one image of N (Ho + 1) rows
+        if (!env_off("EAGLE_F32_STACK") && c.stride == 1 && a.N > 1 && a.Ho == a.H) { a.stack = 1; a.tiles_y = (a.N * (a.Ho + 1) + th - 1) / th; }
+        // raw buffer descriptors with 32-bit byte offsets for the activation loads
+        if ((size_t)a.N * a.H * a.W * a.xcs * 4 >= ((size_t)1 << 31)) fail(EAGLE_E_INVALID, "fp32 conv: the input tensor of %d frames reaches 2 GiB; use a smaller device batch", a.N);
+    }
+    const bool ws = f.kind == WSTAT;
+    if (a.am && (!prec_is_f16_kernels(precision) || ws))
         fail(EAGLE_E_NOKERNEL, "fused heat-map maxima need the generic fp16 kernel");
     if (prec_is_f16_kernels(precision)) {                   // the fp16 kernels address tensors through raw buffer descriptors with 32-bit byte offsets
         const size_t lim = (size_t)1 << 31;
@@ -525,27 +515,26 @@ void conv_launch(int precision, const ConvLaunch& L, hipStream_t s)
         if ((size_t)a.N * a.H * a.W * a.xcs * 2 >= lim || (size_t)a.N * a.Ho * a.Wo * cs_out * 2 >= lim)
             fail(EAGLE_E_INVALID, "fp16 conv: a tensor of %d frames reaches 2 GiB; use a smaller device batch", a.N);
     }
+    const ConvKernel fn = generic_inst(precision, c)->fn;
     const size_t lds = lds_bytes(precision, c);
-    ensure_max_dynamic_lds((const void*)inst->fn, 160 * 1024);
+    ensure_max_dynamic_lds((const void*)fn, 160 * 1024);
     const int gy = c.cout_pad / (c.nt * 16);
     int gx = a.stack ? a.tiles_x * a.tiles_y : a.tiles_x * a.tiles_y * a.N;
-    if (conv_ws(c)) {                                       // persistent, weight-stationary: 8*gy | grid, as many workgroups as stay resident
+    if (ws) {                                               // persistent, weight-stationary: 8*gy | grid, up to two workgroups per CU
         if (c.kc != c.cin || a.out_f32 || a.r2 || a.pre_act != 0 || a.post_act > 1 || (size_t)a.N * a.H * a.W * a.xcs * 2 >= (1ull << 31) || (size_t)a.N * a.Ho * a.Wo * std::max(a.ycs, a.r1 ? a.r1cs : 0) * 2 >= (1ull << 31))
             fail(EAGLE_E_NOKERNEL, "weight-stationary conv needs kc == cin, fp16 output, at most one residual, pre_act none, post_act in {none, ReLU} and tensors below 2 GiB (kc=%d cin=%d)", c.kc, c.cin);
-        static const int ws_cap = getenv("EAGLE_CONV_WS_PER_CU") ? atoi(getenv("EAGLE_CONV_WS_PER_CU")) : 2;     // developer knob, as above
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(ws_cap, (160 * 1024) / lds));
+        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
         const int unit = 8 * gy;
         gx = std::max(unit, std::min((gx * gy + unit - 1) / unit * unit, 256 * per_cu / unit * unit));
     }
     a.gy = gy;
-    static const int xcd_env = getenv("EAGLE_CONV_XCD") ? atoi(getenv("EAGLE_CONV_XCD")) : 1;
     // 1x1 layers with several Cout blocks re-read their input tile once per block: in tile-major / block-minor order on one XCD the
     // re-reads hit that XCD's L2 instead of HBM
-    a.xcd = (prec_is_f16_kernels(precision) && !conv_ws(c) && (c.ks == 3 || (c.ks == 1 && gy > 1)) && xcd_env) ? 1 : 0;
+    a.xcd = (prec_is_f16_kernels(precision) && !ws && (c.ks == 3 || (c.ks == 1 && gy > 1))) ? 1 : 0;
     dim3 grid(gx, gy);
     if (a.xcd) grid = dim3(gx * gy, 1);
-    if (conv_ws(c)) grid = dim3(gx, 1);
-    hipLaunchKernelGGL(inst->fn, grid, dim3(256), lds, s, a);
+    if (ws) grid = dim3(gx, 1);
+    hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, a);
     HIP_CHECK(hipGetLastError());
 }
 

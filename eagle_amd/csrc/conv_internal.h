@@ -43,19 +43,28 @@ struct BneckArgs {          // bneck.hip; channel strides / offsets in fp16 elem
 
 typedef void (*ConvKernel)(ConvArgs);
 struct Inst { int prec, ks, s, kc, nt, variant; ConvKernel fn; };
-const Inst* conv_inst_part(int part, int* n);       // instance tables of conv_inst_0..3.hip (declared per part below)
-const Inst* conv_inst_part0(int* n); const Inst* conv_inst_part1(int* n); const Inst* conv_inst_part2(int* n); const Inst* conv_inst_part3(int* n);
+const Inst* conv_inst_part0(int* n); const Inst* conv_inst_part1(int* n); const Inst* conv_inst_part2(int* n); const Inst* conv_inst_part3(int* n);      // instance tables of conv_inst_0..3.hip
 const Inst* conv_inst_split0(int* n); const Inst* conv_inst_split1(int* n); const Inst* conv_inst_split2(int* n);      // EAGLE_PREC_F32S instances (conv_inst_s0..2.hip)
-// the A-direct kernel instance for (cout_groups x pixel_groups, number of residual operands): wide = 4 x 1 (BN 192), otherwise 2 x 2 (BN 96)
-ConvKernel conv_ad_kernel_s1(bool wide, int n_res);
-ConvKernel conv_ad_kernel_s2(bool wide, int n_res);
-ConvKernel conv_ad_split_kernel(bool wide, int n_res);      // EAGLE_PREC_F32S form (conv_ad_split.inc), stride 1
-ConvKernel conv_ad_split32_kernel_w64(bool wide, int n_res, bool deep); // ... with the wave's two pixel blocks side by side: BN = 192, tile 2 x 64 (variant 23) / BN = 96, tile 4 x 64 (variant 24)
-ConvKernel conv_ad_split32_kernel(bool wide, int n_res, bool deep);    // the 32x32x16 form (conv_ad_split32.inc): BN = 192, tile 4 x 32 (variant 21) / BN = 96, tile 8 x 32 (variant 22)
-ConvKernel conv_ad_split_kernel48(int n_res);               // the same for Cout = 48 (K split over wave pairs; variant 12)
-ConvKernel conv_ad_split_kernel_s2(bool wide, int n_res);    // stride 2 (variants 10 / 11 of the split family)
-ConvKernel conv_ad_split_kernel_s2t(bool wide, int n_res);   // TRUE stride 2 on a column-plane halo, single halo buffer: BN = 192 (variant 14) / BN = 96 with the K split (variant 15)
-ConvKernel conv_ad_split_kernel48sb(int n_res);             // Cout = 48, 16 x 32 tile, single halo buffer (variant 13)
-ConvKernel conv_ad_split_kernel48ring(int n_res);           // Cout = 48, 16 x 32 tile, two-deep halo ring, one persistent workgroup per CU (variant 19)
+// A-direct kernel getters, one per form of conv.hip's form table: the instance for 0 / 1 / 2 residual operands.  `deep`: the deep weight ring
+// of the 32x32x16 forms (conv_ad_split32.hip); the other forms have one ring depth and ignore it.  bn192 / bn96: a workgroup's Cout block (BN).
+inline int res_slot(int n_res) { return n_res < 0 ? 0 : n_res > 2 ? 2 : n_res; }
+typedef ConvKernel (*ConvKernelGetter)(int n_res, bool deep);
+ConvKernel conv_ad_kernel_s1_bn192(int n_res, bool deep);              // fp16, stride 1 (variants 8 / 9)
+ConvKernel conv_ad_kernel_s1_bn96(int n_res, bool deep);
+ConvKernel conv_ad_kernel_s2_bn192(int n_res, bool deep);              // fp16, stride 2 over the space-to-depth image (variants 10 / 11)
+ConvKernel conv_ad_kernel_s2_bn96(int n_res, bool deep);
+ConvKernel conv_ad_split_kernel_bn192(int n_res, bool deep);           // EAGLE_PREC_F32S form (conv_ad_split.inc), stride 1 (variants 8 / 9)
+ConvKernel conv_ad_split_kernel_bn96(int n_res, bool deep);
+ConvKernel conv_ad_split_kernel_s2_bn192(int n_res, bool deep);        // stride 2 over the space-to-depth image (variants 10 / 11)
+ConvKernel conv_ad_split_kernel_s2_bn96(int n_res, bool deep);
+ConvKernel conv_ad_split_kernel_s2t_bn192(int n_res, bool deep);       // TRUE stride 2 on a column-plane halo, single halo buffer (variant 14) / with the K split (variant 15)
+ConvKernel conv_ad_split_kernel_s2t_bn96(int n_res, bool deep);
+ConvKernel conv_ad_split_kernel48(int n_res, bool deep);               // Cout = 48, K split over wave pairs (variant 12)
+ConvKernel conv_ad_split_kernel48sb(int n_res, bool deep);             // Cout = 48, 16 x 32 tile, single halo buffer (variant 13)
+ConvKernel conv_ad_split_kernel48ring(int n_res, bool deep);           // Cout = 48, 16 x 32 tile, two-deep halo ring, one persistent workgroup per CU (variant 19)
+ConvKernel conv_ad_split32_kernel_bn192(int n_res, bool deep);         // the 32x32x16 form (conv_ad_split32.inc): tile 4 x 32 (variant 21) / 8 x 32 (variant 22)
+ConvKernel conv_ad_split32_kernel_bn96(int n_res, bool deep);
+ConvKernel conv_ad_split32_kernel_w64_bn192(int n_res, bool deep);     // ... with the wave's two pixel blocks side by side: tile 2 x 64 (variant 23) / 4 x 64 (variant 24)
+ConvKernel conv_ad_split32_kernel_w64_bn96(int n_res, bool deep);
 
 }  // namespace eagle

@@ -341,7 +341,7 @@ struct Builder {
             if (FILE* f = fopen(dump, "a")) { fprintf(f, "%d,%d,%d,%d,%d,%d,%d\n", ks, stride, x.c, cout_pad, x.h, x.w, N); fclose(f); }
         }
         ConvLaunch L;
-        L.cfg = conv_choose(prec, ks, stride, x.c, cout_pad, wo, pre == ACT_NONE && post <= ACT_RELU && !out_f32, r1 && r2, r1 || r2);
+        L.cfg = conv_choose(prec, ks, stride, x.c, cout_pad, wo, pre == ACT_NONE && post <= ACT_RELU && !out_f32, r1 && r2);
         if (!conv_supported(prec, L.cfg))
             fail(EAGLE_E_NOKERNEL, "%s: no kernel instance (ks=%d s=%d kc=%d nt=%d)", cname.c_str(), ks, stride, L.cfg.kc, L.cfg.nt);
         const size_t ne = conv_weight_elems(prec, L.cfg);
@@ -367,7 +367,7 @@ struct Builder {
                      cname.c_str(), t->n, t->h, t->w, t->cs, N);
         L.am_slot = am_slot;
         if (prec == EAGLE_PREC_F32S && !out_f32 && !am_slot) L.sat_slot = &H->cur_sat;
-        if (am_slot) { H->hm_chunks = conv_tiles_per_frame(L.cfg, ho, wo); H->fused_argmax = true; }
+        if (am_slot) { H->hm_chunks = conv_tiles_per_frame(prec, L.cfg, ho, wo); H->fused_argmax = true; }
         L.flop = 2.0 * N * ho * wo * (double)cout * cin * ks * ks;
         const int pr = prec;
         char label[64];
@@ -989,7 +989,8 @@ static void launch_step(EagleHandle* h, int p, const uint8_t* d_src, int n_activ
             CaptureExclusive only_this_thread_talks_to_hip;
             if (only_this_thread_talks_to_hip.ok) {
                 // thread-local capture mode: only THIS thread is held to capture-safe calls while the capture is open (it makes none: the warm-up step above has
-                // set every function attribute and allocated the zero / trash pages).  The global mode made every hipMalloc / hipFree / synchronise of ANY other
+                // set the function attributes of every kernel a step may launch at any frame count — conv_launch sets those of both weight-ring depths, which
+                // depend on the number of work items — and allocated the zero / trash pages).  The global mode made every hipMalloc / hipFree / synchronise of ANY other
                 // thread fail with "operation not permitted when stream is capturing" — a second handle on another host thread, which is how the concurrency
                 // tests and a multi-handle server run — and left this stream in a broken capture (round 5: six tests of the suite, once small batches captured by default)
                 struct CaptureScope {                       // a throw between Begin and End must not leave s_main capturing: end it, drop the graph, stop replaying
@@ -2139,7 +2140,7 @@ int eagle_op_conv2d(int device, int precision, const float* x, int n, int h, int
     const int ho = (h + 2 * (ks / 2) - ks) / stride + 1, wo = (w + 2 * (ks / 2) - ks) / stride + 1;
     ConvLaunch L;
     to_dev(net, precision, x, n, h, w, cin, cin_pad, L.x);
-    L.cfg = conv_choose(precision, ks, stride, cin_pad, cout_pad, wo, pre_act == ACT_NONE && post_act <= ACT_RELU, r1 && r2, r1 || r2);
+    L.cfg = conv_choose(precision, ks, stride, cin_pad, cout_pad, wo, pre_act == ACT_NONE && post_act <= ACT_RELU, r1 && r2);
     if (!conv_supported(precision, L.cfg)) fail(EAGLE_E_NOKERNEL, "no kernel instance ks=%d s=%d kc=%d nt=%d", ks, stride, L.cfg.kc, L.cfg.nt);
     std::vector<char> tiled(conv_weight_elems(precision, L.cfg) * (precision == EAGLE_PREC_F32 ? 4 : 2));
     conv_tile_weights(precision, L.cfg, w_hwio, cin, cout, tiled.data(), &L.descale);

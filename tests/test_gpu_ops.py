@@ -238,10 +238,11 @@ def test_conv_split_a_direct_m32(cin, cout, shape, res, post, tile, monkeypatch)
 @pytest.mark.parametrize("form", ["12", "13", "19"])
 def test_conv_split_a_direct_k_split_48(shape, res, post, form, monkeypatch):
     """The Cout = 48 forms of the split A-direct kernel: variant 12 (K split over wave pairs, partial accumulators exchanged through LDS) and
-    variant 13 (four pixel groups, 16 x 32 tile, one halo buffer).  Selected through EAGLE_CONV_KQ / the tuned table; covered here either way."""
+    variant 13 (four pixel groups, 16 x 32 tile, one halo buffer), variant 19 (the same tile with the two-deep halo ring, persistent), forced through
+    EAGLE_CONV_FORCE."""
     from eagle_amd import lib
     from oracle import prims as P
-    monkeypatch.setenv("EAGLE_CONV_KQ", form)
+    monkeypatch.setenv("EAGLE_CONV_FORCE", f"16,3,{form}")
     n, h, w = shape
     x = _rand((n, h, w, 48), 61)
     wt = _rand((3, 3, 48, 48), 62, (2.0 / (48 * 9)) ** 0.5)
