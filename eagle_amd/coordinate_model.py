@@ -67,12 +67,22 @@ class CoordinateModel:
         return m
 
     # ---- raw records ---------------------------------------------------------------------------------
-    def process_records(self, frames):
-        return self.handle.process(np.asarray(frames))
+    def process_records(self, frames, pixel_format="bgr"):
+        """frames: uint8 BGR [n, h, w, 3] (pixel_format "bgr"), or 4:2:0 decoder output [n, 3h/2, w] ("nv12" / "i420": the records of the BGR
+        frames cv2.cvtColor(..., COLOR_YUV2BGR_NV12 / _I420) gives)."""
+        if pixel_format == "bgr":
+            return self.handle.process(np.asarray(frames))
+        return self.handle.process_yuv(frames, pixel_format)
+
+    def _upload(self, frames, pixel_format):
+        """a dense BGR device clip of the frames (the entries that read resident frames take BGR): 4:2:0 frames are uploaded as they are and converted on the GPU"""
+        return self.handle.upload_bgr(frames, pixel_format)
 
     # ---- reference-shaped API ------------------------------------------------------------------------
     def get_coordinates(self, frames, fps: int, num_homography: int = 1, num_keypoint_detection: int = 1,
-                        verbose: bool = True, calibration: bool = False) -> dict:
+                        verbose: bool = True, calibration: bool = False, pixel_format: str = "bgr") -> dict:
+        """pixel_format: "bgr" (uint8 [n, h, w, 3]) or a decoder's 4:2:0 output "nv12" / "i420" (uint8 [n, 3h/2, w]): the same output as for the BGR
+        frames cv2.cvtColor(..., COLOR_YUV2BGR_NV12 / _I420) gives."""
         homography_interval = max(1, int(fps / max(1, num_homography)))
         keypoint_interval = max(1, int(fps / max(1, num_keypoint_detection)))
         if self.tracker:
@@ -81,13 +91,13 @@ class CoordinateModel:
             self._ensure_tracker_open()
         if calibration or keypoint_interval != 1:
             motion = [] if (self.tracker and self.camera_motion) else None
-            recs = self.flow_records(frames, keypoint_interval, homography_interval, calibration, motion=motion)
+            recs = self.flow_records(frames, keypoint_interval, homography_interval, calibration, motion=motion, pixel_format=pixel_format)
             if self.tracker:
-                self._track(recs, motion[0] if motion else None, frames)
+                self._track(recs, motion[0] if motion else None, frames, pixel_format)
             return {i: records.to_reference_dict(r, i, fps, own_h=bool(r["pad"][0])) for i, r in enumerate(recs)}
-        recs = self.process_records(frames)
+        recs = self.process_records(frames, pixel_format)
         if self.tracker:
-            self._track(recs, self._clip_motion(frames) if self.camera_motion else None, frames)
+            self._track(recs, self._clip_motion(frames, pixel_format) if self.camera_motion else None, frames, pixel_format)
         own = np.ones(len(recs), bool)
         if homography_interval > 1:
             # cm.py:333-367: H is solved on scheduled frames or while the retry flag is set, and carried otherwise.  Every
@@ -140,15 +150,14 @@ class CoordinateModel:
             count.append(k)
         return np.asarray(crops, np.int32).reshape(-1, 5), np.asarray(det, np.int32), np.asarray(count, np.int32)
 
-    def _track(self, recs, warps=None, frames=None):
+    def _track(self, recs, warps=None, frames=None, pixel_format="bgr"):
         """One clip: track ids + smoothed boxes into the records (frame order), pitch coordinates re-projected on the GPU.  Like the
         reference's single BotSort instance (cm.py:66-72, 577) the tracker state lives as long as the model: ids keep increasing over
         successive clips and only the very first frame ever seen activates its tracks at once; ``reset_tracker()`` starts over."""
         self._ensure_tracker_open()
         if self.reid and frames is not None:
             crops, det, count = self.reid_inputs(recs)
-            frames = np.ascontiguousarray(frames, np.uint8)
-            d = self.handle.upload(frames)
+            d = self._upload(frames, pixel_format)
             try:
                 feats = self.handle.reid_features(d, len(frames), crops)
             finally:
@@ -164,10 +173,9 @@ class CoordinateModel:
             return self.handle.clip_motion_ecc(0, n, carry=True)
         return self.handle.clip_motion(0, n)
 
-    def _clip_motion(self, frames):
+    def _clip_motion(self, frames, pixel_format="bgr"):
         """[n, 6] camera motions of a clip that is not in a clip session yet: gray pyramids + sparse LK on the GPU (eagle_clip_open / _motion)."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        d = self.handle.upload(frames)
+        d = self._upload(frames, pixel_format)
         try:
             self.handle.clip_open(d, len(frames))
             try:
@@ -177,12 +185,12 @@ class CoordinateModel:
         finally:
             self.handle.free(d)
 
-    def flow_records(self, frames, keypoint_interval, homography_interval, calibration=False, stats=None, keypoint_source=None, motion=None):
+    def flow_records(self, frames, keypoint_interval, homography_interval, calibration=False, stats=None, keypoint_source=None, motion=None,
+                     pixel_format="bgr"):
         """Records of the reference loop in a stateful cadence (cm.py:188-416); see eagle_amd/clip.py."""
-        frames = np.ascontiguousarray(frames, np.uint8)
         if len(frames) == 0:
             return np.zeros(0, lib.RESULT_DTYPE)
-        d = self.handle.upload(frames)
+        d = self._upload(frames, pixel_format)
         try:
             return clip.run_clip(self.handle, d, len(frames), keypoint_interval, homography_interval, calibration, stats, keypoint_source, motion,
                                  motion_fn=self._session_motion)

@@ -172,6 +172,16 @@ struct EccResult { int ok, iters; double rho; float M[6]; };       // M: 2 x 3 w
 void ecc_small_launch(const uint8_t* gray, uint8_t* small, int n, int h, int w, int dh, int dw, double inv_scale /* 1 / fx */, hipStream_t s);
 // pairs[k] = (template frame or -1 = `carry`, image frame), indices into `small` ([n, h, w] u8)
 void ecc_launch(const uint8_t* small, const uint8_t* carry, const int2* pairs, int n_pairs, EccResult* out, int h, int w, int max_iter, double eps, hipStream_t s);
+// ---- decoder-native input (yuv.hip, K18): NV12 / I420 -> dense BGR [n, h, w, 3] -----------------------------------------------------
+struct YuvArgs {
+    const uint8_t* src;          // frame 0 of the 4:2:0 source (device)
+    uint8_t* dst;                // dense BGR
+    int h, w;                    // even
+    int64_t frame_stride, y_pitch, c_offset, c_pitch, v_offset;     // bytes; v_offset = c_offset + 1 for NV12 (interleaved U V)
+    int c_step;                  // bytes between chroma samples of one plane: 2 NV12, 1 I420
+    int vec;                     // the source allows the 8-byte Y / NV12 and 4-byte I420 loads of the interior strips (checked by the caller)
+};
+void yuv_to_bgr_launch(const YuvArgs& a, int n, hipStream_t s);
 // ---- team colours (teams.hip, K15) ----------------------------------------------------------------------------------------------
 void team_colors_launch(const uint8_t* d_bgr, int n_frames, int fh, int fw, const EagleCrop* d_crops, int n_crops, int* d_counts, hipStream_t s);
 

@@ -207,6 +207,8 @@ struct EagleHandle {
         unsigned* h_sat = nullptr;           // (and of h_out): one memset and one device-to-host copy serve both
         uint8_t* d_frames = nullptr;         // staging copy of the batch (stable pointer for the captured graph)
         uint8_t* h_frames = nullptr;         // pinned ring slot for caller frames that live in pageable memory (allocated on first use)
+        uint8_t* d_yuv = nullptr;            // dense 4:2:0 frames of a host-fed eagle_process_frames_yuv step (allocated on the first such call)
+        uint8_t* h_yuv = nullptr;            // pinned ring slot for 4:2:0 frames that live in pageable memory (allocated on first use)
         bool copy_pending = false;           // ev_copy has been recorded for this slot
         hipEvent_t ev_compute = nullptr, ev_done = nullptr, ev_copy = nullptr;
         // hipGraph instances of this slot's network phase, one per frame count (the source is always d_frames when graphs are on: a device-fed call is staged
@@ -1292,6 +1294,95 @@ static void finalize(EagleHandle* h)
     h->finalized = true;
 }
 
+// ---- decoder-native input (eagle_*_yuv): layout of the caller's 4:2:0 frames ---------------------------------------------------------------
+struct YuvPlane { int64_t off, pitch, rows, row_bytes, dense_off; };
+struct YuvGeom {
+    int fmt, h, w, nplanes;
+    int64_t frame_stride, y_pitch, c_offset, c_pitch, v_offset;
+    int64_t extent;          // bytes of one frame from its start to the end of its last row
+    int64_t dense_bytes;     // h * w * 3 / 2
+    bool dense;              // the layout is the dense default
+    YuvPlane pl[3];          // Y, then UV (NV12) or U, V (I420)
+};
+
+// The one argument check of the four eagle_*yuv* entries: fills the dense defaults and rejects what the kernel cannot read safely.
+static YuvGeom yuv_geometry(int fmt, int h, int w, const EagleYuvLayout* L)
+{
+    if (fmt != EAGLE_PIX_NV12 && fmt != EAGLE_PIX_I420) fail(EAGLE_E_INVALID, "unknown pixel format %d (EAGLE_PIX_NV12 = 1, EAGLE_PIX_I420 = 2)", fmt);
+    if (h < 2 || w < 2 || (h & 1) || (w & 1)) fail(EAGLE_E_INVALID, "4:2:0 frames need an even height and width (got %d x %d)", h, w);
+    EagleYuvLayout l{};
+    if (L) l = *L;
+    const int64_t lim = (int64_t)1 << 40;
+    const int64_t* f = &l.frame_stride;
+    static const char* names[5] = {"frame_stride", "y_pitch", "c_offset", "c_pitch", "v_offset"};
+    for (int k = 0; k < 5; ++k)
+        if (f[k] < 0 || f[k] > lim) fail(EAGLE_E_INVALID, "layout.%s = %lld is negative or out of range", names[k], (long long)f[k]);
+    YuvGeom g{};
+    g.fmt = fmt; g.h = h; g.w = w;
+    const bool nv12 = fmt == EAGLE_PIX_NV12;
+    const int64_t c_row = nv12 ? w : w / 2, c_rows = h / 2;
+    g.y_pitch = l.y_pitch ? l.y_pitch : w;
+    g.c_offset = l.c_offset ? l.c_offset : g.y_pitch * h;
+    g.c_pitch = l.c_pitch ? l.c_pitch : c_row;
+    g.v_offset = nv12 ? 0 : l.v_offset ? l.v_offset : g.c_offset + g.c_pitch * c_rows;
+    if (g.y_pitch < w) fail(EAGLE_E_INVALID, "layout.y_pitch %lld is smaller than a Y row (%d bytes)", (long long)g.y_pitch, w);
+    if (g.c_pitch < c_row) fail(EAGLE_E_INVALID, "layout.c_pitch %lld is smaller than a chroma row (%lld bytes)", (long long)g.c_pitch, (long long)c_row);
+    g.nplanes = nv12 ? 2 : 3;
+    g.pl[0] = {0, g.y_pitch, h, w, 0};
+    g.pl[1] = {g.c_offset, g.c_pitch, c_rows, c_row, (int64_t)h * w};
+    g.pl[2] = {g.v_offset, g.c_pitch, c_rows, c_row, (int64_t)h * w + c_row * c_rows};
+    static const char* pn[2][3] = {{"Y", "UV", ""}, {"Y", "U", "V"}};
+    int64_t end = 0;
+    g.extent = 0;
+    for (int a = 0; a < g.nplanes; ++a) {
+        const YuvPlane& p = g.pl[a];
+        const int64_t a1 = p.off + p.pitch * (p.rows - 1) + p.row_bytes;
+        g.extent = std::max(g.extent, a1);
+        end = std::max(end, p.off + p.pitch * p.rows);
+        for (int b = 0; b < a; ++b) {
+            const YuvPlane& q = g.pl[b];
+            const int64_t b1 = q.off + q.pitch * (q.rows - 1) + q.row_bytes;
+            if (p.off < b1 && q.off < a1)
+                fail(EAGLE_E_INVALID, "the %s plane [%lld, %lld) overlaps the %s plane [%lld, %lld) of the frame", pn[!nv12][a], (long long)p.off, (long long)a1,
+                     pn[!nv12][b], (long long)q.off, (long long)b1);
+        }
+    }
+    g.frame_stride = l.frame_stride ? l.frame_stride : end;
+    if (g.frame_stride < g.extent) fail(EAGLE_E_INVALID, "layout.frame_stride %lld is smaller than a frame's extent (%lld bytes)", (long long)g.frame_stride, (long long)g.extent);
+    g.dense_bytes = (int64_t)h * w * 3 / 2;
+    g.dense = g.y_pitch == w && g.c_offset == (int64_t)h * w && g.c_pitch == c_row && (nv12 || g.v_offset == g.pl[2].dense_off) && g.frame_stride == g.dense_bytes;
+    return g;
+}
+
+static YuvArgs yuv_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst)
+{
+    YuvArgs a{};
+    const bool nv12 = g.fmt == EAGLE_PIX_NV12;
+    a.src = src; a.dst = dst; a.h = g.h; a.w = g.w;
+    a.frame_stride = g.frame_stride; a.y_pitch = g.y_pitch; a.c_offset = g.c_offset; a.c_pitch = g.c_pitch;
+    a.v_offset = nv12 ? g.c_offset + 1 : g.v_offset;
+    a.c_step = nv12 ? 2 : 1;
+    const uint64_t al = (uint64_t)(uintptr_t)src | (uint64_t)g.frame_stride | (uint64_t)g.y_pitch;                 // 8-byte Y loads
+    const uint64_t ac = nv12 ? ((uint64_t)g.c_offset | (uint64_t)g.c_pitch) & 7                                    // 8-byte UV loads
+                             : ((uint64_t)g.c_offset | (uint64_t)g.c_pitch | (uint64_t)g.v_offset) & 3;            // 4-byte U and V loads
+    a.vec = (al & 7) == 0 && ac == 0;
+    return a;
+}
+
+// n frames of layout g at src (device) -> dense BGR at dst, on stream s (timed as "yuv_to_bgr": 4:2:0 read once + BGR written once)
+static void yuv_convert(EagleHandle* h, const YuvGeom& g, const uint8_t* src, int n, uint8_t* dst, hipStream_t s)
+{
+    timed(h, "yuv_to_bgr", (double)n * g.h * g.w * (1.5 + 3.0), s, [&] { yuv_to_bgr_launch(yuv_args(g, src, dst), n, s); });
+}
+
+static void ensure_copy_pool(EagleHandle* h)
+{
+    if (h->pool) return;
+    int nt = getenv("EAGLE_COPY_THREADS") ? atoi(getenv("EAGLE_COPY_THREADS")) : 8;
+    nt = std::max(1, std::min(nt, (int)std::max(1u, std::thread::hardware_concurrency())));
+    h->pool.reset(new CopyPool(nt));
+}
+
 }  // namespace eagle
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1403,6 +1494,7 @@ void eagle_destroy(EagleHandle* h)
         for (auto& kv : sb.graphs) (void)hipGraphExecDestroy(kv.second);
         if (sb.h_sat) (void)hipHostFree(sb.h_sat);       // (h_out lies inside it)
         if (sb.h_frames) (void)hipHostFree(sb.h_frames);
+        if (sb.h_yuv) (void)hipHostFree(sb.h_yuv);           // (d_yuv belongs to the misc Net)
         if (sb.ev_compute) (void)hipEventDestroy(sb.ev_compute);
         if (sb.ev_done) (void)hipEventDestroy(sb.ev_done);
         if (sb.ev_copy) (void)hipEventDestroy(sb.ev_copy);
@@ -1508,11 +1600,7 @@ int eagle_process_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t fram
     (void)hipGetLastError();                               // an unregistered pointer is reported as an error: not one of ours
     if (getenv("EAGLE_H2D_UNSTAGED")) pinned = true;       // developer A/B: round-1 behaviour (pageable memory handed to hipMemcpy2DAsync)
     const bool dense = row_stride == (int64_t)fw * 3 && frame_stride == (int64_t)fsz;
-    if (!pinned && !h->pool) {
-        int nt = getenv("EAGLE_COPY_THREADS") ? atoi(getenv("EAGLE_COPY_THREADS")) : 8;
-        nt = std::max(1, std::min(nt, (int)std::max(1u, std::thread::hardware_concurrency())));
-        h->pool.reset(new CopyPool(nt));
-    }
+    if (!pinned) ensure_copy_pool(h);
     run_pipeline(h, n, out, [&](int p, int i, int na) -> const uint8_t* {
         EagleHandle::StepBuf& sb = h->sb[p];
         hipStream_t sc = h->prof ? h->s_main : h->s_copy;
@@ -1546,6 +1634,99 @@ int eagle_process_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t fram
         return sb.d_frames;
     });
     check_saturation(h, "eagle_process_frames");
+    API_END(h)
+}
+
+int eagle_process_frames_yuv(EagleHandle* h, int format, const uint8_t* src, int n, const EagleYuvLayout* layout, EagleFrameResult* out)
+{
+    if (!h) return EAGLE_E_INVALID;
+    API_BEGIN
+    if (!h->finalized) fail(EAGLE_E_STATE, "eagle_finalize_weights has not been called");
+    if (!src || !out || n < 0) fail(EAGLE_E_INVALID, "bad argument");
+    const YuvGeom g = yuv_geometry(format, h->cfg.frame_h, h->cfg.frame_w, layout);
+    const YuvGeom dg = yuv_geometry(format, h->cfg.frame_h, h->cfg.frame_w, nullptr);      // what the staging buffer holds
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    hipPointerAttribute_t pa;
+    const bool pinned = hipPointerGetAttributes(&pa, src) == hipSuccess && pa.type == hipMemoryTypeHost;
+    (void)hipGetLastError();                               // an unregistered pointer is reported as an error: not one of ours
+    if (!pinned) ensure_copy_pool(h);
+    const size_t fsz = (size_t)g.dense_bytes;
+    if (!h->sb[0].d_yuv) {                                 // first 4:2:0 call of the handle: both slots' staging, before anything of this call is enqueued
+        for (auto& sb : h->sb) sb.d_yuv = (uint8_t*)h->misc->get((size_t)h->cfg.batch * fsz);
+        HIP_CHECK(hipDeviceSynchronize());                 // Net::get zeroes on the null stream, which the handle's non-blocking streams do not wait for
+    }
+    // As in eagle_process_frames the planes of batch k go up on s_copy while batch k-1 computes, into the slot's own d_yuv[p].  Its previous
+    // reader is batch k-2's conversion on s_main, and run_pipeline has collected batch k-2's records (ev_done, behind that conversion on s_main)
+    // before it stages batch k: the upload cannot overwrite planes that are still to be read.  The pinned ring h_yuv[p] waits for the DMA of
+    // batch k-2 (ev_copy) before the workers refill it.  The conversion then writes the slot's BGR staging buffer on s_main, in stream order
+    // behind batch k-2's network phase that read it.
+    run_pipeline(h, n, out, [&](int p, int i, int na) -> const uint8_t* {
+        EagleHandle::StepBuf& sb = h->sb[p];
+        hipStream_t sc = h->prof ? h->s_main : h->s_copy;
+        const uint8_t* s = src + (size_t)i * g.frame_stride;
+        if (!pinned) {
+            if (!sb.h_yuv) HIP_CHECK(hipHostMalloc((void**)&sb.h_yuv, (size_t)h->cfg.batch * fsz, hipHostMallocDefault));
+            if (sb.copy_pending) HIP_CHECK(hipEventSynchronize(sb.ev_copy));      // the DMA of batch k-2 has left this slot
+            const int parts = 2;                                                  // row ranges per plane: keeps every worker busy on small batches
+            h->pool->run(na * g.nplanes * parts, [&](int t) {
+                const int k = t / (g.nplanes * parts), q = t % (g.nplanes * parts);
+                const YuvPlane& pl = g.pl[q / parts];
+                const int64_t r0 = pl.rows * (q % parts) / parts, r1 = pl.rows * (q % parts + 1) / parts;
+                const uint8_t* s0 = s + (size_t)k * g.frame_stride + pl.off;
+                uint8_t* d0 = sb.h_yuv + (size_t)k * fsz + pl.dense_off;
+                if (pl.pitch == pl.row_bytes) memcpy(d0 + r0 * pl.row_bytes, s0 + r0 * pl.pitch, (size_t)((r1 - r0) * pl.row_bytes));
+                else for (int64_t r = r0; r < r1; ++r) memcpy(d0 + r * pl.row_bytes, s0 + r * pl.pitch, (size_t)pl.row_bytes);
+            });
+            HIP_CHECK(hipMemcpyAsync(sb.d_yuv, sb.h_yuv, (size_t)na * fsz, hipMemcpyHostToDevice, sc));
+        } else if (g.dense) {
+            HIP_CHECK(hipMemcpyAsync(sb.d_yuv, s, (size_t)na * fsz, hipMemcpyHostToDevice, sc));
+        } else {
+            for (int k = 0; k < na; ++k)
+                for (int q = 0; q < g.nplanes; ++q) {
+                    const YuvPlane& pl = g.pl[q];
+                    HIP_CHECK(hipMemcpy2DAsync(sb.d_yuv + (size_t)k * fsz + pl.dense_off, (size_t)pl.row_bytes, s + (size_t)k * g.frame_stride + pl.off,
+                                               (size_t)pl.pitch, (size_t)pl.row_bytes, (size_t)pl.rows, hipMemcpyHostToDevice, sc));
+                }
+        }
+        if (!h->prof) {
+            HIP_CHECK(hipEventRecord(sb.ev_copy, sc));
+            sb.copy_pending = true;
+            HIP_CHECK(hipStreamWaitEvent(h->s_main, sb.ev_copy, 0));
+        }
+        yuv_convert(h, dg, sb.d_yuv, na, sb.d_frames, h->s_main);
+        return sb.d_frames;
+    });
+    check_saturation(h, "eagle_process_frames_yuv");
+    API_END(h)
+}
+
+int eagle_process_device_frames_yuv(EagleHandle* h, int format, const void* d_src, int n, const EagleYuvLayout* layout, EagleFrameResult* out)
+{
+    if (!h) return EAGLE_E_INVALID;
+    API_BEGIN
+    if (!h->finalized) fail(EAGLE_E_STATE, "eagle_finalize_weights has not been called");
+    if (!d_src || !out || n < 0) fail(EAGLE_E_INVALID, "bad argument");
+    const YuvGeom g = yuv_geometry(format, h->cfg.frame_h, h->cfg.frame_w, layout);
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    // the caller's frames are read in place, with their layout; the conversion writes the slot's staging buffer (stream order on s_main behind
+    // batch k-2's network phase, the last reader), which is also the source graph replay needs: no device-to-device copy
+    run_pipeline(h, n, out, [&](int p, int i, int na) -> const uint8_t* {
+        yuv_convert(h, g, (const uint8_t*)d_src + (size_t)i * g.frame_stride, na, h->sb[p].d_frames, h->s_main);
+        return h->sb[p].d_frames;
+    });
+    check_saturation(h, "eagle_process_device_frames_yuv");
+    API_END(h)
+}
+
+int eagle_yuv_to_bgr(EagleHandle* h, int format, const void* d_src, int n, const EagleYuvLayout* layout, void* d_bgr)
+{
+    if (!h) return EAGLE_E_INVALID;
+    API_BEGIN
+    if (!d_src || !d_bgr || n < 0) fail(EAGLE_E_INVALID, "bad argument");
+    const YuvGeom g = yuv_geometry(format, h->cfg.frame_h, h->cfg.frame_w, layout);
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    yuv_to_bgr_launch(yuv_args(g, (const uint8_t*)d_src, (uint8_t*)d_bgr), n, h->s_main);
+    HIP_CHECK(hipStreamSynchronize(h->s_main));
     API_END(h)
 }
 
@@ -2261,6 +2442,23 @@ int eagle_op_preprocess_lb(int device, int precision, const uint8_t* bgr, int n,
     HIP_CHECK(hipDeviceSynchronize());
     from_dev(kp, 3, kp_out);
     from_dev(det, 3, det_out);
+    API_END(hh)
+}
+
+int eagle_op_yuv_to_bgr(int device, int format, const uint8_t* src, int n, int h, int w, const EagleYuvLayout* layout, uint8_t* bgr)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!src || !bgr || n < 0) fail(EAGLE_E_INVALID, "bad argument");
+    const YuvGeom g = yuv_geometry(format, h, w, layout);
+    if (n == 0) return EAGLE_OK;
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const uint8_t* d = (const uint8_t*)net.upload(src, (size_t)((n - 1) * g.frame_stride + g.extent));      // exactly the bytes the frames span
+    uint8_t* o = (uint8_t*)net.get((size_t)n * h * w * 3);
+    yuv_to_bgr_launch(yuv_args(g, d, o), n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(bgr, o, (size_t)n * h * w * 3, hipMemcpyDeviceToHost));
     API_END(hh)
 }
 

@@ -50,6 +50,14 @@ class EagleTrackParams(C.Structure):
                 ("track_buffer", C.c_int32), ("frame_rate", C.c_int32)]
 
 
+class EagleYuvLayout(C.Structure):
+    """include/eagle.h EagleYuvLayout: byte offsets / pitches of 4:2:0 frames; 0 = the dense default of that field."""
+    _fields_ = [("frame_stride", C.c_int64), ("y_pitch", C.c_int64), ("c_offset", C.c_int64), ("c_pitch", C.c_int64), ("v_offset", C.c_int64)]
+
+
+PIX_FORMATS = {"nv12": 1, "i420": 2}                                   # include/eagle.h EAGLE_PIX_*
+
+
 class EagleKernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 40), ("ms", C.c_float), ("launches", C.c_int32), ("bytes", C.c_double), ("flop", C.c_double)]
 
@@ -142,6 +150,11 @@ def load():
     L.eagle_clip_motion.argtypes = [vp, i32, i32, C.POINTER(C.c_double)]
     L.eagle_clip_motion_ecc.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(i32)]
     L.eagle_reid_features.argtypes = [vp, vp, i32, vp, i32, fp]
+    yl = C.POINTER(EagleYuvLayout)
+    L.eagle_process_frames_yuv.argtypes = [vp, i32, u8p, i32, yl, vp]
+    L.eagle_process_device_frames_yuv.argtypes = [vp, i32, vp, i32, yl, vp]
+    L.eagle_yuv_to_bgr.argtypes = [vp, i32, vp, i32, yl, vp]
+    L.eagle_op_yuv_to_bgr.argtypes = [i32, i32, u8p, i32, i32, i32, yl, u8p]
     L.eagle_track_frames_reid.argtypes = [vp, vp, i32, C.POINTER(C.c_double), fp, C.POINTER(i32), C.POINTER(i32)]
     _lib = L
     return L
@@ -153,7 +166,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_set_profiling", "eagle_get_timings", "eagle_get_kernel_times", "eagle_op_conv2d", "eagle_op_bottleneck", "eagle_op_fuse_sum", "eagle_op_preprocess", "eagle_op_preprocess_lb",
            "eagle_op_find_homography", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
            "eagle_clip_set_keypoints", "eagle_clip_flow", "eagle_clip_run", "eagle_clip_fetch", "eagle_debug", "eagle_track_open", "eagle_track_frames", "eagle_track_frames_cmc", "eagle_clip_motion_ecc", "eagle_clip_motion", "eagle_team_colors",
-           "eagle_reid_features", "eagle_track_frames_reid"]
+           "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
+           "eagle_op_yuv_to_bgr"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -320,6 +334,80 @@ class Handle:
             out = np.zeros(n, RESULT_DTYPE)
         self._check_records(self.L.eagle_process_device_frames(self._h, dptr, n, out.ctypes.data_as(C.c_void_p)), "process_device_frames", out)
         return out
+
+    # --- decoder-native input: 4:2:0 frames (include/eagle.h, eagle_*_yuv) ---------------------------------
+    def _yuv_frames(self, frames, fmt, layout, n):
+        """-> (uint8 array the library reads, frame count, EagleYuvLayout or None).  [n, 3h/2, w] / [3h/2, w] is the cv2 / numpy convention
+        (dense); a flat buffer (a decoder's surface, e.g. host_buffer()) needs its layout and n."""
+        h, w = self.cfg.frame_h, self.cfg.frame_w
+        a = np.asarray(frames)
+        if a.dtype != np.uint8:
+            raise EagleError(f"4:2:0 frames must be uint8 (got {a.dtype})")
+        if a.ndim in (2, 3):
+            if a.ndim == 2:
+                a = a[None]
+            if a.shape[1:] != (h * 3 // 2, w):
+                raise EagleError(f"4:2:0 frame shape {a.shape[1:]} does not match the handle ({h * 3 // 2}, {w})")
+            if n is not None and n != len(a):
+                raise EagleError(f"n = {n} but {len(a)} frames were given")
+            a, n = np.ascontiguousarray(a), len(a)
+        elif a.ndim == 1:
+            if layout is None or n is None:
+                raise EagleError("a flat 4:2:0 buffer needs an explicit layout and frame count n")
+            a = np.ascontiguousarray(a)
+            need = yuv_span(fmt, h, w, layout, n)
+            if a.nbytes < need:
+                raise EagleError(f"the buffer holds {a.nbytes} bytes, {n} frames of this layout span {need}")
+        else:
+            raise EagleError(f"4:2:0 frames: [n, 3h/2, w], [3h/2, w] or a flat buffer (got shape {a.shape})")
+        return a, n, _yuv_layout(layout)
+
+    def process_yuv(self, frames, fmt="nv12", layout=None, out=None, n=None):
+        """NV12 / I420 frames (host memory) -> records equal to process() of the BGR frames cv2.cvtColor(yuv, COLOR_YUV2BGR_NV12 / _I420) gives.
+        ``frames``: uint8 [n, 3h/2, w] or [3h/2, w] (cv2 / numpy convention), or a flat buffer such as host_buffer() filled by a decoder together
+        with ``layout`` (dict or EagleYuvLayout: frame_stride, y_pitch, c_offset, c_pitch, v_offset in bytes, 0 = dense default) and ``n``."""
+        a, n, lay = self._yuv_frames(frames, fmt, layout, n)
+        if out is None:
+            out = np.zeros(n, RESULT_DTYPE)
+        assert out.dtype == RESULT_DTYPE and len(out) >= n and out.flags.c_contiguous
+        self._check_records(self.L.eagle_process_frames_yuv(self._h, _pix(fmt), C.cast(a.ctypes.data, C.POINTER(C.c_uint8)), n,
+                                                            None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p)), "process_frames_yuv", out)
+        return out
+
+    def process_device_yuv(self, dptr, n, fmt="nv12", layout=None, out=None):
+        """NV12 / I420 frames resident in HBM (read in place with their layout) -> records, as process_yuv."""
+        if out is None:
+            out = np.zeros(n, RESULT_DTYPE)
+        assert out.dtype == RESULT_DTYPE and len(out) >= n and out.flags.c_contiguous
+        lay = _yuv_layout(layout)
+        self._check_records(self.L.eagle_process_device_frames_yuv(self._h, _pix(fmt), dptr, n, None if lay is None else C.byref(lay),
+                                                                   out.ctypes.data_as(C.c_void_p)), "process_device_frames_yuv", out)
+        return out
+
+    def yuv_to_bgr_device(self, d_src, n, fmt="nv12", layout=None):
+        """n NV12 / I420 frames in HBM -> a new dense BGR [n, h, w, 3] device buffer (free it with free()): the clip the entries that take
+        resident BGR frames read (clip_open, reid_features, team_colors)."""
+        d = C.c_void_p()
+        self._check(self.L.eagle_device_alloc(self._h, max(n, 1) * self.cfg.frame_h * self.cfg.frame_w * 3, C.byref(d)), "device_alloc")
+        lay = _yuv_layout(layout)
+        try:
+            self._check(self.L.eagle_yuv_to_bgr(self._h, _pix(fmt), d_src, n, None if lay is None else C.byref(lay), d), "yuv_to_bgr")
+        except EagleError:
+            self.free(d)
+            raise
+        return d
+
+    def upload_bgr(self, frames, pixel_format="bgr"):
+        """Frames (host) -> a dense BGR device clip (free it with free()): uploaded as they are for "bgr", converted on the GPU from "nv12" / "i420"
+        ([n, 3h/2, w]) otherwise."""
+        if pixel_format == "bgr":
+            return self.upload(frames)
+        a, n, _ = self._yuv_frames(frames, pixel_format, None, None)
+        d = self.upload(a)
+        try:
+            return self.yuv_to_bgr_device(d, n, pixel_format)
+        finally:
+            self.free(d)
 
     def reproject(self, recs, Hs, flags):
         """In place: re-project foot points / boundaries of the flagged records with the given homographies (cadence mode)."""
@@ -551,3 +639,63 @@ def op_find_homography(img_pts, world_pts, thresh=5.0, max_iters=2000, lm_iters=
     if rc:
         raise EagleError(f"eagle_op_find_homography failed ({rc}): {L.eagle_last_error(None).decode()}")
     return (H.reshape(3, 3), mask[:n]) if ok.value else (None, None)
+
+
+# --- decoder-native input helpers -------------------------------------------------------------------------------
+def _pix(fmt):
+    if isinstance(fmt, str):
+        if fmt.lower() not in PIX_FORMATS:
+            raise EagleError(f"unknown pixel format {fmt!r} (nv12 or i420)")
+        return PIX_FORMATS[fmt.lower()]
+    return int(fmt)                          # an integer goes to the library as it is (which rejects unknown codes)
+
+
+def _yuv_layout(layout):
+    if layout is None or isinstance(layout, EagleYuvLayout):
+        return layout
+    lay = EagleYuvLayout()
+    for k, v in dict(layout).items():
+        if k not in dict(EagleYuvLayout._fields_):
+            raise TypeError(f"unknown layout field {k}")
+        setattr(lay, k, int(v))
+    return lay
+
+
+def yuv_span(fmt, h, w, layout, n):
+    """Bytes that n frames of this layout span in the caller's buffer: (n - 1) * frame_stride + the last frame's extent, with the dense defaults of
+    include/eagle.h for zero fields (the buffer-size check of the flat-buffer form; the layout itself is checked by the library)."""
+    lay = _yuv_layout(layout) or EagleYuvLayout()
+    nv12 = _pix(fmt) == PIX_FORMATS["nv12"]
+    c_row = w if nv12 else w // 2
+    yp = lay.y_pitch or w
+    co = lay.c_offset or yp * h
+    cp = lay.c_pitch or c_row
+    planes = [(0, yp, h, w), (co, cp, h // 2, c_row)]
+    if not nv12:
+        planes.append((lay.v_offset or co + cp * (h // 2), cp, h // 2, c_row))
+    extent = max(o + p * (r - 1) + b for o, p, r, b in planes)
+    stride = lay.frame_stride or max(o + p * r for o, p, r, _ in planes)
+    return 0 if n <= 0 else (n - 1) * stride + extent
+
+
+def op_yuv_to_bgr(frames, fmt="nv12", layout=None, h=None, w=None, n=None, device=0):
+    """One yuv_to_bgr launch on host buffers (include/eagle.h eagle_op_yuv_to_bgr): uint8 [n, 3h/2, w] / [3h/2, w], or a flat buffer with layout,
+    h, w and n -> BGR uint8 [n, h, w, 3]."""
+    L = load()
+    a = np.asarray(frames)
+    if a.ndim in (2, 3):
+        if a.ndim == 2:
+            a = a[None]
+        n, h, w = a.shape[0], a.shape[1] * 2 // 3, a.shape[2]
+    elif h is None or w is None or n is None:
+        raise EagleError("a flat 4:2:0 buffer needs h, w and n")
+    a = np.ascontiguousarray(a, np.uint8)
+    lay = _yuv_layout(layout)
+    if a.ndim == 1 and a.nbytes < yuv_span(fmt, h, w, lay, n):
+        raise EagleError(f"the buffer holds {a.nbytes} bytes, {n} frames of this layout span {yuv_span(fmt, h, w, lay, n)}")
+    out = np.empty((n, h, w, 3), np.uint8)
+    rc = L.eagle_op_yuv_to_bgr(device, _pix(fmt), a.ctypes.data_as(C.POINTER(C.c_uint8)), n, h, w, None if lay is None else C.byref(lay),
+                               out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc:
+        raise EagleError(f"eagle_op_yuv_to_bgr failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out

@@ -15,21 +15,21 @@ class Processor:
     def __init__(self, model: CoordinateModel = None, **model_kwargs):
         self.model = model or CoordinateModel(**model_kwargs)
 
-    def process(self, frame):
-        """frame: uint8 HWC BGR.  -> {"players": {id: {...}}, "ball": {k: {...}}, "H": 3x3 float64 | None, ...}"""
-        rec = self.model.process_records(np.asarray(frame)[None])[0]
+    def process(self, frame, pixel_format="bgr"):
+        """frame: uint8 HWC BGR, or a decoder's 4:2:0 frame [3h/2, w] with pixel_format "nv12" / "i420".
+        -> {"players": {id: {...}}, "ball": {k: {...}}, "H": 3x3 float64 | None, ...}"""
+        rec = self.model.process_records(np.asarray(frame)[None], pixel_format)[0]
         return records.to_process_dict(rec)
 
-    def process_clip(self, frames):
-        return [records.to_process_dict(r) for r in self.model.process_records(frames)]
+    def process_clip(self, frames, pixel_format="bgr"):
+        return [records.to_process_dict(r) for r in self.model.process_records(frames, pixel_format)]
 
-    def get_team_mapping(self, frames, coords):
+    def get_team_mapping(self, frames, coords, pixel_format="bgr"):
         """The reference post-processor's ``get_team_mapping`` (eagle/processor.py:405-464; its "pretty slow" step) for a clip and the
         ``get_coordinates`` output of that clip: colour segmentation and counting of every player crop on the GPU (eagle_amd/teams.py).
         -> {player_id: 0 | 1}.  Player ids are track ids when the model was built with ``tracker=True``."""
         from . import teams
-        frames = np.ascontiguousarray(frames, np.uint8)
-        d = self.model.handle.upload(frames)
+        d = self.model._upload(frames, pixel_format)
         try:
             return teams.get_team_mapping(self.model.handle, d, coords, n_frames=len(frames))
         finally:

@@ -133,3 +133,41 @@ def clip(seed, n, h=720, w=1280, distinct=None):
         return base
     reps = (n + d - 1) // d
     return np.concatenate([base] * reps)[:n]
+
+
+def _bgr_to_yuv420_planes(frames):
+    """BT.601 limited-range encoder (the integer form of the standard's 8-bit matrix): Y per pixel, U and V from the mean of each 2x2 block.
+    Any reasonable encoder serves here: the library's contract is checked against the decoded BGR frames, not against the source."""
+    f = np.asarray(frames, np.uint8)
+    if f.ndim == 3:
+        f = f[None]
+    n, h, w, _ = f.shape
+    if h % 2 or w % 2:
+        raise ValueError(f"4:2:0 needs an even height and width (got {h} x {w})")
+    b, g, r = (f[..., k].astype(np.int32) for k in range(3))
+    y = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
+    u = ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128
+    v = ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
+
+    def sub(c):
+        return (c.reshape(n, h // 2, 2, w // 2, 2).sum((2, 4)) + 2) // 4
+
+    cl = lambda a: np.clip(a, 0, 255).astype(np.uint8)
+    return cl(y), cl(sub(u)), cl(sub(v))
+
+
+def bgr_to_nv12(frames):
+    """BGR [n, h, w, 3] (or one [h, w, 3] frame) -> NV12 as cv2 / numpy hold it, uint8 [n, 3h/2, w]: the Y plane, then h/2 rows of interleaved
+    U V — what a hardware decoder emits (synthetic decoder output for tests and tools)."""
+    y, u, v = _bgr_to_yuv420_planes(frames)
+    n, h, w = y.shape
+    uv = np.stack([u, v], -1).reshape(n, h // 2, w)
+    return np.concatenate([y, uv], 1)
+
+
+def bgr_to_i420(frames):
+    """BGR [n, h, w, 3] (or one [h, w, 3] frame) -> I420 as cv2 / numpy hold it, uint8 [n, 3h/2, w]: the Y plane, then the U plane and the V plane
+    (h/2 rows of w/2 each, packed two per array row) — what libavcodec's yuv420p emits."""
+    y, u, v = _bgr_to_yuv420_planes(frames)
+    n, h, w = y.shape
+    return np.concatenate([y.reshape(n, -1), u.reshape(n, -1), v.reshape(n, -1)], 1).reshape(n, h * 3 // 2, w)

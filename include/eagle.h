@@ -157,8 +157,9 @@ int eagle_finalize_weights(EagleHandle* h);
 /* The hot path: n BGR uint8 HWC frames (host memory) -> n records.  frame_stride / row_stride in bytes, 0 = dense ([n, h, w, 3] contiguous); a
  * row_stride below 3 * frame_w, a frame_stride below (frame_h - 1) * row_stride + 3 * frame_w or a negative stride is EAGLE_E_INVALID.  This is the call that replaces the reference's
  * per-frame loop over host frames (cm.py:277; frames come from eagle/utils/io.py::read_video).  The upload of batch k+1 overlaps the
- * networks of batch k.  Frames in pinned memory (eagle_host_alloc: what a decoder should write into) are DMA'd in place; frames in
- * pageable memory are first copied into a pinned ring by a few worker threads of the handle (EAGLE_COPY_THREADS, default 8). */
+ * networks of batch k.  Frames in pinned memory (eagle_host_alloc) are DMA'd in place; frames in pageable memory are first copied into a
+ * pinned ring by a few worker threads of the handle (EAGLE_COPY_THREADS, default 8).  A video decoder writes 4:2:0, not BGR: its frames go to
+ * eagle_process_frames_yuv below, and pinned memory is what the decoder should write into there too. */
 int eagle_process_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t frame_stride, int64_t row_stride,
                          EagleFrameResult* out);
 int eagle_host_alloc(EagleHandle* h, int64_t bytes, void** ptr);   /* pinned host memory for frames */
@@ -170,6 +171,35 @@ int eagle_process_device_frames(EagleHandle* h, const void* d_bgr, int n, EagleF
 int eagle_device_alloc(EagleHandle* h, int64_t bytes, void** dptr);
 int eagle_device_free(EagleHandle* h, void* dptr);
 int eagle_device_upload(EagleHandle* h, void* dptr, const void* src, int64_t bytes);
+
+/* ---- decoder-native input: 4:2:0 frames as video decoders emit them ------------------------------------------------------------------
+ * EAGLE_PIX_NV12: a Y plane, then one plane of interleaved U V at half resolution (hardware decoders: VCN through VA-API, FFmpeg's hwaccel paths).
+ * EAGLE_PIX_I420: a Y plane, then a U plane, then a V plane at half resolution (libavcodec yuv420p, PyAV's to_ndarray()).
+ * Each frame is converted on the GPU (yuv.hip) to exactly the BGR bytes of cv2.cvtColor(yuv, COLOR_YUV2BGR_NV12 / _I420) — OpenCV's integer
+ * BT.601 limited-range path, one chroma sample per 2x2 block — so every record equals that of eagle_process_frames on those BGR frames.
+ * frame_h and frame_w must be even.  A layout field of 0 takes the dense default: y_pitch = w, c_offset = y_pitch * h, c_pitch = w (NV12) or w / 2
+ * (I420), v_offset = c_offset + c_pitch * h / 2, frame_stride = the end of the last plane.  A negative field, a pitch below its plane's row, planes
+ * that overlap within a frame or a frame_stride below the frame's extent is EAGLE_E_INVALID (eagle_last_error says which). */
+#define EAGLE_PIX_NV12 1
+#define EAGLE_PIX_I420 2
+typedef struct EagleYuvLayout {      /* bytes; 0 = the dense default for that field */
+    int64_t frame_stride;            /* frame k starts at src + k * frame_stride */
+    int64_t y_pitch;                 /* Y rows (h rows of w bytes) */
+    int64_t c_offset;                /* first chroma plane (NV12: UV; I420: U) from the frame start */
+    int64_t c_pitch;                 /* chroma rows (h/2 rows of w bytes for NV12, w/2 for I420) */
+    int64_t v_offset;                /* I420 only: V plane from the frame start, same c_pitch */
+} EagleYuvLayout;
+/* n frames in host memory -> n records, as eagle_process_frames.  Pinned source (eagle_host_alloc: a decoder's output surface): the planes are
+ * DMA'd from it; pageable source: worker threads first pack them into a pinned ring.  The conversion writes the step's BGR staging buffer, so a
+ * YUV call of n frames replays the hipGraph a BGR call of n frames captured.  layout NULL: dense. */
+int eagle_process_frames_yuv(EagleHandle* h, int format, const uint8_t* src, int n, const EagleYuvLayout* layout, EagleFrameResult* out);
+/* Same, the frames already in HBM (a hardware decoder's device surface, read in place with its layout). */
+int eagle_process_device_frames_yuv(EagleHandle* h, int format, const void* d_src, int n, const EagleYuvLayout* layout, EagleFrameResult* out);
+/* Device to device: n frames of the handle's size -> d_bgr, a dense [n, h, w, 3] buffer of the caller (eagle_device_alloc).  For the entries that
+ * take a BGR clip resident in HBM: eagle_clip_open, eagle_reid_features, eagle_team_colors.  Returns when the conversion is done. */
+int eagle_yuv_to_bgr(EagleHandle* h, int format, const void* d_src, int n, const EagleYuvLayout* layout, void* d_bgr);
+/* Operator entry (host buffers in / out, parity tests): n frames of h x w -> bgr [n, h, w, 3]. */
+int eagle_op_yuv_to_bgr(int device, int format, const uint8_t* src, int n, int h, int w, const EagleYuvLayout* layout, uint8_t* bgr);
 
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
