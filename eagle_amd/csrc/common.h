@@ -1,4 +1,4 @@
-// Internal declarations shared by the runtime (graph/weights/api) and the kernel launchers.
+// Internal declarations shared by the runtime (runtime.h: runtime / nets / step / clip / ops_api .hip) and the kernel launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>

@@ -12,7 +12,7 @@
 //                      reflect-101 borders taken on the fly.  All pixel arithmetic is float32 with separate multiplies and adds
 //                      (-ffp-contract=off), all sums are float64 over exact float32 products, like Mat::dot.
 // The pairs of a clip are independent except after a failed alignment (boxmot keeps the OLD template then): the host side of the library
-// (runtime.hip::eagle_clip_motion_ecc) launches all adjacent pairs at once and re-runs the rare pair behind a failure.
+// (clip.hip::eagle_clip_motion_ecc) launches all adjacent pairs at once and re-runs the rare pair behind a failure.
 // Latency-bound by design (a 108 x 192 image per workgroup, ~10 iterations): 1000 pairs fill the 256 CUs four times over.
 #include "common.h"
 #include "resize.h"

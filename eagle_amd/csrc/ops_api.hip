@@ -1,0 +1,211 @@
+// Operator-level entry points (eagle_op_*): one kernel family each, host tensors in and out, for the parity tests.
+#include "runtime.h"
+
+extern "C" {
+
+// ---- operator-level entry points for the parity tests ---------------------------------------------------------------
+static void to_dev(Net& net, int prec, const float* src, int n, int h, int w, int c, int cpad, TView& v)
+{
+    v.n = n; v.h = h; v.w = w; v.c = cpad; v.cs = cpad; v.off = 0; v.f32 = prec_tensor_fmt(prec);
+    const size_t px = (size_t)n * h * w;
+    if (v.f32 == 2) {                                       // [hi x 8][lo x 8] per 8 channels, hi = rn(16 v), lo = rn(16 v - hi)
+        std::vector<_Float16> t(px * cpad * 2, (_Float16)0.f);
+        for (size_t p = 0; p < px; ++p)
+            for (int k = 0; k < c; ++k) {
+                const float sv = src[p * c + k] * 16.0f;
+                const _Float16 hi = (_Float16)sv;
+                t[p * cpad * 2 + (k / 8) * 16 + (k % 8)] = hi;
+                t[p * cpad * 2 + (k / 8) * 16 + 8 + (k % 8)] = (_Float16)(sv - (float)hi);
+            }
+        v.p = net.upload(t.data(), t.size() * 2);
+    } else if (v.f32) {
+        std::vector<float> t(px * cpad, 0.f);
+        for (size_t p = 0; p < px; ++p) for (int k = 0; k < c; ++k) t[p * cpad + k] = src[p * c + k];
+        v.p = net.upload(t.data(), t.size() * 4);
+    } else {
+        std::vector<_Float16> t(px * cpad, (_Float16)0.f);
+        for (size_t p = 0; p < px; ++p) for (int k = 0; k < c; ++k) t[p * cpad + k] = (_Float16)src[p * c + k];
+        v.p = net.upload(t.data(), t.size() * 2);
+    }
+}
+static void from_dev(const TView& v, int c, float* dst)
+{
+    const size_t px = (size_t)v.n * v.h * v.w;
+    if (v.f32 == 2) {
+        std::vector<_Float16> t(px * v.cs * 2);
+        HIP_CHECK(hipMemcpy(t.data(), v.p, t.size() * 2, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < px; ++p)
+            for (int k = 0; k < c; ++k) {
+                const size_t e = p * v.cs * 2 + (size_t)((v.off + k) / 8) * 16 + (v.off + k) % 8;
+                dst[p * c + k] = ((float)t[e] + (float)t[e + 8]) * 0.0625f;
+            }
+    } else if (v.f32) {
+        std::vector<float> t(px * v.cs);
+        HIP_CHECK(hipMemcpy(t.data(), v.p, t.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < px; ++p) for (int k = 0; k < c; ++k) dst[p * c + k] = t[p * v.cs + v.off + k];
+    } else {
+        std::vector<_Float16> t(px * v.cs);
+        HIP_CHECK(hipMemcpy(t.data(), v.p, t.size() * 2, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < px; ++p) for (int k = 0; k < c; ++k) dst[p * c + k] = (float)t[p * v.cs + v.off + k];
+    }
+}
+
+int eagle_op_conv2d(int device, int precision, const float* x, int n, int h, int w, int cin, const float* w_hwio,
+                    const float* bias, int cout, int ks, int stride, int pre_act, const float* r1, const float* r2,
+                    int post_act, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const int g = precision == EAGLE_PREC_F32 ? 4 : 8;
+    const int cin_pad = cin <= g ? g : (cin + 15) / 16 * 16, cout_pad = (cout + 15) / 16 * 16;
+    const int ho = (h + 2 * (ks / 2) - ks) / stride + 1, wo = (w + 2 * (ks / 2) - ks) / stride + 1;
+    ConvLaunch L;
+    to_dev(net, precision, x, n, h, w, cin, cin_pad, L.x);
+    L.cfg = conv_choose(precision, ks, stride, cin_pad, cout_pad, wo, pre_act == ACT_NONE && post_act <= ACT_RELU, r1 && r2);
+    if (!conv_supported(precision, L.cfg)) fail(EAGLE_E_NOKERNEL, "no kernel instance ks=%d s=%d kc=%d nt=%d", ks, stride, L.cfg.kc, L.cfg.nt);
+    std::vector<char> tiled(conv_weight_elems(precision, L.cfg) * (precision == EAGLE_PREC_F32 ? 4 : 2));
+    conv_tile_weights(precision, L.cfg, w_hwio, cin, cout, tiled.data(), &L.descale);
+    L.w = net.upload(tiled.data(), tiled.size());
+    std::vector<float> b(cout_pad, 0.f);
+    for (int i = 0; i < cout; ++i) b[i] = bias[i];
+    L.bias = (const float*)net.upload(b.data(), b.size() * 4);
+    L.y.n = n; L.y.h = ho; L.y.w = wo; L.y.c = cout_pad; L.y.cs = cout_pad; L.y.f32 = prec_tensor_fmt(precision);
+    L.y.p = net.get((size_t)n * ho * wo * cout_pad * L.y.esize());
+    if (r1) to_dev(net, precision, r1, n, ho, wo, cout, cout_pad, L.r1);
+    if (r2) to_dev(net, precision, r2, n, ho, wo, cout, cout_pad, L.r2);
+    L.pre_act = pre_act; L.post_act = post_act;
+    conv_launch(precision, L, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    from_dev(L.y, cout, y);
+    API_END(hh)
+}
+
+int eagle_op_bottleneck(int device, const float* x, int n, int h, int w, int cin, const float* w1, const float* b1, const float* w2, const float* b2,
+                        const float* w3, const float* b3, const float* res, float* y, int reps, float* ms, const float* wd, const float* bd)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    if (!x || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !y || n < 1 || h < 1 || w < 1 || cin % 16 || cin < 16) fail(EAGLE_E_INVALID, "eagle_op_bottleneck: bad argument (Cin must be a multiple of 16)");
+    if ((wd != nullptr) != (bd != nullptr) || (wd && (res || cin != 64))) fail(EAGLE_E_INVALID, "eagle_op_bottleneck: the in-kernel downsample branch takes (wd, bd) together, Cin = 64 and no residual tensor");
+    if (!res && !wd && cin != 256) fail(EAGLE_E_INVALID, "eagle_op_bottleneck: an identity shortcut needs Cin = 256");
+    Net net;
+    BneckLaunch L;
+    to_dev(net, EAGLE_PREC_F32S, x, n, h, w, cin, cin, L.x);
+    if (res) to_dev(net, EAGLE_PREC_F32S, res, n, h, w, 256, 256, L.res); else L.res = L.x;
+    L.y = L.x; L.y.c = L.y.cs = 256; L.y.off = 0; L.y.p = net.get((size_t)n * h * w * 256 * 4);
+    if (wd) L.res = L.y;                                    // (not read)
+    std::vector<_Float16> img;
+    bneck_tile_weights(w1, 1, cin, 64, img, &L.ds1); L.w1 = net.upload(img.data(), img.size() * 2);
+    bneck_tile_weights(w2, 9, 64, 64, img, &L.ds2); L.w2 = net.upload(img.data(), img.size() * 2);
+    std::vector<float> w3x(w3, w3 + 64 * 256), sb3(b3, b3 + 256);
+    if (wd) {                                               // K = 128: [W3 | Wd], bias b3 + bd
+        w3x.insert(w3x.end(), wd, wd + 64 * 256);
+        for (int o = 0; o < 256; ++o) sb3[o] = sb3[o] + bd[o];
+        L.ds_fused = true;
+    }
+    bneck_tile_weights(w3x.data(), 1, wd ? 128 : 64, 256, img, &L.ds3); L.w3 = net.upload(img.data(), img.size() * 2);
+    std::vector<float> sb1(b1, b1 + 64), sb2(b2, b2 + 64);
+    bneck_scale_bias(sb1, L.ds1); bneck_scale_bias(sb2, L.ds2); bneck_scale_bias(sb3, L.ds3);
+    L.b1 = (const float*)net.upload(sb1.data(), 64 * 4); L.b2 = (const float*)net.upload(sb2.data(), 64 * 4); L.b3 = (const float*)net.upload(sb3.data(), 256 * 4);
+    if (getenv("EAGLE_BNECK_TIMING")) L.dbg = (unsigned long long*)net.get(8192 * 8 * 8);      // (developer timing builds: -DEAGLE_BNECK_TIMING)
+    unsigned* op_sat = nullptr; unsigned* const* op_sat_slot = &op_sat;
+    if (getenv("EAGLE_BNECK_OPSAT")) { op_sat = (unsigned*)net.get(sizeof(unsigned) * (size_t)n); L.sat_slot = op_sat_slot; }      // developer: the per-frame saturation counters the pipeline passes
+    bneck_launch(L, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (L.dbg) {
+        std::vector<unsigned long long> t(8192 * 8);
+        HIP_CHECK(hipMemcpy(t.data(), L.dbg, t.size() * 8, hipMemcpyDeviceToHost));
+        double sum[8] = {0}; int nw = 0;
+        for (int b = 0; b < 8192; ++b) { bool any = false; for (int k = 0; k < 8; ++k) { sum[k] += (double)t[b * 8 + k]; any |= t[b * 8 + k] != 0; } nw += any; }
+        if (nw) fprintf(stderr, "[bneck timing] %d workgroups, mean us per workgroup: phase1 %.1f  wait %.1f  epi1 %.1f  phase2 %.1f  epi2 %.1f  phase3 %.1f\n", nw,
+                        sum[0] / nw / 100, sum[1] / nw / 100, sum[2] / nw / 100, sum[3] / nw / 100, sum[4] / nw / 100, sum[5] / nw / 100);
+    }
+    if (reps > 0 && ms) {                                   // developer timing: the launch alone, HIP events on the launch stream
+        hipEvent_t e0, e1;
+        HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+        HIP_CHECK(hipEventRecord(e0, nullptr));
+        for (int i = 0; i < reps; ++i) bneck_launch(L, nullptr);
+        HIP_CHECK(hipEventRecord(e1, nullptr));
+        HIP_CHECK(hipEventSynchronize(e1));
+        HIP_CHECK(hipEventElapsedTime(ms, e0, e1));
+        *ms /= (float)reps;
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    from_dev(L.y, 256, y);
+    API_END(hh)
+}
+
+int eagle_op_fuse_sum(int device, int precision, const float* base, int n, int H, int W, int c, int n_up,
+                      const float* const* ups, const int* up_h, const int* up_w, int relu, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    if (n_up > 3 || c % 8) fail(EAGLE_E_INVALID, "fuse_sum: n_up <= 3 and c %% 8 == 0 required");
+    Net net;
+    TView b, o;
+    to_dev(net, precision, base, n, H, W, c, c, b);
+    FuseUp u[3];
+    for (int i = 0; i < n_up; ++i) to_dev(net, precision, ups[i], n, up_h[i], up_w[i], c, c, u[i].z);
+    o = b; o.p = net.get((size_t)n * H * W * c * b.esize());
+    fuse_sum_launch(b, u, n_up, relu, o, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    from_dev(o, c, y);
+    API_END(hh)
+}
+
+int eagle_op_preprocess(int device, int precision, const uint8_t* bgr, int n, int h, int w, int det_imgsz,
+                        float* kp_out, float* det_out, int* det_hw)
+{
+    return eagle_op_preprocess_lb(device, precision, bgr, n, h, w, det_imgsz, EAGLE_LETTERBOX_RECT, kp_out, det_out, det_hw);
+}
+
+int eagle_op_preprocess_lb(int device, int precision, const uint8_t* bgr, int n, int h, int w, int det_imgsz, int letterbox,
+                           float* kp_out, float* det_out, int* det_hw)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const int cp = precision == EAGLE_PREC_F32 ? 4 : 8;
+    const LetterBox lb = letterbox_geometry(h, w, det_imgsz, letterbox);
+    det_hw[0] = lb.out_h; det_hw[1] = lb.out_w;
+    if (!kp_out || !det_out) return EAGLE_OK;
+    uint8_t* d = (uint8_t*)net.upload(bgr, (size_t)n * h * w * 3);
+    TView kp, det;
+    kp.n = n; kp.h = 540; kp.w = 960; kp.c = kp.cs = cp; kp.f32 = prec_tensor_fmt(precision);
+    det = kp; det.h = lb.out_h; det.w = lb.out_w;
+    kp.p = net.get((size_t)n * 540 * 960 * cp * kp.esize());
+    det.p = net.get((size_t)n * lb.out_h * lb.out_w * cp * det.esize());
+    preprocess_launch(precision, d, n, h, w, kp, det, lb, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    from_dev(kp, 3, kp_out);
+    from_dev(det, 3, det_out);
+    API_END(hh)
+}
+
+int eagle_op_find_homography(int device, const float* img_pts, const float* world_pts, int n, double thresh,
+                             int max_iters, int lm_iters, double* H9, uint8_t* mask, int* ok)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    if (n < 0 || n > EAGLE_MAX_KP) fail(EAGLE_E_INVALID, "0 <= n <= %d required", EAGLE_MAX_KP);
+    Net net;
+    float* di = (float*)net.upload(img_pts, sizeof(float) * 2 * std::max(n, 1));
+    float* dw = (float*)net.upload(world_pts, sizeof(float) * 2 * std::max(n, 1));
+    double* dH = (double*)net.get(72);
+    uint8_t* dm = (uint8_t*)net.get(256);
+    int* dok = (int*)net.get(16);
+    homography_only_launch(di, dw, n, thresh, max_iters, lm_iters, dH, dm, dok, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(H9, dH, 72, hipMemcpyDeviceToHost));
+    if (n > 0) HIP_CHECK(hipMemcpy(mask, dm, n, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(ok, dok, sizeof(int), hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
+}  // extern "C"

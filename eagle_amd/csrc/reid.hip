@@ -7,7 +7,7 @@
 // This file holds the kernels the convolution family does not have: crop + resize + normalise, the 7 x 7 stem, 3 x 3 / stride-2 max-pool,
 // depthwise 3 x 3 (+ BatchNorm + ReLU), the shared channel gate with the four-stream sum, 2 x 2 average pool, and the head (global average
 // -> Linear(128, 512) -> BatchNorm1d -> ReLU).  All 1 x 1 convolutions (three quarters of the multiply-adds) run on the exact fp32 MFMA
-// convolution kernels (conv_f32_kernel); the schedule is built in runtime.hip::build_reid.  fp32 NHWC throughout, channel counts padded to 16
+// convolution kernels (conv_f32_kernel); the schedule is built in nets.hip::build_reid.  fp32 NHWC throughout, channel counts padded to 16
 // (padding channels are written as zeros by every kernel here).  The network is 0.08 GMAC per crop — a few per cent of a frame's HRNet —
 // and only runs when the caller asks for track identities with appearance, so these kernels are written for clarity, one thread per output
 // element, not for a roofline.
