@@ -125,7 +125,8 @@ static void clip_detect_keypoints(EagleHandle* h, int first, int stride, int cou
                 HIP_CHECK(hipMemcpyAsync(sb.d_frames + (size_t)k * fb, c.cv.bgr + (size_t)(first + (k0 + k) * stride) * fb, fb, hipMemcpyDeviceToDevice, h->s_main));
             src = sb.d_frames;
         }
-        preprocess_launch(h->prec, src, na, cf.frame_h, cf.frame_w, h->kp_in, h->det_in, h->lb, h->s_main, 1);
+        h->cur_src = src; h->cur_n = na;
+        if (!h->stem_on) preprocess_launch(h->prec, src, na, cf.frame_h, cf.frame_w, h->kp_in, h->det_in, h->lb, h->s_main, 1);      // (the fused stem reads the frames itself)
         h->cur_parts = sb.parts;
         run_net(h, h->hr.get(), h->s_main, ev_i);
         if (!h->fused_argmax) heat_argmax_launch(h->logits, sb.parts, h->hm_chunks, h->s_main);

@@ -102,6 +102,21 @@ void bneck_tile_weights(const float* w, int taps, int cin, int cout, std::vector
 void bneck_scale_bias(std::vector<float>& b, float descale);      // b /= descale (exact: a power of two): what BneckLaunch::b1 / b2 / b3 must hold
 void bneck_launch(const BneckLaunch& L, hipStream_t s);
 
+// ---- fused input path of HRNet (stem.hip; EAGLE_PREC_F32S): BGR u8 frames -> resize + normalise + conv1 3x3/2 3->64 + ReLU in one launch, no key-point input tensor ----
+struct StemLaunch {
+    const uint8_t* bgr = nullptr;            // dense BGR u8 frames [n, sh, sw, 3] (device)
+    int n = 0, sh = 0, sw = 0;               // frames to process (<= y.n), source size
+    int dh = 540, dw = 960;                  // the resized map conv1 reads
+    const void* w = nullptr;                 // weight image (stem_tile_weights)
+    const float* bias = nullptr;             // folded-BN bias [64]
+    float descale = 1.f;
+    TView y;                                 // [>= n, (dh - 1) / 2 + 1, (dw - 1) / 2 + 1, 64], split format
+    unsigned* const* sat_slot = nullptr;
+};
+bool stem_supported(int precision, int ks, int stride, int cin, int cout);
+void stem_tile_weights(const float* w /* folded fp32 [9][3][64] */, std::vector<_Float16>& out, float* descale);
+void stem_launch(const StemLaunch& L, hipStream_t s);
+
 // ---- other kernels ----------------------------------------------------------------------------------------
 struct LetterBox { int new_h, new_w, top, left, out_h, out_w; };
 LetterBox letterbox_geometry(int h, int w, int imgsz, int square = 0);      // square: EagleConfig::letterbox (auto=False)

@@ -4,6 +4,7 @@
 #include <type_traits>
 #include "common.h"
 #include "dmath.h"
+#include "resize.h"
 
 namespace eagle {
 
@@ -15,46 +16,7 @@ using half8 = __attribute__((ext_vector_type(8))) _Float16;
 //     (b) letter-boxed RGB/255 tensor for the detector (ultralytics LetterBox).
 // u8 resize restates cv2.resize INTER_LINEAR: 2x decimation = area fast path, else 11-bit fixed point.
 // ------------------------------------------------------------------------------------------------------------
-struct ResizeAxis { int s0, s1; int a0, a1; };
-
-__device__ __forceinline__ ResizeAxis lin_coef(int d, int dsize, int ssize)
-{
-    const double scale = (double)ssize / (double)dsize;
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= ssize - 1) { s = ssize - 1; f = 0.f; }
-    ResizeAxis r;
-    r.s0 = s; r.s1 = (s + 1 < ssize) ? s + 1 : s;
-    r.a0 = (int)(short)lrintf((1.f - f) * 2048.f);
-    r.a1 = (int)(short)lrintf(f * 2048.f);
-    return r;
-}
-
-// resized RGB u8 pixel (dy,dx) of an (sh,sw)->(dh,dw) resize; src is BGR
-__device__ __forceinline__ void resize_px(const uint8_t* src, int sh, int sw, int dh, int dw, int dy, int dx, int rgb[3])
-{
-    const size_t rs = (size_t)sw * 3;
-    if (sh == dh && sw == dw) {
-        const uint8_t* p = src + dy * rs + dx * 3;
-        rgb[0] = p[2]; rgb[1] = p[1]; rgb[2] = p[0];
-    } else if (sh == 2 * dh && sw == 2 * dw) {
-        const uint8_t* p = src + (size_t)(2 * dy) * rs + (size_t)(2 * dx) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[2 - c] = (p[c] + p[3 + c] + p[rs + c] + p[rs + 3 + c] + 2) >> 2;
-    } else {
-        const ResizeAxis ax = lin_coef(dx, dw, sw), ay = lin_coef(dy, dh, sh);
-        const uint8_t* r0 = src + ay.s0 * rs; const uint8_t* r1 = src + ay.s1 * rs;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int t0 = r0[ax.s0 * 3 + c] * ax.a0 + r0[ax.s1 * 3 + c] * ax.a1;
-            const int t1 = r1[ax.s0 * 3 + c] * ax.a0 + r1[ax.s1 * 3 + c] * ax.a1;
-            rgb[2 - c] = (((ay.a0 * (t0 >> 4)) >> 16) + ((ay.a1 * (t1 >> 4)) >> 16) + 2) >> 2;
-        }
-    }
-}
-
+// (the resize arithmetic itself lives in resize.h: one definition for K1, the player crops and HRNet's fused input kernel)
 // EAGLE_PREC_F32S tensors: a value v is stored as hi = rn(16 v), lo = rn(16 v - hi) (binary16), 8 channels = [hi x 8][lo x 8] (32 bytes);
 // hi + lo has at most 23 significant bits, so (hi + lo) / 16 is exact in fp32 and re-splitting a loaded value returns the same pair value.
 struct SplitT { char b[4]; };
@@ -94,15 +56,15 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* bgr, int
         int rgb[3];
         if (r < kp_px) {
             const int dy = r / kp.w, dx = r - dy * kp.w;
-            resize_px(src, h, w, kp.h, kp.w, dy, dx, rgb);
-            const float m0 = 0x1.eeb334p+6f, m1 = 0x1.d11eb8p+6f, m2 = 0x1.9e1eb8p+6f;      // f32(mean)*255
-            const float s0 = 0x1.18926cp-6f, s1 = 0x1.1ed5bp-6f, s2 = 0x1.1d8f56p-6f;       // 1/(f32(std)*255)
-            store_px<T>(kp, (size_t)f * kp_px + r, ((float)rgb[0] - m0) * s0, ((float)rgb[1] - m1) * s1, ((float)rgb[2] - m2) * s2);
+            resize_px_strided(src, (size_t)w * 3, h, w, kp.h, kp.w, dy, dx, rgb);
+            float v[3];
+            kp_normalize(rgb, v);
+            store_px<T>(kp, (size_t)f * kp_px + r, v[0], v[1], v[2]);
         } else {
             r -= kp_px;
             const int dy = r / det.w, dx = r - dy * det.w;
             const int yy = dy - lb.top, xx = dx - lb.left;
-            if (yy >= 0 && yy < lb.new_h && xx >= 0 && xx < lb.new_w) resize_px(src, h, w, lb.new_h, lb.new_w, yy, xx, rgb);
+            if (yy >= 0 && yy < lb.new_h && xx >= 0 && xx < lb.new_w) resize_px_strided(src, (size_t)w * 3, h, w, lb.new_h, lb.new_w, yy, xx, rgb);
             else rgb[0] = rgb[1] = rgb[2] = 114;
             store_px<TD>(det, (size_t)f * det_px + r, (float)rgb[0] / 255.0f, (float)rgb[1] / 255.0f, (float)rgb[2] / 255.0f);
         }

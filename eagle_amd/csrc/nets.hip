@@ -166,6 +166,31 @@ struct Builder {
                   [L](hipStream_t s) { bneck_launch(L, s); });
         return L.y;
     }
+    // One launch from the frames to conv1's output (stem.hip): cv2.resize + A.Normalize + relu(bn1(conv1 3x3/2 3->64)).  x_in carries the shape only (no memory);
+    // the frames and their number are read from the handle when the launch is enqueued (cur_src / cur_n)
+    TView stem(const TView& x_in, const std::string& cname, const std::string& bn)
+    {
+        std::vector<float> hwio, bias; int cin, cout, ks;
+        fold(cname, bn, hwio, bias, cin, cout, ks);
+        if (!stem_supported(prec, ks, 2, cin, cout)) fail(EAGLE_E_NOKERNEL, "%s: not the 3x3/2 3->64 convolution of the fused stem", cname.c_str());
+        StemLaunch L;
+        std::vector<_Float16> img;
+        stem_tile_weights(hwio.data(), img, &L.descale);
+        L.w = net->upload(img.data(), img.size() * 2);
+        L.bias = (const float*)net->upload(bias.data(), bias.size() * 4);
+        L.sh = H->cfg.frame_h; L.sw = H->cfg.frame_w; L.dh = x_in.h; L.dw = x_in.w;
+        L.y = act((x_in.h - 1) / 2 + 1, (x_in.w - 1) / 2 + 1, 64);
+        L.sat_slot = &H->cur_sat;
+        refuse_2gib(cname, "layer", {&L.y});
+        const double flop = 2.0 * N * L.y.h * L.y.w * 64.0 * 27;
+        char label[64];
+        snprintf(label, sizeof(label), "conv stem 3x3/2 3->64 @%dx%d%s", L.y.h, L.y.w, label_suffix);
+        EagleHandle* const Hh = H;
+        // algorithmic HBM bytes: the frames once, the output once, weights once
+        emit_conv(label, flop, (double)N * L.sh * L.sw * 3.0 + (double)N * L.y.h * L.y.w * 64 * 4.0 + 27.0 * 64 * 4,
+                  [L, Hh](hipStream_t s) { StemLaunch l = L; l.bgr = Hh->cur_src; l.n = Hh->cur_n; stem_launch(l, s); });
+        return L.y;
+    }
     static double vbytes(const TView& v) { return (double)v.n * v.h * v.w * v.c * (v.f32 ? 4 : 2); }
     void other(std::function<void(hipStream_t)> fn, const char* tag, double bytes = 0)
     {
@@ -264,7 +289,7 @@ static TView build_hrnet(Builder& B, const TView& x_in)
 {
     const int R = ACT_RELU;
     const std::string P = HRP;
-    TView x = B.conv(x_in, P + "conv1", P + "bn1", 2, 0, nullptr, nullptr, R);
+    TView x = B.H->stem_on ? B.stem(x_in, P + "conv1", P + "bn1") : B.conv(x_in, P + "conv1", P + "bn1", 2, 0, nullptr, nullptr, R);
     TView x2 = B.conv(x, P + "conv2", P + "bn2", 2, 0, nullptr, nullptr, R);
     B.release(x); x = x2;
     for (int b = 0; b < 4; ++b) {
@@ -601,7 +626,11 @@ void finalize(EagleHandle* h)
     Builder Bh{h, h->hr.get(), h->prec, 1e-5, B};
     Builder By{h, h->yo.get(), h->det_prec, 1e-3, B};
     By.label_suffix = " d";
-    h->kp_in = Bh.act(540, 960, cin_pad);
+    // the split family's HRNet starts from the frames themselves (stem.hip): its input tensor is a shape without memory
+    const HostTensor& w1 = Bh.W(std::string(HRP) + "conv1.weight");      // [cout, cin, ks, ks]
+    h->stem_on = w1.shape.size() == 4 && stem_supported(h->prec, (int)w1.shape[2], 2, (int)w1.shape[1], (int)w1.shape[0]);
+    if (h->stem_on) { TView v; v.n = B; v.h = 540; v.w = 960; v.c = v.cs = cin_pad; v.f32 = prec_tensor_fmt(h->prec); h->kp_in = v; }
+    else h->kp_in = Bh.act(540, 960, cin_pad);
     h->det_in = By.act(h->lb.out_h, h->lb.out_w, det_cin_pad);
     h->logits = build_hrnet(Bh, h->kp_in);
     build_yolo(By, h->det_in, c.det_variant, h->levels, 5, det_mixed);

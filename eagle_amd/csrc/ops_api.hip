@@ -138,6 +138,33 @@ int eagle_op_bottleneck(int device, const float* x, int n, int h, int w, int cin
     API_END(hh)
 }
 
+int eagle_op_stem(int device, const uint8_t* bgr, int n, int h, int w, int dh, int dw, const float* w1, const float* b1, float* y, uint32_t* sat)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    if (!bgr || !w1 || !b1 || !y || n < 1 || h < 1 || w < 1 || dh < 1 || dw < 1) fail(EAGLE_E_INVALID, "eagle_op_stem: bad argument");
+    if (!stem_supported(EAGLE_PREC_F32S, 3, 2, 3, 64)) fail(EAGLE_E_NOKERNEL, "eagle_op_stem: no kernel");
+    Net net;
+    StemLaunch L;
+    L.bgr = (const uint8_t*)net.upload(bgr, (size_t)n * h * w * 3);
+    L.n = n; L.sh = h; L.sw = w; L.dh = dh; L.dw = dw;
+    std::vector<_Float16> img;
+    stem_tile_weights(w1, img, &L.descale);
+    L.w = net.upload(img.data(), img.size() * 2);
+    L.bias = (const float*)net.upload(b1, 64 * 4);
+    L.y.n = n; L.y.h = (dh - 1) / 2 + 1; L.y.w = (dw - 1) / 2 + 1; L.y.c = L.y.cs = 64; L.y.f32 = 2;
+    L.y.p = net.get((size_t)n * L.y.h * L.y.w * 64 * 4);
+    unsigned* d_sat = (unsigned*)net.get(sizeof(unsigned) * (size_t)n);      // (Net::get returns zeroed memory)
+    unsigned* const* slot = &d_sat;
+    L.sat_slot = slot;
+    stem_launch(L, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    from_dev(L.y, 64, y);
+    if (sat) HIP_CHECK(hipMemcpy(sat, d_sat, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
 int eagle_op_fuse_sum(int device, int precision, const float* base, int n, int H, int W, int c, int n_up,
                       const float* const* ups, const int* up_h, const int* up_w, int relu, float* y)
 {

@@ -198,7 +198,10 @@ struct EagleHandle {
     eagle::Tracker* tracker = nullptr;       // K14 state of the clip being tracked (eagle_track_*)
     std::unique_ptr<CopyPool> pool;          // host-side copy workers (eagle_process_frames from pageable memory)
     // step buffers
-    TView kp_in, det_in, logits;
+    TView kp_in, det_in, logits;             // kp_in.p == nullptr: the fused stem reads the frames itself (stem_on)
+    bool stem_on = false;                    // HRNet's first launch is stem.hip: no key-point half of K1, no kp_in tensor
+    const uint8_t* cur_src = nullptr;        // frames of the step being enqueued (device) and their number: what the stem launch reads
+    int cur_n = 0;
     LetterBox lb;
     int hm_chunks = 64;                      // heat-map partials per channel and frame (fused: output tiles of the head convolution)
     ArgmaxPart* cur_parts = nullptr;         // where the head convolution of the step being enqueued writes its partials (fused K5)

@@ -72,11 +72,13 @@ static void enqueue_compute(EagleHandle* h, int p, const uint8_t* d_src, int n_a
     size_t ev_i = 0;
     HIP_CHECK(hipMemsetAsync(sb.d_sat, 0, sat_pad_bytes(B) + sizeof(EagleFrameResult) * B, h->s_main));      // saturation words + records
     h->cur_sat = sb.d_sat;
-    const double esz = h->prec == EAGLE_PREC_F16 ? 2 : 4;
+    h->cur_src = d_src; h->cur_n = n_active;
+    const double esz = h->prec == EAGLE_PREC_F16 ? 2 : 4, det_esz = h->det_prec == EAGLE_PREC_F16 ? 2 : 4;
     if (!(g_dbg_skip & 16))
-        timed(h, "preprocess", (double)n_active * ((double)c.frame_h * c.frame_w * 3 + (540.0 * 960 + (double)h->lb.out_h * h->lb.out_w) * h->kp_in.c * esz), h->s_main,
+        timed(h, "preprocess", (double)n_active * ((double)c.frame_h * c.frame_w * 3 + (h->stem_on ? 0.0 : 540.0 * 960 * h->kp_in.c * esz) + (double)h->lb.out_h * h->lb.out_w * h->det_in.c * det_esz), h->s_main,
               [&] {
-                  preprocess_launch(h->prec, d_src, n_active, c.frame_h, c.frame_w, h->kp_in, h->det_in, h->lb, h->s_main, 3, h->det_prec);      // one launch, each tensor in its network's format
+                  // one launch, each tensor in its network's format; with the fused stem (stem.hip) only the detector's: HRNet reads the frames itself
+                  preprocess_launch(h->prec, d_src, n_active, c.frame_h, c.frame_w, h->kp_in, h->det_in, h->lb, h->s_main, h->stem_on ? 2 : 3, h->det_prec);
               });
     const bool two = !h->prof;
     hipStream_t sd = two ? h->s_det : h->s_main;

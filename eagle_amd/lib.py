@@ -138,6 +138,7 @@ def load():
     L.eagle_get_kernel_times.argtypes = [vp, C.POINTER(EagleKernelTime), i32, C.POINTER(i32)]
     L.eagle_op_conv2d.argtypes = [i32, i32, fp, i32, i32, i32, i32, fp, fp, i32, i32, i32, i32, fp, fp, i32, fp]
     L.eagle_op_bottleneck.argtypes = [i32, fp, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, i32, fp, fp, fp]
+    L.eagle_op_stem.argtypes = [i32, u8p, i32, i32, i32, i32, i32, fp, fp, fp, C.POINTER(C.c_uint32)]
     L.eagle_op_fuse_sum.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, C.POINTER(fp), C.POINTER(i32), C.POINTER(i32), i32, fp]
     L.eagle_op_preprocess.argtypes = [i32, i32, u8p, i32, i32, i32, i32, fp, fp, C.POINTER(i32)]
     L.eagle_op_preprocess_lb.argtypes = [i32, i32, u8p, i32, i32, i32, i32, i32, fp, fp, C.POINTER(i32)]
@@ -163,7 +164,7 @@ def load():
 EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_destroy", "eagle_last_error", "eagle_get_config", "eagle_resolve_config", "eagle_load_weights",
            "eagle_finalize_weights", "eagle_process_frames", "eagle_process_device_frames", "eagle_device_alloc",
            "eagle_device_free", "eagle_device_upload", "eagle_host_alloc", "eagle_host_free", "eagle_reproject", "eagle_comm_id", "eagle_comm_init", "eagle_gather",
-           "eagle_set_profiling", "eagle_get_timings", "eagle_get_kernel_times", "eagle_op_conv2d", "eagle_op_bottleneck", "eagle_op_fuse_sum", "eagle_op_preprocess", "eagle_op_preprocess_lb",
+           "eagle_set_profiling", "eagle_get_timings", "eagle_get_kernel_times", "eagle_op_conv2d", "eagle_op_bottleneck", "eagle_op_stem", "eagle_op_fuse_sum", "eagle_op_preprocess", "eagle_op_preprocess_lb",
            "eagle_op_find_homography", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
            "eagle_clip_set_keypoints", "eagle_clip_flow", "eagle_clip_run", "eagle_clip_fetch", "eagle_debug", "eagle_track_open", "eagle_track_frames", "eagle_track_frames_cmc", "eagle_clip_motion_ecc", "eagle_clip_motion", "eagle_team_colors",
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
@@ -595,6 +596,23 @@ def op_bottleneck(x, w1, b1, w2, b2, w3, b3, res=None, reps=0, device=0, wd=None
     if rc:
         raise EagleError(f"eagle_op_bottleneck failed ({rc}): {L.eagle_last_error(None).decode()}")
     return (y, ms.value) if reps > 0 else y
+
+
+def op_stem(frames, w1, b1, out_hw=(540, 960), device=0):
+    """The fused input launch of HRNet in the split family (include/eagle.h eagle_op_stem; csrc/stem.hip): BGR u8 frames [n, h, w, 3] -> relu(conv1(normalise(resize)))
+    [n, ho, wo, 64].  Returns (y, sat): sat[i] = lanes of frame i that stored a value beyond the split format's range."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, h, w, _ = frames.shape
+    w1 = np.ascontiguousarray(w1, np.float32); b1 = np.ascontiguousarray(b1, np.float32)
+    assert w1.shape == (3, 3, 3, 64) and b1.shape == (64,), "HWIO weights of HRNet's conv1"
+    dh, dw = out_hw
+    y = np.empty((n, (dh - 1) // 2 + 1, (dw - 1) // 2 + 1, 64), np.float32)
+    sat = np.zeros(n, np.uint32)
+    rc = L.eagle_op_stem(device, frames.ctypes.data_as(C.POINTER(C.c_uint8)), n, h, w, dh, dw, _fp(w1), _fp(b1), _fp(y), sat.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc:
+        raise EagleError(f"eagle_op_stem failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return y, sat
 
 
 def op_fuse_sum(base, ups, relu=True, precision=PREC_F32, device=0):

@@ -321,6 +321,10 @@ int eagle_op_conv2d(int device, int precision, const float* x, int n, int h, int
 int eagle_op_bottleneck(int device, const float* x, int n, int h, int w, int cin, const float* w1, const float* b1, const float* w2, const float* b2,
                         const float* w3, const float* b3, const float* res, float* y, int reps, float* ms,
                         const float* wd /* NULL, or the 1x1 downsample branch [1][1][64][256] computed inside the launch (Cin = 64, res = NULL) */, const float* bd);
+/* The fused input path of HRNet in the split family (stem.hip): y = relu(conv1 3x3/2 3->64 (normalise(resize(bgr, dh x dw)))), BatchNorm already folded into
+ * (w1 HWIO [3][3][3][64], b1); bgr: n dense u8 frames [h][w][3]; y: [n][(dh-1)/2+1][(dw-1)/2+1][64]; sat (or NULL): per frame, the lanes that stored a value
+ * beyond the split format's range (what EagleFrameResult's saturation flag is made of). */
+int eagle_op_stem(int device, const uint8_t* bgr, int n, int h, int w, int dh, int dw, const float* w1, const float* b1, float* y, uint32_t* sat);
 int eagle_op_fuse_sum(int device, int precision, const float* base, int n, int H, int W, int c, int n_up,
                       const float* const* ups, const int* up_h, const int* up_w, int relu, float* y);
 int eagle_op_preprocess(int device, int precision, const uint8_t* bgr, int n, int h, int w, int det_imgsz,
