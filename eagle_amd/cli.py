@@ -5,7 +5,11 @@ the GPU path and write ``raw_coordinates.json`` exactly the way the reference's 
     python -m eagle_amd.cli --frames 10 --fps 5 --out output/synthetic          # synthetic clip (no video decode here)
     python -m eagle_amd.cli --clip frames.npy --fps 25 --out output/myclip       # uint8 [n,h,w,3] BGR frames
 
-Video decode/encode, the pandas post-processor and the annotated video of ``main.py:34-81`` are out of scope
+    python -m eagle_amd.cli --frames 10 --fps 5 --out output/synthetic --annotated      # + annotated.y4m and the team mapping
+
+``--annotated`` writes the annotated video of ``main.py:43-81`` as ``annotated.y4m`` (YUV4MPEG2: uncompressed I420, which common players open
+without a codec), drawn on the GPU from the raw records, and ``metadata.json`` then carries the ``team_mapping`` like the reference's
+(``main.py:37-38``).  Video decode, compressed encode and the pandas post-processor of ``main.py:34-41`` are out of scope
 (SURVEY §8f rows 3-4).  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
@@ -71,6 +75,8 @@ def main(argv=None):
     ap.add_argument("--detector-weights", help="detector checkpoint: a torch state-dict (.pth) with ultralytics key names model.N.*, or an ultralytics .pt whose 'model' entry has .state_dict()")
     ap.add_argument("--synthetic-weights", action="store_true", help="run with seeded RANDOM networks (plumbing / benchmarking only: the coordinates are meaningless)")
     ap.add_argument("--native-fps", type=float, default=None, help="frame rate of --clip: sample it down to --fps the way read_video does (io.py:17-25)")
+    ap.add_argument("--annotated", action="store_true",
+                    help="also write <out>/annotated.y4m (the reference's annotated video, main.py:43-81, as uncompressed YUV4MPEG2) and put the team mapping into metadata.json")
     a = ap.parse_args(argv)
 
     from . import synth
@@ -108,8 +114,15 @@ def main(argv=None):
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "raw_coordinates.json"), "w") as f:
         json.dump(coordinates, f, default=float)
+    meta = {"fps": a.fps, "frames": n, "seconds": dt, "note": "team_mapping needs the post-processor (out of scope)"}
+    if a.annotated:
+        from .annotate import write_y4m
+        from .processor import Processor
+        team_mapping = Processor(model).get_team_mapping(frames, coordinates)
+        write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420"), a.fps)
+        meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
     with open(os.path.join(a.out, "metadata.json"), "w") as f:
-        json.dump({"fps": a.fps, "frames": n, "seconds": dt, "note": "team_mapping needs the post-processor (out of scope)"}, f)
+        json.dump(meta, f, default=str)
     print(f"{n} frames in {dt:.3f} s -> {os.path.join(a.out, 'raw_coordinates.json')}")
     return 0
 

@@ -94,7 +94,8 @@ class CoordinateModel:
             recs = self.flow_records(frames, keypoint_interval, homography_interval, calibration, motion=motion, pixel_format=pixel_format)
             if self.tracker:
                 self._track(recs, motion[0] if motion else None, frames, pixel_format)
-            return {i: records.to_reference_dict(r, i, fps, own_h=bool(r["pad"][0])) for i, r in enumerate(recs)}
+            return self._remember({i: records.to_reference_dict(r, i, fps, own_h=bool(r["pad"][0])) for i, r in enumerate(recs)}, recs,
+                                  np.array([bool(r["pad"][0]) for r in recs], bool))
         recs = self.process_records(frames, pixel_format)
         if self.tracker:
             self._track(recs, self._clip_motion(frames, pixel_format) if self.camera_motion else None, frames, pixel_format)
@@ -118,7 +119,40 @@ class CoordinateModel:
                         Hs[i] = cur
             if flags.any():
                 recs = self.handle.reproject(np.ascontiguousarray(recs), Hs, flags)
-        return {i: records.to_reference_dict(r, i, fps, own_h=bool(own[i])) for i, r in enumerate(recs)}
+        return self._remember({i: records.to_reference_dict(r, i, fps, own_h=bool(own[i])) for i, r in enumerate(recs)}, recs, own)
+
+    # ---- annotated output ----------------------------------------------------------------------------
+    _last = None
+
+    def _remember(self, coords, recs, own):
+        """the records behind the last get_coordinates output (and which frames solved their own homography): annotate() draws from them, the dict is
+        never parsed back"""
+        self._last = (coords, recs, np.asarray(own, bool))
+        return coords
+
+    def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr"):
+        """The frames with their records drawn on them (the reference's annotated video, main.py:43-81; include/eagle.h eagle_annotate_frames):
+        uint8 [n, h, w, 3] for out_format "bgr", [n, 3h/2, w] for "nv12" / "i420".  ``frames`` as get_coordinates takes them (pixel_format "bgr",
+        "nv12" or "i420"); ``coords_or_records``: raw records (process_records / flow_records), or the dict the LAST get_coordinates call of this
+        model returned; team_mapping: Processor.get_team_mapping's {player id: 0 | 1}, or None for a neutral player colour."""
+        if isinstance(coords_or_records, dict):
+            if self._last is None or coords_or_records is not self._last[0]:
+                raise ValueError("annotate() takes raw records, or the dict returned by this model's last get_coordinates call")
+            _, recs, own = self._last
+            recs = np.array(recs, lib.RESULT_DTYPE, copy=True)
+            recs["H_valid"][~own] = 0          # a carried homography: the dict lists every key-point of the frame (cm.py:330,415), and so does the picture
+        else:
+            recs = np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1)
+        if len(recs) != len(frames):
+            raise ValueError(f"{len(frames)} frames but {len(recs)} records")
+        if len(recs) == 0:
+            h, w = self.handle.cfg.frame_h, self.handle.cfg.frame_w
+            return np.zeros((0, h, w, 3) if out_format == "bgr" else (0, h * 3 // 2, w), np.uint8)
+        d = self._upload(frames, pixel_format)
+        try:
+            return self.handle.annotate(d, len(recs), recs, team_mapping, out_format)
+        finally:
+            self.handle.free(d)
 
     def reset_tracker(self):
         """Forget every track: the next clip starts with a fresh tracker (frame counter 0, ids from 1), which is what a new

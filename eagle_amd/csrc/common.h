@@ -197,6 +197,22 @@ struct YuvArgs {
     int vec;                     // the source allows the 8-byte Y / NV12 and 4-byte I420 loads of the interior strips (checked by the caller)
 };
 void yuv_to_bgr_launch(const YuvArgs& a, int n, hipStream_t s);
+// ---- annotated output (annotate.hip, K19): dense BGR + per-frame primitive lists -> BGR / NV12 / I420 in the caller's layout ---------------
+struct AnnotArgs {
+    const uint8_t* src;          // frame 0 of the dense BGR clip (device, read only)
+    uint8_t* dst;                // frame 0 of the output
+    const EaglePrim* prims;      // all frames' primitives (device)
+    const int32_t* offs;         // frame k owns prims[offs[k] .. offs[k + 1]) (device, n + 1 entries)
+    int h, w, fmt;               // EAGLE_PIX_*
+    int64_t frame_stride, y_pitch, c_offset, c_pitch, v_offset;     // bytes, resolved; BGR: y_pitch = row pitch; NV12: v_offset = c_offset + 1
+    int c_step;                  // bytes between chroma samples of one plane: 2 NV12, 1 I420
+    int vec;                     // 4:2:0: the destination allows 8-byte Y / NV12 and 4-byte I420 chroma stores (BGR rows are checked per thread)
+};
+void annotate_launch(const AnnotArgs& a, int n, hipStream_t s);
+// the primitive list of one record (at most EAGLE_MAX_PRIMS entries written to out) -> its length
+int overlay_from_record(const EagleFrameResult& rec, const int32_t* team_ids, const int32_t* team_vals, int n_team, EaglePrim* out);
+// throws EAGLE_E_INVALID for an unknown kind, a coordinate or radius outside the documented range, or a frame with more than EAGLE_MAX_PRIMS
+void check_prims(const EaglePrim* prims, const int32_t* offs, int n);
 // ---- team colours (teams.hip, K15) ----------------------------------------------------------------------------------------------
 void team_colors_launch(const uint8_t* d_bgr, int n_frames, int fh, int fw, const EagleCrop* d_crops, int n_crops, int* d_counts, hipStream_t s);
 

@@ -674,6 +674,9 @@ void finalize(EagleHandle* h)
     h->conv_ev.resize((size_t)h->n_conv * 2);
     for (auto& e : h->conv_ev) HIP_CHECK(hipEventCreate(&e));
     h->weights.clear();      // host copies are no longer needed
+    // Net::get zeroes on the null stream, which the handle's non-blocking streams do not wait for: while another handle keeps the GPU busy a zeroing of the
+    // scratch above (staged frames, NMS keys, records) could still be queued when the first step writes them
+    HIP_CHECK(hipStreamSynchronize(nullptr));
     h->finalized = true;
 }
 

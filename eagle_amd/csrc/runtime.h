@@ -250,6 +250,11 @@ struct EagleHandle {
     // comm
     void* rccl = nullptr; void* comm = nullptr; int rank = 0, world = 1;
     void* gather_buf = nullptr; size_t gather_cap = 0;      // device staging of eagle_gather (send | receive), grown on demand
+    // annotated output (annotate.hip): the primitive lists of the call being run (device), and the device / pinned staging of eagle_annotate_frames.
+    // Grown on demand, the handle's own: an annotate call touches neither the step's staging buffers nor its graphs
+    void* annot_prims = nullptr; size_t annot_prims_cap = 0;
+    uint8_t* annot_out = nullptr; size_t annot_out_cap = 0;
+    uint8_t* annot_ring = nullptr; size_t annot_ring_cap = 0;
 };
 
 namespace eagle {
@@ -258,6 +263,23 @@ void finalize(EagleHandle* h);                                                  
 size_t sat_pad_bytes(int B);                                                    // step.hip
 void run_net(EagleHandle* h, Net* net, hipStream_t s, size_t& ev_i);
 void check_saturation(EagleHandle* h, const char* what);
+// profiling mode: HIP events around fn()'s launches on stream st, accumulated under `name` with their algorithmic bytes by collect_spans; otherwise just fn()
+void timed_launch(EagleHandle* h, const char* name, double bytes, hipStream_t st, const std::function<void()>& fn);
+void collect_spans(EagleHandle* h);                                             // after the stream has been synchronised
+// one plane of a frame in caller memory: `rows` rows of `row_bytes` bytes at off + r * pitch; at dense_off + r * row_bytes in the dense frame
+struct HostPlane { int64_t off, pitch, rows, row_bytes, dense_off; };
+// layout of a caller's frames: 4:2:0 (eagle_*_yuv, and the output of eagle_annotate_*) or, for annotated output only, pitched BGR (one plane)
+struct YuvGeom {
+    int fmt, h, w, nplanes;
+    int64_t frame_stride, y_pitch, c_offset, c_pitch, v_offset;
+    int64_t extent;          // bytes of one frame from its start to the end of its last row
+    int64_t dense_bytes;     // h * w * 3 / 2 (BGR: h * w * 3)
+    bool dense;              // the layout is the dense default
+    HostPlane pl[3];          // Y, then UV (NV12) or U, V (I420); BGR: the frame
+};
+// The one argument check of every entry that takes an EagleYuvLayout: fills the dense defaults and rejects what a kernel cannot read or write safely.
+YuvGeom yuv_geometry(int fmt, int h, int w, const EagleYuvLayout* L, bool output = false);      // output: EAGLE_PIX_BGR is a format too
+bool host_pinned(EagleHandle* h, const void* p);
 void clip_close(EagleHandle* h);                                                // clip.hip
 }  // namespace eagle
 

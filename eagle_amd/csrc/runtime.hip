@@ -151,6 +151,9 @@ void eagle_destroy(EagleHandle* h)
     h->hr.reset(); h->yo.reset(); h->misc.reset(); h->reid.reset();
     if (h->ecc_prev) (void)hipFree(h->ecc_prev);
     if (h->gather_buf) (void)hipFree(h->gather_buf);
+    if (h->annot_prims) (void)hipFree(h->annot_prims);
+    if (h->annot_out) (void)hipFree(h->annot_out);
+    if (h->annot_ring) (void)hipHostFree(h->annot_ring);
     if (h->reid_crops_h) (void)hipHostFree(h->reid_crops_h);
     if (h->reid_feats_h) (void)hipHostFree(h->reid_feats_h);
     if (h->clip_sat_h) (void)hipHostFree(h->clip_sat_h);

@@ -28,6 +28,8 @@ static void timed(EagleHandle* h, const char* name, double bytes, hipStream_t st
     h->spans.push_back(sp);
 }
 
+void timed_launch(EagleHandle* h, const char* name, double bytes, hipStream_t st, const std::function<void()>& fn) { timed(h, name, bytes, st, fn); }
+
 size_t sat_pad_bytes(int B) { return ((size_t)B * sizeof(unsigned) + 255) & ~(size_t)255; }
 
 void run_net(EagleHandle* h, Net* net, hipStream_t s, size_t& ev_i)
@@ -167,6 +169,17 @@ static void launch_step(EagleHandle* h, int p, const uint8_t* d_src, int n_activ
     HIP_CHECK(hipEventRecord(sb.ev_done, sp));
 }
 
+void collect_spans(EagleHandle* h)
+{
+    for (const EagleHandle::Span& sp : h->spans) {
+        float t = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&t, sp.a, sp.b));
+        EagleKernelTime& e = h->ktab[sp.k];
+        e.ms += t; e.launches += 1; e.bytes += sp.bytes;
+    }
+    h->spans.clear(); h->span_used = 0;
+}
+
 static void collect_step(EagleHandle* h, int p, int n_active, EagleFrameResult* out)
 {
     HIP_CHECK(hipEventSynchronize(h->sb[p].ev_done));
@@ -188,13 +201,7 @@ static void collect_step(EagleHandle* h, int p, int n_active, EagleFrameResult* 
             }
         }
         h->conv_ops.clear();
-        for (const EagleHandle::Span& sp : h->spans) {
-            float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, sp.a, sp.b));
-            EagleKernelTime& e = h->ktab[sp.k];
-            e.ms += t; e.launches += 1; e.bytes += sp.bytes;
-        }
-        h->spans.clear(); h->span_used = 0;
+        collect_spans(h);
     }
 }
 
@@ -239,24 +246,14 @@ void check_saturation(EagleHandle* h, const char* what)
              what, h->sat_events, h->sat_frames);
 }
 
-// one plane of a frame in caller memory: `rows` rows of `row_bytes` bytes at off + r * pitch; at dense_off + r * row_bytes in the dense frame
-struct HostPlane { int64_t off, pitch, rows, row_bytes, dense_off; };
-
 // ---- decoder-native input (eagle_*_yuv): layout of the caller's 4:2:0 frames ---------------------------------------------------------------
-struct YuvGeom {
-    int fmt, h, w, nplanes;
-    int64_t frame_stride, y_pitch, c_offset, c_pitch, v_offset;
-    int64_t extent;          // bytes of one frame from its start to the end of its last row
-    int64_t dense_bytes;     // h * w * 3 / 2
-    bool dense;              // the layout is the dense default
-    HostPlane pl[3];          // Y, then UV (NV12) or U, V (I420)
-};
-
-// The one argument check of the four eagle_*yuv* entries: fills the dense defaults and rejects what the kernel cannot read safely.
-static YuvGeom yuv_geometry(int fmt, int h, int w, const EagleYuvLayout* L)
+// The one argument check of every entry that takes an EagleYuvLayout (declared in runtime.h; eagle_annotate_* check their output layout with it)
+YuvGeom yuv_geometry(int fmt, int h, int w, const EagleYuvLayout* L, bool output)
 {
-    if (fmt != EAGLE_PIX_NV12 && fmt != EAGLE_PIX_I420) fail(EAGLE_E_INVALID, "unknown pixel format %d (EAGLE_PIX_NV12 = 1, EAGLE_PIX_I420 = 2)", fmt);
-    if (h < 2 || w < 2 || (h & 1) || (w & 1)) fail(EAGLE_E_INVALID, "4:2:0 frames need an even height and width (got %d x %d)", h, w);
+    const bool bgr = output && fmt == EAGLE_PIX_BGR;       // pitched BGR exists as an OUTPUT layout only: one plane, y_pitch = row pitch
+    if (!bgr && fmt != EAGLE_PIX_NV12 && fmt != EAGLE_PIX_I420)
+        fail(EAGLE_E_INVALID, output ? "unknown pixel format %d (EAGLE_PIX_BGR = 0, EAGLE_PIX_NV12 = 1, EAGLE_PIX_I420 = 2)" : "unknown pixel format %d (EAGLE_PIX_NV12 = 1, EAGLE_PIX_I420 = 2)", fmt);
+    if (bgr ? (h < 1 || w < 1) : (h < 2 || w < 2 || (h & 1) || (w & 1))) fail(EAGLE_E_INVALID, "4:2:0 frames need an even height and width (got %d x %d)", h, w);
     EagleYuvLayout l{};
     if (L) l = *L;
     const int64_t lim = (int64_t)1 << 40;
@@ -266,6 +263,19 @@ static YuvGeom yuv_geometry(int fmt, int h, int w, const EagleYuvLayout* L)
         if (f[k] < 0 || f[k] > lim) fail(EAGLE_E_INVALID, "layout.%s = %lld is negative or out of range", names[k], (long long)f[k]);
     YuvGeom g{};
     g.fmt = fmt; g.h = h; g.w = w;
+    if (bgr) {
+        const int64_t row = (int64_t)w * 3;
+        g.y_pitch = l.y_pitch ? l.y_pitch : row;
+        if (g.y_pitch < row) fail(EAGLE_E_INVALID, "layout.y_pitch %lld is smaller than a row of %d BGR pixels (%lld bytes)", (long long)g.y_pitch, w, (long long)row);
+        g.nplanes = 1;
+        g.pl[0] = {0, g.y_pitch, h, row, 0};
+        g.extent = g.y_pitch * (h - 1) + row;
+        g.frame_stride = l.frame_stride ? l.frame_stride : g.y_pitch * h;
+        if (g.frame_stride < g.extent) fail(EAGLE_E_INVALID, "layout.frame_stride %lld is smaller than a frame's extent (%lld bytes)", (long long)g.frame_stride, (long long)g.extent);
+        g.dense_bytes = row * h;
+        g.dense = g.y_pitch == row && g.frame_stride == g.dense_bytes;
+        return g;
+    }
     const bool nv12 = fmt == EAGLE_PIX_NV12;
     const int64_t c_row = nv12 ? w : w / 2, c_rows = h / 2;
     g.y_pitch = l.y_pitch ? l.y_pitch : w;
@@ -332,7 +342,7 @@ static void process_begin(EagleHandle* h, const void* src, const void* out, int 
 }
 
 // is the caller's memory pinned (eagle_host_alloc, hipHostMalloc, hipHostRegister)?  Pageable memory needs the copy workers: started here
-static bool host_pinned(EagleHandle* h, const void* p)
+bool host_pinned(EagleHandle* h, const void* p)
 {
     hipPointerAttribute_t pa;
     const bool pinned = hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost;

@@ -56,6 +56,11 @@ class EagleYuvLayout(C.Structure):
 
 
 PIX_FORMATS = {"nv12": 1, "i420": 2}                                   # include/eagle.h EAGLE_PIX_*
+OUT_FORMATS = {"bgr": 0, "nv12": 1, "i420": 2}                         # ... of annotated output (EAGLE_PIX_BGR is an output format only)
+PRIM_ARC, PRIM_LABEL, PRIM_DISC, PRIM_TRI = 0, 1, 2, 3                 # include/eagle.h EAGLE_PRIM_*
+MAX_PRIMS = 2 * MAX_DET + MAX_KP + 1                                   # include/eagle.h EAGLE_MAX_PRIMS
+# numpy mirror of EaglePrim (32 bytes)
+PRIM_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4", 6), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("pad", "u1")], align=True)
 
 
 class EagleKernelTime(C.Structure):
@@ -157,6 +162,10 @@ def load():
     L.eagle_yuv_to_bgr.argtypes = [vp, i32, vp, i32, yl, vp]
     L.eagle_op_yuv_to_bgr.argtypes = [i32, i32, u8p, i32, i32, i32, yl, u8p]
     L.eagle_track_frames_reid.argtypes = [vp, vp, i32, C.POINTER(C.c_double), fp, C.POINTER(i32), C.POINTER(i32)]
+    L.eagle_annotate_device_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, yl, vp]
+    L.eagle_annotate_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, yl, vp]
+    L.eagle_overlay_from_record.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(i32)]
+    L.eagle_op_annotate.argtypes = [i32, u8p, i32, i32, i32, vp, vp, i32, yl, u8p]
     _lib = L
     return L
 
@@ -168,7 +177,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_find_homography", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
            "eagle_clip_set_keypoints", "eagle_clip_flow", "eagle_clip_run", "eagle_clip_fetch", "eagle_debug", "eagle_track_open", "eagle_track_frames", "eagle_track_frames_cmc", "eagle_clip_motion_ecc", "eagle_clip_motion", "eagle_team_colors",
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
-           "eagle_op_yuv_to_bgr"]
+           "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -409,6 +418,35 @@ class Handle:
             return self.yuv_to_bgr_device(d, n, pixel_format)
         finally:
             self.free(d)
+
+    # --- annotated output (include/eagle.h, eagle_annotate_*) --------------------------------------------------
+    def annotate_device(self, d_bgr, n, recs, d_out, team_mapping=None, fmt="bgr", layout=None):
+        """n frames of a dense BGR clip resident in HBM + their records -> n annotated frames at ``d_out`` (device: free()-able memory of this
+        handle or an encoder's surface) as "bgr", "nv12" or "i420" in ``layout`` (dict or EagleYuvLayout, None = dense).  team_mapping:
+        {player id: 0 | 1} (Processor.get_team_mapping) or None (every player in a neutral colour)."""
+        recs, ids, vals, nt = _annot_args(recs, n, team_mapping)
+        lay = _yuv_layout(layout)
+        self._check(self.L.eagle_annotate_device_frames(self._h, d_bgr, n, recs.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p),
+                                                        None if vals is None else vals.ctypes.data_as(C.c_void_p), nt, _out_pix(fmt),
+                                                        None if lay is None else C.byref(lay), d_out), "annotate_device_frames")
+
+    def annotate(self, d_bgr, n, recs, team_mapping=None, fmt="bgr", layout=None, out=None):
+        """As annotate_device, the result in host memory: uint8 [n, h, w, 3] ("bgr") or [n, 3h/2, w] ("nv12" / "i420"); with a ``layout`` a flat
+        uint8 buffer of the layout's span (``out``: the caller's buffer, e.g. host_buffer(); bytes the layout does not cover are left alone)."""
+        h, w = self.cfg.frame_h, self.cfg.frame_w
+        recs, ids, vals, nt = _annot_args(recs, n, team_mapping)
+        lay = _yuv_layout(layout)
+        need = out_span(fmt, h, w, lay, n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+            if lay is None:
+                out = out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise EagleError(f"annotate: out must be a contiguous uint8 array of at least {need} bytes")
+        self._check(self.L.eagle_annotate_frames(self._h, d_bgr, n, recs.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p),
+                                                 None if vals is None else vals.ctypes.data_as(C.c_void_p), nt, _out_pix(fmt),
+                                                 None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p)), "annotate_frames")
+        return out
 
     def reproject(self, recs, Hs, flags):
         """In place: re-project foot points / boundaries of the flagged records with the given homographies (cadence mode)."""
@@ -716,4 +754,75 @@ def op_yuv_to_bgr(frames, fmt="nv12", layout=None, h=None, w=None, n=None, devic
                                out.ctypes.data_as(C.POINTER(C.c_uint8)))
     if rc:
         raise EagleError(f"eagle_op_yuv_to_bgr failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
+
+
+# --- annotated output helpers -----------------------------------------------------------------------------------
+def _out_pix(fmt):
+    if isinstance(fmt, str):
+        if fmt.lower() not in OUT_FORMATS:
+            raise EagleError(f"unknown output pixel format {fmt!r} (bgr, nv12 or i420)")
+        return OUT_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def _team_arrays(team_mapping):
+    if team_mapping is None:
+        return None, None, 0
+    ids = np.ascontiguousarray([int(k) for k in team_mapping], np.int32)
+    vals = np.ascontiguousarray([int(v) for v in team_mapping.values()], np.int32)
+    return ids, vals, len(ids)
+
+
+def _annot_args(recs, n, team_mapping):
+    recs = np.ascontiguousarray(recs, RESULT_DTYPE).reshape(-1)
+    if len(recs) < n:
+        raise EagleError(f"{n} frames but {len(recs)} records")
+    return (recs,) + _team_arrays(team_mapping)
+
+
+def out_span(fmt, h, w, layout, n):
+    """Bytes n annotated frames of this output format and layout span (0 fields: the dense defaults of include/eagle.h)."""
+    if _out_pix(fmt) != 0:
+        return yuv_span(_out_pix(fmt), h, w, layout, n)
+    lay = _yuv_layout(layout) or EagleYuvLayout()
+    pitch = lay.y_pitch or 3 * w
+    return 0 if n <= 0 else (n - 1) * (lay.frame_stride or pitch * h) + pitch * (h - 1) + 3 * w
+
+
+def overlay_from_record(rec, team_mapping=None):
+    """The primitive list the library draws for one record (include/eagle.h eagle_overlay_from_record; no GPU involved) -> PRIM_DTYPE array."""
+    rec = np.ascontiguousarray(rec, RESULT_DTYPE).reshape(-1)[:1]
+    ids, vals, nt = _team_arrays(team_mapping)
+    out = np.zeros(MAX_PRIMS, PRIM_DTYPE); n = C.c_int(0)
+    L = load()
+    rc = L.eagle_overlay_from_record(rec.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p),
+                                     None if vals is None else vals.ctypes.data_as(C.c_void_p), nt, out.ctypes.data_as(C.c_void_p), MAX_PRIMS, C.byref(n))
+    if rc:
+        raise EagleError(f"eagle_overlay_from_record failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out[: n.value].copy()
+
+
+def op_annotate(frames, prims, offsets, fmt="bgr", layout=None, out=None, device=0):
+    """One annotate launch on host buffers (include/eagle.h eagle_op_annotate): BGR uint8 [n, h, w, 3], a PRIM_DTYPE array and n + 1 offsets into it
+    -> the annotated frames: [n, h, w, 3] / [n, 3h/2, w] when dense, else the flat buffer ``out`` (or a zeroed one) written in ``layout``."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, h, w, _ = frames.shape
+    prims = np.ascontiguousarray(prims, PRIM_DTYPE)
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    if len(offsets) != n + 1 or (n and int(offsets[-1]) > len(prims)):
+        raise EagleError("op_annotate: offsets must have n + 1 entries inside the primitive array")
+    lay = _yuv_layout(layout)
+    need = out_span(fmt, h, w, lay, n) if _out_pix(fmt) == 0 or (h % 2 == 0 and w % 2 == 0) else 0      # (odd 4:2:0 sizes: the library rejects them)
+    if out is None:
+        out = np.zeros(need, np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+        raise EagleError(f"op_annotate: out must be a contiguous uint8 array of at least {need} bytes")
+    rc = L.eagle_op_annotate(device, frames.ctypes.data_as(C.POINTER(C.c_uint8)), n, h, w, prims.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                             _out_pix(fmt), None if lay is None else C.byref(lay), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc:
+        raise EagleError(f"eagle_op_annotate failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if lay is None:
+        return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
     return out

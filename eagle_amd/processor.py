@@ -34,3 +34,7 @@ class Processor:
             return teams.get_team_mapping(self.model.handle, d, coords, n_frames=len(frames))
         finally:
             self.model.handle.free(d)
+
+    def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr"):
+        """The annotated frames of a clip (the reference's annotated video, main.py:43-81), drawn on the GPU: see CoordinateModel.annotate."""
+        return self.model.annotate(frames, coords_or_records, team_mapping, pixel_format, out_format)

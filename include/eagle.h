@@ -201,6 +201,47 @@ int eagle_yuv_to_bgr(EagleHandle* h, int format, const void* d_src, int n, const
 /* Operator entry (host buffers in / out, parity tests): n frames of h x w -> bgr [n, h, w, 3]. */
 int eagle_op_yuv_to_bgr(int device, int format, const uint8_t* src, int n, int h, int w, const EagleYuvLayout* layout, uint8_t* bgr);
 
+/* ---- annotated output: the frames with the records drawn on them, in the layout a video encoder takes ---------------------------------------
+ * What the reference's main.py:43-81 draws into annotated.mp4, its one validation aid: a foot ellipse with a gap and the id per player in the
+ * team colour, a triangle above the ball, a disc per pitch key-point.  One kernel launch (annotate.hip) reads the clip resident in HBM (it stays
+ * untouched), draws and writes BGR, NV12 or I420; the 4:2:0 outputs are converted from the drawn pixels in registers.  The rasterisation is this
+ * library's own (tests/annot_ref.py defines every pixel: integer ellipse outline, 5 x 7 bitmap digits; NOT cv2.ellipse / cv2.putText pixels);
+ * BGR -> 4:2:0 is OpenCV's integer BT.601 limited-range path of COLOR_BGR2YUV_I420, chroma taken from the even-row even-column pixel of each 2 x 2 block.
+ * An overlay is an ordered list of primitives; a pixel takes the colour of the LAST primitive covering it; primitives are clipped to the frame.
+ *   EAGLE_PRIM_ARC    a = {cx, cy}                    outline of the ellipse of half-axes 35 x 18, open at the top (parametric angles 235 .. 315 degrees)
+ *   EAGLE_PRIM_LABEL  a = {x, y, id}                  decimal digits of id (0 .. 99999, else nothing), 10 x 14 glyphs, bottom-left pixel at (x - 3, y)
+ *   EAGLE_PRIM_DISC   a = {cx, cy, r}                 filled, 0 <= r <= 16384
+ *   EAGLE_PRIM_TRI    a = {x0, y0, x1, y1, x2, y2}    filled, edges inclusive
+ * Coordinates are frame pixels, |coordinate| <= 2^20.  Output layout: EagleYuvLayout with the rules above (0 = dense, EAGLE_E_INVALID for negative
+ * fields, short pitches, overlapping planes, odd frame sizes for 4:2:0); EAGLE_PIX_BGR is an output format only: dense or pitched [h][w][3],
+ * layout->y_pitch = row pitch, layout->frame_stride, the other fields unused.  Bytes between rows, planes and frames are left untouched. */
+#define EAGLE_PIX_BGR 0
+#define EAGLE_PRIM_ARC 0
+#define EAGLE_PRIM_LABEL 1
+#define EAGLE_PRIM_DISC 2
+#define EAGLE_PRIM_TRI 3
+#define EAGLE_MAX_PRIMS (2 * EAGLE_MAX_DET + EAGLE_MAX_KP + 1)     /* per frame: two per detection, the key-points, one ball */
+typedef struct EaglePrim { int32_t kind; int32_t a[6]; uint8_t b, g, r, pad; } EaglePrim;
+/* n frames of a BGR clip resident in HBM (dense [n, h, w, 3] of the handle's size) + their records -> n annotated frames in HBM (a buffer of the
+ * caller: eagle_device_alloc, or an encoder's input surface with its layout).  team_ids / team_vals: Processor.get_team_mapping as two arrays of
+ * n_team entries (team 0 red, any other blue; goalkeepers green; players without an entry are not drawn, main.py:64-65); team_ids NULL: every
+ * player white.  Runs on the handle's main stream behind whatever is enqueued and returns when the output is complete; the step's graphs and
+ * staging buffers are not involved. */
+int eagle_annotate_device_frames(EagleHandle* h, const void* d_bgr, int n, const EagleFrameResult* recs, const int32_t* team_ids,
+                                 const int32_t* team_vals, int n_team, int out_format, const EagleYuvLayout* out_layout, void* d_out);
+/* Same, the result copied to host memory (pinned: DMA'd; pageable: through a pinned ring of the handle). */
+int eagle_annotate_frames(EagleHandle* h, const void* d_bgr, int n, const EagleFrameResult* recs, const int32_t* team_ids,
+                          const int32_t* team_vals, int n_team, int out_format, const EagleYuvLayout* out_layout, uint8_t* out);
+/* What a record's overlay is (no GPU involved), for callers that draw themselves and for the tests: persons in detection order (ARC + LABEL at
+ * the foot point), the marker of the first reported ball, a black disc of radius 6 per key-point of the reference dict (the RANSAC inliers when
+ * H_valid, else all).  cap >= EAGLE_MAX_PRIMS always suffices; a smaller cap that does not is EAGLE_E_INVALID. */
+int eagle_overlay_from_record(const EagleFrameResult* rec, const int32_t* team_ids, const int32_t* team_vals, int n_team, EaglePrim* out,
+                              int cap, int* n_out);
+/* Operator entry (host buffers in / out, no handle): arbitrary primitive lists, frame k owns prims[prim_offsets[k] .. prim_offsets[k + 1]) (at most
+ * EAGLE_MAX_PRIMS); every list empty = the plain conversion.  `out` is read first, so bytes the layout does not cover come back as they were. */
+int eagle_op_annotate(int device, const uint8_t* bgr, int n, int h, int w, const EaglePrim* prims, const int32_t* prim_offsets /* n + 1 */,
+                      int out_format, const EagleYuvLayout* out_layout, uint8_t* out);
+
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
  * flags[i] = 0 keep the record, 1 re-project foot points and boundaries with Hs[9*i..], 2 no homography available yet. */
