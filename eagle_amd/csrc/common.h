@@ -72,6 +72,8 @@ struct ConvLaunch {
 };
 // output tiles per frame of a convolution with this configuration (the number of partials per channel the fused arg-max writes)
 int conv_tiles_per_frame(int precision, const ConvConfig& cfg, int ho, int wo);
+// rows x columns of output pixels one workgroup of this configuration owns (row-major tiles; the last row / column of tiles may be partial)
+void conv_tile_shape(int precision, const ConvConfig& cfg, int* th, int* tw);
 // returns false when no kernel instance exists for cfg
 bool conv_supported(int precision, const ConvConfig& cfg);
 void conv_launch(int precision, const ConvLaunch& L, hipStream_t s);
@@ -120,6 +122,7 @@ void stem_launch(const StemLaunch& L, hipStream_t s);
 // ---- other kernels ----------------------------------------------------------------------------------------
 struct LetterBox { int new_h, new_w, top, left, out_h, out_w; };
 LetterBox letterbox_geometry(int h, int w, int imgsz, int square = 0);      // square: EagleConfig::letterbox (auto=False)
+int detector_anchor_count(int h, int w, int imgsz, int square);             // anchors per frame of the three Detect levels (strides 8, 16, 32) on that letterbox
 // which: bit 0 = write the key-point tensor, bit 1 = write the detector tensor; det_precision >= 0: the detector tensor's family when it differs from `precision`
 void preprocess_launch(int precision, const uint8_t* d_bgr, int n, int h, int w, const TView& kp, const TView& det,
                        const LetterBox& lb, hipStream_t s, int which = 3, int det_precision = -1);
@@ -151,6 +154,9 @@ struct PostParams {
     int ransac_max_iters, lm_iters;
 };
 void nms_launch(const DetScratch& sc, int n, const PostParams& pp, EagleFrameResult* d_out, hipStream_t s);
+int nms_anchor_limit();      // the largest DetScratch::A nms_launch accepts (one workgroup sorts a frame's candidates in LDS)
+// throws EAGLE_E_INVALID when the detector geometry of this configuration has more anchors than that (eagle_resolve_config, eagle_create)
+void check_anchor_limit(const EagleConfig& cfg);
 void post_launch(const ArgmaxPart* parts, int n, const PostParams& pp, EagleFrameResult* d_out, hipStream_t s);
 void reproject_launch(EagleFrameResult* d_recs, const double* d_Hs, const unsigned char* d_flags, int n, int frame_h, int frame_w, hipStream_t s);
 void homography_only_launch(const float* d_img, const float* d_world, int npts, double thresh, int max_iters, int lm_iters,

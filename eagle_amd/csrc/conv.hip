@@ -116,10 +116,16 @@ static size_t lds_bytes(int precision, const ConvConfig& c)
 }
 
 size_t conv_lds_bytes(int precision, const ConvConfig& c) { return lds_bytes(precision, c); }
-int conv_tiles_per_frame(int precision, const ConvConfig& c, int ho, int wo)
+void conv_tile_shape(int precision, const ConvConfig& c, int* th, int* tw)
 {
     const Form& f = form_of(precision, c);
-    const int th = f.kind == ADIRECT ? f.rows : 4 * f.pw / c.wx, tw = f.kind == ADIRECT ? f.cols : 16 * c.wx;
+    *th = f.kind == ADIRECT ? f.rows : 4 * f.pw / c.wx; *tw = f.kind == ADIRECT ? f.cols : 16 * c.wx;
+}
+
+int conv_tiles_per_frame(int precision, const ConvConfig& c, int ho, int wo)
+{
+    int th, tw;
+    conv_tile_shape(precision, c, &th, &tw);
     return ((wo + tw - 1) / tw) * ((ho + th - 1) / th);
 }
 

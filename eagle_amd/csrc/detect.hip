@@ -252,15 +252,32 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
     }
 }
 
+// The sort runs on a power-of-two number of keys (8 bytes) and dead flags (1 byte) in the workgroup's dynamic LDS
+#define NMS_LDS_MAX (160 * 1024 - 4096)
+int nms_anchor_limit()
+{
+    int cap = 1;
+    while ((size_t)cap * 2 * 9 <= NMS_LDS_MAX) cap <<= 1;
+    return cap;
+}
+
+void check_anchor_limit(const EagleConfig& cfg)
+{
+    const int A = detector_anchor_count(cfg.frame_h, cfg.frame_w, cfg.det_imgsz, cfg.letterbox), lim = nms_anchor_limit();
+    if (A > lim)
+        fail(EAGLE_E_INVALID, "%dx%d frames with det_imgsz %d and letterbox %d give %d detector anchors per frame; the NMS kernel sorts at most %d (use the rect letterbox or a smaller det_imgsz)",
+             cfg.frame_w, cfg.frame_h, cfg.det_imgsz, cfg.letterbox, A, lim);
+}
+
 void nms_launch(const DetScratch& sc, int n, const PostParams& pp, EagleFrameResult* d_out, hipStream_t s)
 {
     NmsArgs a; a.sc = sc; a.pp = pp; a.out = d_out;
+    if (sc.A > nms_anchor_limit()) fail(EAGLE_E_INVALID, "too many anchors for the NMS workgroup: %d (limit %d)", sc.A, nms_anchor_limit());
     int cap = 1;
     while (cap < sc.A) cap <<= 1;
     a.cap = cap;
     const size_t lds = (size_t)cap * 9;
-    ensure_max_dynamic_lds((const void*)nms_kernel, 160 * 1024 - 4096);
-    if (lds > 160 * 1024 - 4096) fail(EAGLE_E_INVALID, "too many anchors for the NMS workgroup: %d", sc.A);
+    ensure_max_dynamic_lds((const void*)nms_kernel, NMS_LDS_MAX);
     hipLaunchKernelGGL(nms_kernel, dim3(n), dim3(NMS_T), lds, s, a);
     HIP_CHECK(hipGetLastError());
 }

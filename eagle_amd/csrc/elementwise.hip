@@ -86,6 +86,14 @@ LetterBox letterbox_geometry(int h, int w, int imgsz, int square)
     return lb;
 }
 
+int detector_anchor_count(int h, int w, int imgsz, int square)
+{
+    const LetterBox lb = letterbox_geometry(h, w, imgsz, square);
+    int A = 0;
+    for (int s = 8; s <= 32; s *= 2) A += ((lb.out_h + s - 1) / s) * ((lb.out_w + s - 1) / s);
+    return A;
+}
+
 template <typename T>
 static void preprocess_launch_det(int det_precision, dim3 grid, hipStream_t s, const uint8_t* d_bgr, int n, int h, int w, const TView& kp, const TView& det, const LetterBox& lb, int which)
 {

@@ -235,4 +235,122 @@ int eagle_op_find_homography(int device, const float* img_pts, const float* worl
     API_END(hh)
 }
 
+// ---- the tail behind the networks on chosen inputs (tests/test_gpu_tail.py) -----------------------------------------------------
+int eagle_op_detect_tail(int device, int n_lv, const int* gh, const int* gw, const float* stride, const float* const* box, const float* const* cls, int n, int nc,
+                         float conf_floor, float nms_iou, double detector_conf, int frame_h, int frame_w, int in_h, int in_w,
+                         EagleFrameResult* out, float* boxes, float* conf, int32_t* cls_out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (n_lv < 1 || n_lv > 3 || !gh || !gw || !stride || !box || !cls || !out || n < 1 || nc < 1 || nc > 16 || frame_h < 1 || frame_w < 1 || in_h < 1 || in_w < 1)
+        fail(EAGLE_E_INVALID, "eagle_op_detect_tail: bad argument (1 - 3 levels, 1 - 16 classes)");
+    int A = 0;
+    for (int l = 0; l < n_lv; ++l) {
+        if (gh[l] < 1 || gw[l] < 1 || !box[l] || !cls[l]) fail(EAGLE_E_INVALID, "eagle_op_detect_tail: bad level %d", l);
+        A += gh[l] * gw[l];
+    }
+    if (A > nms_anchor_limit()) fail(EAGLE_E_INVALID, "eagle_op_detect_tail: %d anchors, the NMS kernel sorts at most %d", A, nms_anchor_limit());
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    DetLevel lv[3];
+    int a0 = 0;
+    for (int l = 0; l < n_lv; ++l) {
+        to_dev(net, EAGLE_PREC_F32, box[l], n, gh[l], gw[l], 64, 64, lv[l].box);
+        to_dev(net, EAGLE_PREC_F32, cls[l], n, gh[l], gw[l], nc, (nc + 3) / 4 * 4, lv[l].cls);
+        lv[l].gh = gh[l]; lv[l].gw = gw[l]; lv[l].stride = stride[l]; lv[l].a0 = a0;
+        a0 += gh[l] * gw[l];
+    }
+    DetScratch sc;
+    sc.A = A;
+    sc.boxes = (float*)net.get(sizeof(float) * 4 * (size_t)n * A);
+    sc.conf = (float*)net.get(sizeof(float) * (size_t)n * A);
+    sc.cls = (int*)net.get(sizeof(int) * (size_t)n * A);
+    sc.keys = (unsigned long long*)net.get(sizeof(unsigned long long) * (size_t)n * A);
+    sc.count = (int*)net.get(sizeof(int) * (size_t)n);
+    EagleFrameResult* d_out = (EagleFrameResult*)net.get(sizeof(EagleFrameResult) * (size_t)n);
+    PostParams pp{};
+    pp.frame_h = frame_h; pp.frame_w = frame_w; pp.in_h = in_h; pp.in_w = in_w; pp.nms_iou = nms_iou; pp.detector_conf = detector_conf;
+    yolo_decode_launch(lv, n_lv, n, nc, conf_floor, sc, nullptr);
+    nms_launch(sc, n, pp, d_out, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, d_out, sizeof(EagleFrameResult) * (size_t)n, hipMemcpyDeviceToHost));
+    if (boxes) HIP_CHECK(hipMemcpy(boxes, sc.boxes, sizeof(float) * 4 * (size_t)n * A, hipMemcpyDeviceToHost));
+    if (conf) HIP_CHECK(hipMemcpy(conf, sc.conf, sizeof(float) * (size_t)n * A, hipMemcpyDeviceToHost));
+    if (cls_out) HIP_CHECK(hipMemcpy(cls_out, sc.cls, sizeof(int) * (size_t)n * A, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
+int eagle_op_post(int device, int n, int hm_h, int hm_w, int chunks, const float* logits, const EagleArgmaxPart* parts, EagleArgmaxPart* parts_out,
+                  EagleFrameResult* recs, int frame_h, int frame_w, double keypoint_conf, double ransac_thresh, int ransac_max_iters, int lm_iters)
+{
+    static_assert(sizeof(EagleArgmaxPart) == sizeof(ArgmaxPart), "the public partial is the kernels' ArgmaxPart");
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (n < 1 || hm_h < 1 || hm_w < 1 || chunks < 1 || !recs || (logits != nullptr) == (parts != nullptr) || frame_h < 1 || frame_w < 1)
+        fail(EAGLE_E_INVALID, "eagle_op_post: bad argument (exactly one of logits / parts)");
+    for (int f = 0; f < n; ++f)
+        if (recs[f].n_det < 0 || recs[f].n_det > EAGLE_MAX_DET) fail(EAGLE_E_INVALID, "eagle_op_post: record %d has n_det %d", f, recs[f].n_det);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const size_t np = (size_t)n * chunks * 64;
+    ArgmaxPart* d_parts;
+    if (logits) {
+        TView lg;
+        to_dev(net, EAGLE_PREC_F32, logits, n, hm_h, hm_w, 64, 64, lg);
+        d_parts = (ArgmaxPart*)net.get(sizeof(ArgmaxPart) * np);
+        heat_argmax_launch(lg, d_parts, chunks, nullptr);
+    } else {
+        d_parts = (ArgmaxPart*)net.upload(parts, sizeof(ArgmaxPart) * np);
+    }
+    EagleFrameResult* d_recs = (EagleFrameResult*)net.upload(recs, sizeof(EagleFrameResult) * (size_t)n);
+    PostParams pp{};
+    pp.frame_h = frame_h; pp.frame_w = frame_w; pp.hm_h = hm_h; pp.hm_w = hm_w; pp.hm_chunks = chunks;
+    pp.keypoint_conf = keypoint_conf; pp.ransac_thresh = ransac_thresh; pp.ransac_max_iters = ransac_max_iters; pp.lm_iters = lm_iters;
+    post_launch(d_parts, n, pp, d_recs, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(recs, d_recs, sizeof(EagleFrameResult) * (size_t)n, hipMemcpyDeviceToHost));
+    if (parts_out) HIP_CHECK(hipMemcpy(parts_out, d_parts, sizeof(ArgmaxPart) * np, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
+int eagle_op_conv2d_argmax(int device, int precision, const float* x, int n, int h, int w, int cin, const float* w_hwio, const float* bias, int cout, int ks, int stride,
+                           float* logits, EagleArgmaxPart* parts, int* tiles, int* tile_h, int* tile_w)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!prec_is_f16_kernels(precision) || cout < 1 || cout > 64 || n < 1 || h < 1 || w < 1 || cin < 1 || (ks != 1 && ks != 3) || stride < 1 || !tiles || !tile_h || !tile_w)
+        fail(EAGLE_E_INVALID, "eagle_op_conv2d_argmax: the fp16 and split families, cout <= 64, ks 1 or 3");
+    const int cin_pad = cin <= 8 ? 8 : (cin + 15) / 16 * 16, cout_pad = (cout + 15) / 16 * 16;
+    const int ho = (h + 2 * (ks / 2) - ks) / stride + 1, wo = (w + 2 * (ks / 2) - ks) / stride + 1;
+    ConvLaunch L;
+    L.cfg = conv_choose(precision, ks, stride, cin_pad, cout_pad, wo, false, false);      // as Builder::conv for an fp32-output layer
+    if (!conv_supported(precision, L.cfg)) fail(EAGLE_E_NOKERNEL, "no kernel instance ks=%d s=%d kc=%d nt=%d", ks, stride, L.cfg.kc, L.cfg.nt);
+    conv_tile_shape(precision, L.cfg, tile_h, tile_w);
+    *tiles = conv_tiles_per_frame(precision, L.cfg, ho, wo);
+    if (!logits) return EAGLE_OK;
+    if (!x || !w_hwio || !bias || !parts) fail(EAGLE_E_INVALID, "eagle_op_conv2d_argmax: null argument");
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    to_dev(net, precision, x, n, h, w, cin, cin_pad, L.x);
+    std::vector<char> tiled(conv_weight_elems(precision, L.cfg) * 2);
+    conv_tile_weights(precision, L.cfg, w_hwio, cin, cout, tiled.data(), &L.descale);
+    L.w = net.upload(tiled.data(), tiled.size());
+    std::vector<float> b(cout_pad, 0.f);
+    for (int i = 0; i < cout; ++i) b[i] = bias[i];
+    L.bias = (const float*)net.upload(b.data(), b.size() * 4);
+    L.y.n = n; L.y.h = ho; L.y.w = wo; L.y.c = cout_pad; L.y.cs = cout_pad; L.y.f32 = 1;
+    L.y.p = net.get((size_t)n * ho * wo * cout_pad * 4);
+    L.out_f32 = 1;
+    conv_launch(precision, L, nullptr);                     // the logits
+    const size_t np = (size_t)n * *tiles * cout_pad;
+    ArgmaxPart* d_parts = (ArgmaxPart*)net.get(sizeof(ArgmaxPart) * np);
+    ArgmaxPart* const* slot = &d_parts;
+    L.am_slot = slot;
+    conv_launch(precision, L, nullptr);                     // the same launch with the fused arg-max epilogue
+    HIP_CHECK(hipDeviceSynchronize());
+    from_dev(L.y, cout, logits);
+    HIP_CHECK(hipMemcpy(parts, d_parts, sizeof(ArgmaxPart) * np, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
 }  // extern "C"

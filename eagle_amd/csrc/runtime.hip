@@ -86,6 +86,13 @@ int eagle_resolve_config(EagleConfig* cfg)
     // batch: B = 50, same box, three alternating pairs 810.2 / 806.4 / 805.7 -> 823.1 / 820.2 / 818.0 frames/s (profiles/r06aj_*).  EAGLE_MULTI_STREAM=0 in the
     // environment resolves "auto" to one stream per network (developer A/B).
     if (cfg->multi_stream == EAGLE_AUTO) cfg->multi_stream = (getenv("EAGLE_MULTI_STREAM") && atoi(getenv("EAGLE_MULTI_STREAM")) == 0) ? 0 : 1;
+    // A geometry with more anchors than the NMS workgroup sorts is refused here, not by the first step's enqueue (eagle_last_error(NULL) names count and limit).
+    // Fields eagle_create rejects on their own are left to it.
+    if (cfg->frame_h >= 32 && cfg->frame_w >= 32 && cfg->det_imgsz >= 32 && cfg->det_imgsz % 32 == 0 &&
+        (cfg->letterbox == EAGLE_LETTERBOX_RECT || cfg->letterbox == EAGLE_LETTERBOX_SQUARE)) {
+        try { eagle::check_anchor_limit(*cfg); }
+        catch (const eagle::Err& e) { eagle::g_create_error = e.msg; return e.code; }
+    }
     return EAGLE_OK;
 }
 
@@ -101,13 +108,14 @@ int eagle_create(const EagleConfig* cfg, EagleHandle** out)
     if (cfg->det_imgsz < 32 || cfg->det_imgsz % 32) fail(EAGLE_E_INVALID, "det_imgsz must be a positive multiple of 32 (the detector's largest stride)");
     if (cfg->det_precision < EAGLE_DET_PREC_AUTO || cfg->det_precision > EAGLE_DET_PREC_MIXED) fail(EAGLE_E_INVALID, "bad detector precision");
     if (cfg->use_graph < EAGLE_AUTO || cfg->use_graph > 2 || cfg->multi_stream < EAGLE_AUTO || cfg->multi_stream > 1) fail(EAGLE_E_INVALID, "use_graph: -1 (auto), 0, 1 or 2; multi_stream: -1 (auto), 0 or 1");
+    check_anchor_limit(*cfg);                              // before anything is built
     int ndev = 0;
     HIP_CHECK(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev) fail(EAGLE_E_HIP, "device %d not present (%d visible)", cfg->device, ndev);
     HIP_CHECK(hipSetDevice(cfg->device));
     EagleHandle* nh = new EagleHandle;
     nh->cfg = *cfg;
-    eagle_resolve_config(&nh->cfg);                        // det_precision "auto" -> a family, from the precision the caller actually asked for
+    (void)eagle_resolve_config(&nh->cfg);                  // det_precision "auto" -> a family, from the precision the caller actually asked for
     HIP_CHECK(hipStreamCreateWithFlags(&nh->s_main, hipStreamNonBlocking));
     HIP_CHECK(hipStreamCreateWithFlags(&nh->s_det, hipStreamNonBlocking));
     HIP_CHECK(hipStreamCreateWithFlags(&nh->s_post, hipStreamNonBlocking));

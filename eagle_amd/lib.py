@@ -148,6 +148,10 @@ def load():
     L.eagle_op_preprocess.argtypes = [i32, i32, u8p, i32, i32, i32, i32, fp, fp, C.POINTER(i32)]
     L.eagle_op_preprocess_lb.argtypes = [i32, i32, u8p, i32, i32, i32, i32, i32, fp, fp, C.POINTER(i32)]
     L.eagle_op_find_homography.argtypes = [i32, fp, fp, i32, C.c_double, i32, i32, dp, u8p, C.POINTER(i32)]
+    L.eagle_op_detect_tail.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), fp, C.POINTER(fp), C.POINTER(fp), i32, i32, C.c_float, C.c_float, C.c_double,
+                                       i32, i32, i32, i32, vp, fp, fp, C.POINTER(C.c_int32)]
+    L.eagle_op_post.argtypes = [i32, i32, i32, i32, i32, fp, vp, vp, vp, i32, i32, C.c_double, C.c_double, i32, i32]
+    L.eagle_op_conv2d_argmax.argtypes = [i32, i32, fp, i32, i32, i32, i32, fp, fp, i32, i32, i32, fp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.eagle_debug.argtypes = [C.c_char_p, i64, vp, i64]
     L.eagle_team_colors.argtypes = [vp, vp, i32, vp, i32, vp]
     L.eagle_track_open.argtypes = [vp, C.POINTER(EagleTrackParams)]
@@ -174,7 +178,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_finalize_weights", "eagle_process_frames", "eagle_process_device_frames", "eagle_device_alloc",
            "eagle_device_free", "eagle_device_upload", "eagle_host_alloc", "eagle_host_free", "eagle_reproject", "eagle_comm_id", "eagle_comm_init", "eagle_gather",
            "eagle_set_profiling", "eagle_get_timings", "eagle_get_kernel_times", "eagle_op_conv2d", "eagle_op_bottleneck", "eagle_op_stem", "eagle_op_fuse_sum", "eagle_op_preprocess", "eagle_op_preprocess_lb",
-           "eagle_op_find_homography", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
+           "eagle_op_find_homography", "eagle_op_detect_tail", "eagle_op_post", "eagle_op_conv2d_argmax", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
            "eagle_clip_set_keypoints", "eagle_clip_flow", "eagle_clip_run", "eagle_clip_fetch", "eagle_debug", "eagle_track_open", "eagle_track_frames", "eagle_track_frames_cmc", "eagle_clip_motion_ecc", "eagle_clip_motion", "eagle_team_colors",
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
            "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate"]
@@ -195,8 +199,9 @@ def debug(key, value=0, out=None):
 def resolve_config(cfg):
     """A copy of cfg with the "auto" fields resolved the way eagle_create will (no GPU needed)."""
     out = EagleConfig.from_buffer_copy(cfg)
-    if load().eagle_resolve_config(C.byref(out)):
-        raise EagleError("eagle_resolve_config failed")
+    rc = load().eagle_resolve_config(C.byref(out))
+    if rc:
+        raise EagleError(f"eagle_resolve_config failed ({rc}): {load().eagle_last_error(None).decode()}")
     return out
 
 
@@ -695,6 +700,86 @@ def op_find_homography(img_pts, world_pts, thresh=5.0, max_iters=2000, lm_iters=
     if rc:
         raise EagleError(f"eagle_op_find_homography failed ({rc}): {L.eagle_last_error(None).decode()}")
     return (H.reshape(3, 3), mask[:n]) if ok.value else (None, None)
+
+
+PART_DTYPE = np.dtype([("score", "<f4"), ("idx", "<i4")], align=True)      # include/eagle.h EagleArgmaxPart
+
+
+def op_detect_tail(levels, nc, in_hw, frame_hw, conf_floor=0.15, nms_iou=0.7, detector_conf=0.35, device=0):
+    """yolo_decode_kernel + nms_kernel on chosen head tensors (include/eagle.h eagle_op_detect_tail; csrc/detect.hip).  levels: [(box [n, gh, gw, 64],
+    cls [n, gh, gw, nc], stride)], 1 to 3 of them -> (records RESULT_DTYPE [n] with n_det / n_candidates / det written, boxes [n, A, 4], conf [n, A], cls [n, A])."""
+    L = load()
+    nl = len(levels)
+    box = [np.ascontiguousarray(b, np.float32) for b, _, _ in levels]
+    cls = [np.ascontiguousarray(c, np.float32) for _, c, _ in levels]
+    n = box[0].shape[0]
+    for b, c in zip(box, cls):
+        assert b.ndim == 4 and b.shape[0] == n and b.shape[3] == 64 and c.shape == b.shape[:3] + (nc,), (b.shape, c.shape)
+    gh = (C.c_int * nl)(*[b.shape[1] for b in box]); gw = (C.c_int * nl)(*[b.shape[2] for b in box])
+    st = (C.c_float * nl)(*[float(s) for _, _, s in levels])
+    bp = (C.POINTER(C.c_float) * nl)(*[_fp(b) for b in box]); cp = (C.POINTER(C.c_float) * nl)(*[_fp(c) for c in cls])
+    A = sum(b.shape[1] * b.shape[2] for b in box)
+    out = np.zeros(n, RESULT_DTYPE)
+    boxes = np.zeros((n, A, 4), np.float32); conf = np.zeros((n, A), np.float32); cl = np.zeros((n, A), np.int32)
+    rc = L.eagle_op_detect_tail(device, nl, gh, gw, st, bp, cp, n, nc, conf_floor, nms_iou, detector_conf, frame_hw[0], frame_hw[1], in_hw[0], in_hw[1],
+                                out.ctypes.data_as(C.c_void_p), _fp(boxes), _fp(conf), cl.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc:
+        raise EagleError(f"eagle_op_detect_tail failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out, boxes, conf, cl
+
+
+def op_post(hm_hw, frame_hw, logits=None, chunks=64, parts=None, recs=None, keypoint_conf=0.3, ransac_thresh=5.0, ransac_max_iters=2000, lm_iters=10, device=0):
+    """post_kernel on chosen inputs (include/eagle.h eagle_op_post; csrc/geom.hip): logits [n, h, w, 64] (heat_argmax_kernel makes ``chunks`` partials first)
+    or parts PART_DTYPE [n, chunks, 64]; recs: optional RESULT_DTYPE [n] with n_det and det foot points filled in -> (records, the partials that were reduced)."""
+    L = load()
+    if logits is not None:
+        logits = np.ascontiguousarray(logits, np.float32)
+        n = logits.shape[0]
+        assert logits.shape == (n, hm_hw[0], hm_hw[1], 64), logits.shape
+    else:
+        parts = np.ascontiguousarray(parts, PART_DTYPE)
+        n, chunks = parts.shape[0], parts.shape[1]
+        assert parts.shape == (n, chunks, 64), parts.shape
+    out = np.zeros(n, RESULT_DTYPE) if recs is None else np.ascontiguousarray(recs, RESULT_DTYPE).copy()
+    assert len(out) == n
+    pout = np.zeros((n, chunks, 64), PART_DTYPE)
+    rc = L.eagle_op_post(device, n, hm_hw[0], hm_hw[1], chunks, _fp(logits), None if parts is None else parts.ctypes.data_as(C.c_void_p),
+                         pout.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), frame_hw[0], frame_hw[1], keypoint_conf, ransac_thresh, ransac_max_iters, lm_iters)
+    if rc:
+        raise EagleError(f"eagle_op_post failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out, pout
+
+
+def conv2d_argmax_tiles(hw, cin, cout, ks=1, stride=1, precision=PREC_F32S):
+    """(tiles per frame, tile_h, tile_w) of the head-convolution configuration op_conv2d_argmax runs for this shape (no GPU involved)."""
+    L = load()
+    tiles, th, tw = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = L.eagle_op_conv2d_argmax(0, precision, None, 1, hw[0], hw[1], cin, None, None, cout, ks, stride, None, None, C.byref(tiles), C.byref(th), C.byref(tw))
+    if rc:
+        raise EagleError(f"eagle_op_conv2d_argmax failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return tiles.value, th.value, tw.value
+
+
+def op_conv2d_argmax(x, w_hwio, bias, stride=1, precision=PREC_F32S, device=0):
+    """The head convolution twice (include/eagle.h eagle_op_conv2d_argmax): -> (fp32 logits [n, ho, wo, cout], partials PART_DTYPE [n, tiles, cout_pad] of the fused
+    arg-max epilogue, (tile_h, tile_w)); tiles are numbered row-major, ceil(wo / tile_w) per row."""
+    L = load()
+    x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w_hwio, np.float32); b = np.ascontiguousarray(bias, np.float32)
+    n, h, wd, cin = x.shape
+    ks, _, _, cout = w.shape
+    ho = (h + 2 * (ks // 2) - ks) // stride + 1
+    wo = (wd + 2 * (ks // 2) - ks) // stride + 1
+    tiles, th, tw = C.c_int(0), C.c_int(0), C.c_int(0)
+    args = (device, precision, _fp(x), n, h, wd, cin, _fp(w), _fp(b), cout, ks, stride)
+    rc = L.eagle_op_conv2d_argmax(*args, None, None, C.byref(tiles), C.byref(th), C.byref(tw))
+    if rc:
+        raise EagleError(f"eagle_op_conv2d_argmax failed ({rc}): {L.eagle_last_error(None).decode()}")
+    y = np.empty((n, ho, wo, cout), np.float32)
+    parts = np.zeros((n, tiles.value, (cout + 15) // 16 * 16), PART_DTYPE)
+    rc = L.eagle_op_conv2d_argmax(*args, _fp(y), parts.ctypes.data_as(C.c_void_p), C.byref(tiles), C.byref(th), C.byref(tw))
+    if rc:
+        raise EagleError(f"eagle_op_conv2d_argmax failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return y, parts, (th.value, tw.value)
 
 
 # --- decoder-native input helpers -------------------------------------------------------------------------------

@@ -144,7 +144,9 @@ int eagle_default_config(EagleConfig* cfg);
 int eagle_create(const EagleConfig* cfg, EagleHandle** out);
 void eagle_destroy(EagleHandle* h);
 const char* eagle_last_error(EagleHandle* h);   /* h may be NULL: last error of eagle_create */
-int eagle_resolve_config(EagleConfig* cfg);     /* in place, no GPU needed: what eagle_create will make of the "auto" fields (det_precision) */
+int eagle_resolve_config(EagleConfig* cfg);     /* in place, no GPU needed: what eagle_create will make of the "auto" fields (det_precision).  EAGLE_E_INVALID
+                                                   (as eagle_create; message: eagle_last_error(NULL)) for a detector geometry with more anchors per frame than the
+                                                   NMS kernel sorts (16384: e.g. letterbox square with det_imgsz 960 has 18900) */
 int eagle_get_config(EagleHandle* h, EagleConfig* cfg);   /* the handle's configuration as eagle_create resolved it (det_precision no longer "auto") */
 
 /* Weights: state-dict tensors by their reference names, fp32, PyTorch layouts
@@ -374,6 +376,29 @@ int eagle_op_preprocess_lb(int device, int precision, const uint8_t* bgr, int n,
                            float* kp_out, float* det_out, int* det_hw);
 int eagle_op_find_homography(int device, const float* img_pts, const float* world_pts, int n, double thresh,
                              int max_iters, int lm_iters, double* H9, uint8_t* mask, int* ok);
+
+/* ---- the tail behind the two networks, on chosen inputs (tests/test_gpu_tail.py).  Test surface only: the launches are the data path's own. ----
+ * One heat-map partial: the first maximum of sigmoid(logit) of one channel over one pixel range or output tile (score -1, idx 0x7fffffff: empty range). */
+typedef struct EagleArgmaxPart { float score; int32_t idx; } EagleArgmaxPart;
+/* Detect tail: DFL decode + class sigmoid + confidence floor (yolo_decode_kernel), then sort, class-offset NMS, the 300-box cap, scale_boxes and the
+ * detection -> object rules (nms_kernel).  n_lv (1..3) pyramid levels of gh[l] x gw[l] cells and stride[l]; box[l]: fp32 logits [n][gh][gw][64], cls[l]:
+ * [n][gh][gw][nc] (nc <= 16); anchors are numbered level by level, row-major.  out: n records, of which n_det, n_candidates and det[0..n_det) are written.
+ * boxes [n][A][4] / conf [n][A] / cls_out [n][A] (each may be NULL): what the decode left for every anchor.  More anchors than the NMS workgroup sorts: EAGLE_E_INVALID. */
+int eagle_op_detect_tail(int device, int n_lv, const int* gh, const int* gw, const float* stride, const float* const* box, const float* const* cls, int n, int nc,
+                         float conf_floor, float nms_iou, double detector_conf, int frame_h, int frame_w, int in_h, int in_w,
+                         EagleFrameResult* out, float* boxes, float* conf, int32_t* cls_out);
+/* Key-point tail (post_kernel): reduction of the heat-map partials, decode / threshold / dedup, synthesis, homography, bounds and the projection of the foot
+ * points.  Either logits (fp32 [n][hm_h][hm_w][64]: heat_argmax_kernel makes `chunks` partials per channel first) or parts ([n][chunks][64], e.g. those of
+ * eagle_op_conv2d_argmax with 64 padded channels) is given, the other NULL.  recs: n records, read (n_det and det[k].foot_x / foot_y) and completed in place.
+ * parts_out (or NULL): the partials that were reduced, [n][chunks][64]. */
+int eagle_op_post(int device, int n, int hm_h, int hm_w, int chunks, const float* logits, const EagleArgmaxPart* parts, EagleArgmaxPart* parts_out,
+                  EagleFrameResult* recs, int frame_h, int frame_w, double keypoint_conf, double ransac_thresh, int ransac_max_iters, int lm_iters);
+/* The head convolution with its fused arg-max epilogue: ONE ConvLaunch (families EAGLE_PREC_F16 and EAGLE_PREC_F32S, cout <= 64, the configuration the network
+ * builder picks for an fp32-output layer) run twice, once storing the fp32 logits [n][ho][wo][cout], once reducing sigmoid(logit) per output tile into
+ * parts [n][tiles][cout rounded up to 16].  tiles / tile_h / tile_w: partials per frame and channel and the tile rectangle (tiles are numbered row-major,
+ * ceil(wo / tile_w) per row).  logits == NULL: only tiles / tile_h / tile_w are written (no GPU work). */
+int eagle_op_conv2d_argmax(int device, int precision, const float* x, int n, int h, int w, int cin, const float* w_hwio, const float* bias, int cout, int ks, int stride,
+                           float* logits, EagleArgmaxPart* parts, int* tiles, int* tile_h, int* tile_w);
 
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
