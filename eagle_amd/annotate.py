@@ -4,8 +4,8 @@ the ball, a disc per pitch key-point.
 
 Everything is drawn on the GPU by one kernel over the clip resident in HBM (include/eagle.h, eagle_annotate_*; csrc/annotate.hip), which also
 decides what a record's picture is; this module only passes arrays through and writes the container.  The rasterisation is the library's own
-(parity with cv2.ellipse / cv2.putText pixels is not claimed; tests/annot_ref.py defines every pixel).  The picture shows the raw records:
-tracker ids as they are, not the pandas post-processor's merged or interpolated ones."""
+(parity with cv2.ellipse / cv2.putText pixels is not claimed; tests/annot_ref.py defines every pixel).  The picture shows the raw records, tracker ids as
+they are; CoordinateModel.annotate(table=...) draws the post-processed table (eagle_amd/postprocess.py) instead, as main.py does."""
 import numpy as np
 
 from . import lib

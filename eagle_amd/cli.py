@@ -6,11 +6,14 @@ the GPU path and write ``raw_coordinates.json`` exactly the way the reference's 
     python -m eagle_amd.cli --clip frames.npy --fps 25 --out output/myclip       # uint8 [n,h,w,3] BGR frames
 
     python -m eagle_amd.cli --frames 10 --fps 5 --out output/synthetic --annotated      # + annotated.y4m and the team mapping
+    python -m eagle_amd.cli --frames 30 --fps 5 --out output/synthetic --processed      # + raw_data.json, processed_data.json and the team mapping
 
 ``--annotated`` writes the annotated video of ``main.py:43-81`` as ``annotated.y4m`` (YUV4MPEG2: uncompressed I420, which common players open
 without a codec), drawn on the GPU from the raw records, and ``metadata.json`` then carries the ``team_mapping`` like the reference's
-(``main.py:37-38``).  Video decode, compressed encode and the pandas post-processor of ``main.py:34-41`` are out of scope
-(SURVEY §8f rows 3-4).  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(``main.py:37-38``).  ``--processed`` runs the reference's post-processor (``main.py:34-41``: ``Processor.process_data`` and ``format_data``) on
+the GPU (eagle_amd/postprocess.py) and writes ``raw_data.json`` (the table, one record per kept frame), ``processed_data.json`` and the
+``team_mapping`` into ``metadata.json``; together with ``--annotated`` the video is then drawn from the processed table (kept frames only,
+interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -77,6 +80,10 @@ def main(argv=None):
     ap.add_argument("--native-fps", type=float, default=None, help="frame rate of --clip: sample it down to --fps the way read_video does (io.py:17-25)")
     ap.add_argument("--annotated", action="store_true",
                     help="also write <out>/annotated.y4m (the reference's annotated video, main.py:43-81, as uncompressed YUV4MPEG2) and put the team mapping into metadata.json")
+    ap.add_argument("--processed", action="store_true",
+                    help="also run the post-processor of main.py:34-41 on the GPU: write <out>/raw_data.json and <out>/processed_data.json, put the team mapping into "
+                         "metadata.json, and draw --annotated from the processed table")
+    ap.add_argument("--smooth", action="store_true", help="with --processed: process_data(smooth=True)")
     a = ap.parse_args(argv)
 
     from . import synth
@@ -115,7 +122,20 @@ def main(argv=None):
     with open(os.path.join(a.out, "raw_coordinates.json"), "w") as f:
         json.dump(coordinates, f, default=float)
     meta = {"fps": a.fps, "frames": n, "seconds": dt, "note": "team_mapping needs the post-processor (out of scope)"}
-    if a.annotated:
+    if a.processed:
+        from . import postprocess
+        from .annotate import write_y4m
+        from .processor import Processor
+        table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth)
+        with open(os.path.join(a.out, "raw_data.json"), "w") as f:
+            json.dump(postprocess.json_rows(postprocess.raw_data_rows(table)), f)
+        with open(os.path.join(a.out, "processed_data.json"), "w") as f:
+            json.dump(postprocess.json_rows(postprocess.format_data(table)), f)
+        if a.annotated:
+            write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420", table=table), a.fps)
+        table.close()
+        meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
+    elif a.annotated:
         from .annotate import write_y4m
         from .processor import Processor
         team_mapping = Processor(model).get_team_mapping(frames, coordinates)

@@ -130,27 +130,42 @@ class CoordinateModel:
         self._last = (coords, recs, np.asarray(own, bool))
         return coords
 
-    def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr"):
+    def _records_of(self, coords_or_records, carried_as_plain=False):
+        """raw records, or the records behind the dict the LAST get_coordinates call of this model returned.  carried_as_plain: frames that use a
+        carried homography get H_valid = 0, so that their picture lists every key-point, as the dict does (cm.py:330,415)."""
+        if isinstance(coords_or_records, dict):
+            if self._last is None or coords_or_records is not self._last[0]:
+                raise ValueError("raw records, or the dict returned by this model's last get_coordinates call, expected")
+            _, recs, own = self._last
+            recs = np.array(recs, lib.RESULT_DTYPE, copy=True)
+            if carried_as_plain:
+                recs["H_valid"][~own] = 0
+            return recs
+        return np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1)
+
+    def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The frames with their records drawn on them (the reference's annotated video, main.py:43-81; include/eagle.h eagle_annotate_frames):
         uint8 [n, h, w, 3] for out_format "bgr", [n, 3h/2, w] for "nv12" / "i420".  ``frames`` as get_coordinates takes them (pixel_format "bgr",
         "nv12" or "i420"); ``coords_or_records``: raw records (process_records / flow_records), or the dict the LAST get_coordinates call of this
-        model returned; team_mapping: Processor.get_team_mapping's {player id: 0 | 1}, or None for a neutral player colour."""
-        if isinstance(coords_or_records, dict):
-            if self._last is None or coords_or_records is not self._last[0]:
-                raise ValueError("annotate() takes raw records, or the dict returned by this model's last get_coordinates call")
-            _, recs, own = self._last
-            recs = np.array(recs, lib.RESULT_DTYPE, copy=True)
-            recs["H_valid"][~own] = 0          # a carried homography: the dict lists every key-point of the frame (cm.py:330,415), and so does the picture
-        else:
-            recs = np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1)
+        model returned; team_mapping: Processor.get_team_mapping's {player id: 0 | 1}, or None for a neutral player colour.
+        ``table`` (postprocess.process_data): draw the processed table instead, as main.py does — one output frame per kept row, with the
+        interpolated ball, the folded goalkeeper ids and the table's team mapping; key-points still come from the frame's record."""
+        recs = self._records_of(coords_or_records, carried_as_plain=True)
         if len(recs) != len(frames):
             raise ValueError(f"{len(frames)} frames but {len(recs)} records")
-        if len(recs) == 0:
+        if table is not None:
+            frames = np.asarray(frames)[np.asarray(table.rows, np.int64)]
+        n = len(frames)
+        if n == 0:
             h, w = self.handle.cfg.frame_h, self.handle.cfg.frame_w
             return np.zeros((0, h, w, 3) if out_format == "bgr" else (0, h * 3 // 2, w), np.uint8)
         d = self._upload(frames, pixel_format)
         try:
-            return self.handle.annotate(d, len(recs), recs, team_mapping, out_format)
+            if table is None:
+                return self.handle.annotate(d, n, recs, team_mapping, out_format)
+            lists = [table.overlay(r, recs[int(f)]) for r, f in enumerate(table.rows)]
+            offsets = np.concatenate([[0], np.cumsum([len(p) for p in lists])]).astype(np.int32)
+            return self.handle.annotate_prims(d, n, np.concatenate(lists), offsets, out_format)
         finally:
             self.handle.free(d)
 

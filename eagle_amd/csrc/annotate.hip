@@ -380,6 +380,7 @@ static AnnotArgs annot_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst, 
 // algorithmic bytes per pixel: the BGR frame read once + the output written once
 static double annot_bytes_per_px(int fmt) { return 3.0 + (fmt == EAGLE_PIX_BGR ? 3.0 : 1.5); }
 
+static void upload_prims(EagleHandle* h, const std::vector<EaglePrim>& prims, const std::vector<int32_t>& offs, const EaglePrim** d_prims, const int32_t** d_offs);
 // the primitive lists of n records -> the handle's device buffer: [EaglePrim x total][int32 x (n + 1)], on s_main
 static void upload_overlays(EagleHandle* h, const EagleFrameResult* recs, int n, const int32_t* team_ids, const int32_t* team_vals, int n_team,
                             const EaglePrim** d_prims, const int32_t** d_offs)
@@ -392,6 +393,11 @@ static void upload_overlays(EagleHandle* h, const EagleFrameResult* recs, int n,
         prims.insert(prims.end(), one, one + k);
         offs[i + 1] = (int32_t)prims.size();
     }
+    upload_prims(h, prims, offs, d_prims, d_offs);
+}
+// ... and any primitive lists (frame k owns prims[offs[k] .. offs[k + 1]))
+static void upload_prims(EagleHandle* h, const std::vector<EaglePrim>& prims, const std::vector<int32_t>& offs, const EaglePrim** d_prims, const int32_t** d_offs)
+{
     const size_t pb = prims.size() * sizeof(EaglePrim), need = pb + offs.size() * sizeof(int32_t);
     if (need > h->annot_prims_cap) {
         if (h->annot_prims) HIP_CHECK(hipFree(h->annot_prims));
@@ -453,15 +459,12 @@ int eagle_annotate_device_frames(EagleHandle* h, const void* d_bgr, int n, const
     API_END(h)
 }
 
-int eagle_annotate_frames(EagleHandle* h, const void* d_bgr, int n, const EagleFrameResult* recs, const int32_t* team_ids, const int32_t* team_vals, int n_team,
-                          int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
+// n frames drawn with the uploaded primitive lists -> host memory in the caller's layout
+static void annotate_to_host(EagleHandle* h, const void* d_bgr, int n, const EaglePrim* dp, const int32_t* dof, int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
 {
-    API_BEGIN_H(h)
-    annotate_begin(h, d_bgr, n, recs, team_ids, team_vals, n_team, out);
     const int fh = h->cfg.frame_h, fw = h->cfg.frame_w;
     const YuvGeom g = yuv_geometry(out_format, fh, fw, out_layout, true);          // the caller's layout
     const YuvGeom dg = yuv_geometry(out_format, fh, fw, nullptr, true);            // what the kernel writes: dense frames in the handle's staging
-    if (n == 0) return EAGLE_OK;
     const bool pinned = host_pinned(h, out);
     const int B = h->cfg.batch;
     const size_t fsz = (size_t)dg.dense_bytes, need = fsz * B;
@@ -477,8 +480,6 @@ int eagle_annotate_frames(EagleHandle* h, const void* d_bgr, int n, const EagleF
         HIP_CHECK(hipHostMalloc((void**)&h->annot_ring, need, hipHostMallocDefault));
         h->annot_ring_cap = need;
     }
-    const EaglePrim* dp; const int32_t* dof;
-    upload_overlays(h, recs, n, team_ids, team_vals, n_team, &dp, &dof);
     for (int i = 0; i < n; i += B) {
         const int na = std::min(B, n - i);
         annotate_device(h, (const uint8_t*)d_bgr + (size_t)i * fh * fw * 3, na, dp, dof + i, dg, h->annot_out);
@@ -504,6 +505,36 @@ int eagle_annotate_frames(EagleHandle* h, const void* d_bgr, int n, const EagleF
                 else for (int64_t r = 0; r < p.rows; ++r) memcpy(d0 + r * p.pitch, s0 + r * p.row_bytes, (size_t)p.row_bytes);
             });
     }
+}
+
+int eagle_annotate_frames(EagleHandle* h, const void* d_bgr, int n, const EagleFrameResult* recs, const int32_t* team_ids, const int32_t* team_vals, int n_team,
+                          int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    API_BEGIN_H(h)
+    annotate_begin(h, d_bgr, n, recs, team_ids, team_vals, n_team, out);
+    (void)yuv_geometry(out_format, h->cfg.frame_h, h->cfg.frame_w, out_layout, true);
+    if (n == 0) return EAGLE_OK;
+    const EaglePrim* dp; const int32_t* dof;
+    upload_overlays(h, recs, n, team_ids, team_vals, n_team, &dp, &dof);
+    annotate_to_host(h, d_bgr, n, dp, dof, out_format, out_layout, out);
+    API_END(h)
+}
+
+int eagle_annotate_frames_prims(EagleHandle* h, const void* d_bgr, int n, const EaglePrim* prims, const int32_t* prim_offsets, int out_format,
+                                const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    API_BEGIN_H(h)
+    if (!d_bgr || !out || n < 0 || !prim_offsets || (n > 0 && prim_offsets[n] > prim_offsets[0] && !prims)) fail(EAGLE_E_INVALID, "bad argument");
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    (void)yuv_geometry(out_format, h->cfg.frame_h, h->cfg.frame_w, out_layout, true);
+    check_prims(prims, prim_offsets, n);
+    if (n == 0) return EAGLE_OK;
+    std::vector<int32_t> offs(prim_offsets, prim_offsets + n + 1);
+    for (int32_t& v : offs) v -= prim_offsets[0];
+    const std::vector<EaglePrim> list(prims ? prims + prim_offsets[0] : nullptr, prims ? prims + prim_offsets[n] : nullptr);
+    const EaglePrim* dp; const int32_t* dof;
+    upload_prims(h, list, offs, &dp, &dof);
+    annotate_to_host(h, d_bgr, n, dp, dof, out_format, out_layout, out);
     API_END(h)
 }
 

@@ -63,6 +63,17 @@ MAX_PRIMS = 2 * MAX_DET + MAX_KP + 1                                   # include
 PRIM_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4", 6), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("pad", "u1")], align=True)
 
 
+class EaglePostParams(C.Structure):
+    _fields_ = [("fps", C.c_int32), ("frame_w", C.c_int32), ("smooth", C.c_int32), ("filter_ball", C.c_int32), ("team_ids", C.c_void_p),
+                ("team_vals", C.c_void_p), ("n_team", C.c_int32), ("reserved", C.c_int32), ("max_bytes", C.c_int64)]
+
+
+POST_PLAYER, POST_GOALKEEPER, POST_BALL, POST_BOUNDARY = 0, 1, 2, 3    # include/eagle.h EAGLE_POST_*
+POST_NO_BALL = 1                                                       # ... flag: fewer than two ball sightings
+POSTCOL_DTYPE = np.dtype([("kind", "<i4"), ("id", "<i4"), ("video", "<i4"), ("reserved", "<i4")])      # EaglePostColumn
+E_INVALID = -1
+
+
 class EagleKernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 40), ("ms", C.c_float), ("launches", C.c_int32), ("bytes", C.c_double), ("flop", C.c_double)]
 
@@ -170,6 +181,15 @@ def load():
     L.eagle_annotate_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, yl, vp]
     L.eagle_overlay_from_record.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(i32)]
     L.eagle_op_annotate.argtypes = [i32, u8p, i32, i32, i32, vp, vp, i32, yl, u8p]
+    L.eagle_annotate_frames_prims.argtypes = [vp, vp, i32, vp, vp, i32, yl, vp]
+    L.eagle_postprocess.argtypes = [vp, vp, i32, C.POINTER(EaglePostParams), C.POINTER(vp)]
+    L.eagle_post_free.argtypes = [vp]
+    L.eagle_post_free.restype = None
+    L.eagle_post_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.eagle_post_layout.argtypes = [vp, vp, vp]
+    L.eagle_post_values.argtypes = [vp, vp]
+    L.eagle_post_device_values.argtypes = [vp, C.POINTER(vp)]
+    L.eagle_overlay_from_table.argtypes = [vp, i32, vp, vp, i32, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -181,7 +201,9 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_find_homography", "eagle_op_detect_tail", "eagle_op_post", "eagle_op_conv2d_argmax", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
            "eagle_clip_set_keypoints", "eagle_clip_flow", "eagle_clip_run", "eagle_clip_fetch", "eagle_debug", "eagle_track_open", "eagle_track_frames", "eagle_track_frames_cmc", "eagle_clip_motion_ecc", "eagle_clip_motion", "eagle_team_colors",
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
-           "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate"]
+           "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate",
+           "eagle_annotate_frames_prims", "eagle_postprocess", "eagle_post_free", "eagle_post_shape", "eagle_post_layout", "eagle_post_values",
+           "eagle_post_device_values", "eagle_overlay_from_table"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -453,6 +475,36 @@ class Handle:
                                                  None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p)), "annotate_frames")
         return out
 
+    def annotate_prims(self, d_bgr, n, prims, offsets, fmt="bgr", layout=None, out=None):
+        """As annotate, drawing the caller's primitive lists (PRIM_DTYPE array + n + 1 offsets) instead of the records' (eagle_annotate_frames_prims)."""
+        h, w = self.cfg.frame_h, self.cfg.frame_w
+        prims = np.ascontiguousarray(prims, PRIM_DTYPE)
+        offsets = np.ascontiguousarray(offsets, np.int32)
+        if len(offsets) != n + 1 or (n and int(offsets[-1]) > len(prims)):
+            raise EagleError("annotate_prims: offsets must have n + 1 entries inside the primitive array")
+        lay = _yuv_layout(layout)
+        need = out_span(fmt, h, w, lay, n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+            if lay is None:
+                out = out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise EagleError(f"annotate_prims: out must be a contiguous uint8 array of at least {need} bytes")
+        self._check(self.L.eagle_annotate_frames_prims(self._h, d_bgr, n, prims.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), _out_pix(fmt),
+                                                       None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p)), "annotate_frames_prims")
+        return out
+
+    # --- the clip post-processor (include/eagle.h, eagle_postprocess) -------------------------------------------
+    def postprocess(self, recs, fps, frame_w, team_mapping=None, smooth=False, filter_ball=False, max_bytes=0):
+        """The records of a finished clip -> a PostTable (the reference's Processor.process_data table, built on the GPU and resident there)."""
+        recs = np.ascontiguousarray(recs, RESULT_DTYPE).reshape(-1)
+        ids, vals, nt = _team_arrays(team_mapping)
+        p = EaglePostParams(int(fps), int(frame_w), int(bool(smooth)), int(filter_ball), None if ids is None else ids.ctypes.data, None if vals is None else vals.ctypes.data,
+                            nt, 0, int(max_bytes))
+        t = C.c_void_p()
+        self._check(self.L.eagle_postprocess(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), C.byref(p), C.byref(t)), "postprocess")
+        return PostTable(self, t, team_mapping)
+
     def reproject(self, recs, Hs, flags):
         """In place: re-project foot points / boundaries of the flagged records with the given homographies (cadence mode)."""
         Hs = np.ascontiguousarray(Hs, np.float64).reshape(-1, 9)
@@ -596,6 +648,64 @@ class Handle:
         assert out.dtype == RESULT_DTYPE and len(out) == len(local) * world and out.flags.c_contiguous
         self._check(self.L.eagle_gather(self._h, local.ctypes.data_as(C.c_void_p), len(local), out.ctypes.data_as(C.c_void_p)), "gather")
         return out
+
+
+BOUNDARY_NAMES = ("Bottom_Left", "Top_Left", "Top_Right", "Bottom_Right")
+
+
+class PostTable:
+    """A processed clip table (EaglePostTable): ``rows`` kept frame numbers, ``columns`` (POSTCOL_DTYPE, table order) and their reference ``names``,
+    ``flags``; ``values`` copies the table to the host once: float64 [columns][rows][2], NaN = missing.  close() frees the device memory."""
+
+    def __init__(self, handle, ptr, team_mapping=None):
+        self.handle, self._t, self.team_mapping = handle, ptr, team_mapping
+        L = handle.L
+        r, c, f = C.c_int32(), C.c_int32(), C.c_int32()
+        L.eagle_post_shape(ptr, C.byref(r), C.byref(c), C.byref(f))
+        self.flags = f.value
+        self.rows = np.zeros(r.value, np.int32)
+        self.columns = np.zeros(c.value, POSTCOL_DTYPE)
+        L.eagle_post_layout(ptr, self.rows.ctypes.data_as(C.c_void_p), self.columns.ctypes.data_as(C.c_void_p))
+        self.names = [BOUNDARY_NAMES[int(k["id"])] if k["kind"] == POST_BOUNDARY else
+                      ("Ball" if k["kind"] == POST_BALL else f"{'Player' if k['kind'] == POST_PLAYER else 'Goalkeeper'}_{int(k['id'])}") + ("_video" if k["video"] else "")
+                      for k in self.columns]
+        self._values = None
+
+    @property
+    def values(self):
+        if self._values is None:
+            v = np.zeros((len(self.columns), len(self.rows), 2), np.float64)
+            self.handle._check(self.handle.L.eagle_post_values(self._t, v.ctypes.data_as(C.c_void_p)), "post_values")
+            self._values = v
+        return self._values
+
+    @property
+    def device_values(self):
+        d = C.c_void_p()
+        self.handle._check(self.handle.L.eagle_post_device_values(self._t, C.byref(d)), "post_device_values")
+        return d.value
+
+    def overlay(self, row, rec=None):
+        """The primitives drawn for processed row ``row`` (+ the key-points of ``rec``) -> PRIM_DTYPE array (eagle_overlay_from_table)."""
+        cap = 2 * len(self.columns) + MAX_PRIMS
+        out = np.zeros(cap, PRIM_DTYPE); n = C.c_int(0)
+        rec = None if rec is None else np.ascontiguousarray(rec, RESULT_DTYPE).reshape(-1)[:1]
+        self.handle._check(self.handle.L.eagle_overlay_from_table(self._t, int(row), None if rec is None else rec.ctypes.data_as(C.c_void_p),
+                                                                  out.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "overlay_from_table")
+        return out[: n.value].copy()
+
+    def close(self):
+        if self._t:
+            _ = self.values                     # (the host view outlives the device memory)
+            self.handle.L.eagle_post_free(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            if self._t and self.handle._h:
+                self.handle.L.eagle_post_free(self._t)
+        except Exception:
+            pass
 
 
 def comm_unique_id():

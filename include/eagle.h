@@ -244,6 +244,62 @@ int eagle_overlay_from_record(const EagleFrameResult* rec, const int32_t* team_i
 int eagle_op_annotate(int device, const uint8_t* bgr, int n, int h, int w, const EaglePrim* prims, const int32_t* prim_offsets /* n + 1 */,
                       int out_format, const EagleYuvLayout* out_layout, uint8_t* out);
 
+/* As eagle_annotate_frames with the primitive lists given by the caller (eagle_op_annotate's convention: frame k owns prims[prim_offsets[k] ..
+ * prim_offsets[k + 1]), at most EAGLE_MAX_PRIMS) instead of derived from records: how a processed table's rows are drawn (eagle_overlay_from_table). */
+int eagle_annotate_frames_prims(EagleHandle* h, const void* d_bgr, int n, const EaglePrim* prims, const int32_t* prim_offsets /* n + 1 */, int out_format,
+                                const EagleYuvLayout* out_layout, uint8_t* out);
+
+/* ---- the clip post-processor: Processor.process_data / format_data of eagle/processor.py:30-403, what main.py:34-41 writes as raw_data.json and
+ * processed_data.json and draws the annotated video from ------------------------------------------------------------------------------------
+ * eagle_postprocess takes the n records of a finished clip (record i = frame i) and builds the reference's table on the GPU: one row per frame with
+ * at least one Player / Goalkeeper, one column per boundary corner, per {Player, Goalkeeper} id and its video point, and Ball / Ball_video, in the
+ * reference's column order; ids seen in fewer than 1 % of the rows dropped; the ball chosen per frame by parse_ball_detections_with_kalman(filter =
+ * False) and filled linearly to both ends; Player_k folded into Goalkeeper_k (combine_first); every column interpolated linearly over row POSITIONS
+ * inside its valid span; with `smooth` every other row, from the first, replaced by the interpolation of its neighbours.  The arithmetic is pandas'
+ * (np.interp in float64: slope * (x - x0) + y0, no contraction), pinned bit for bit by tests/golden/post_golden.json through tests/post_ref.py.  The
+ * reference's pairwise id merge (proc.py:218-319) never merges as written (its overlap test holds for any two non-empty columns) and is reproduced
+ * as that: nothing.  Host C++ discovers columns and walks the ball; two launches (post.hip) on the handle's main stream build the table, which stays
+ * resident in HBM until eagle_post_free.  The handle's records, staging buffers and graphs are not involved.
+ * Where the reference raises or returns garbage, the library is defined instead:
+ *   - fewer than two ball sightings (the reference hands its candidate lists on and fails later): Ball / Ball_video are all NaN, EAGLE_POST_NO_BALL is set;
+ *   - the boundary columns and Ball / Ball_video are always kept (the reference's 1 % filter can drop them; its format_data then raises KeyError);
+ *   - the goalkeeper fold of an id needs all four of its columns (the reference raises KeyError when Goalkeeper_<id> was dropped by the filter);
+ *   - a clip without a kept frame gives a table of 0 rows and 0 columns (the reference: an empty frame; it raises on a clip of no frames);
+ *   - non-finite boundary values count as missing;
+ *   - filter_ball != 0 (filter_ball_detections=True) is refused with EAGLE_E_INVALID: it needs cv2's SVD-based Kalman gain, which nothing here pins.
+ * Unpinned: with several ball candidates the nearest to cv2.KalmanFilter.predict() wins; predict is taken to compute statePre = F * statePost from a
+ * zero statePost (the reference sets statePre only), so without correct() the prediction stays at the origin (tests/post_ref.py::kalman_predict).
+ * More than 2^20 kept frames, or a table beyond the memory budget (max_bytes; 0: nine tenths of the device's free memory), is EAGLE_E_INVALID with
+ * the sizes in the message, before anything is launched. */
+#define EAGLE_POST_PLAYER 0
+#define EAGLE_POST_GOALKEEPER 1
+#define EAGLE_POST_BALL 2
+#define EAGLE_POST_BOUNDARY 3      /* id 0 .. 3: Bottom_Left, Top_Left, Top_Right, Bottom_Right */
+#define EAGLE_POST_NO_BALL 1       /* flag: fewer than two ball sightings, the ball columns are all NaN */
+typedef struct EaglePostTable EaglePostTable;
+typedef struct EaglePostParams {
+    int32_t fps;                   /* > 0 (the reference's merge thresholds derive from it; its merge never fires) */
+    int32_t frame_w;               /* > 0 (the refused ball filter's threshold, 0.1 * width) */
+    int32_t smooth;                /* process_data(smooth=...) */
+    int32_t filter_ball;           /* must be 0 */
+    const int32_t* team_ids;       /* Processor.get_team_mapping as two arrays of n_team entries: kept with the table for eagle_overlay_from_table; */
+    const int32_t* team_vals;      /* team_ids NULL: no mapping (players drawn white) */
+    int32_t n_team;
+    int32_t reserved;
+    int64_t max_bytes;             /* device-memory budget of the call, 0 = nine tenths of what is free */
+} EaglePostParams;
+typedef struct EaglePostColumn { int32_t kind /* EAGLE_POST_* */, id, video /* 1: the "_video" column */, reserved; } EaglePostColumn;
+int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, EaglePostTable** out);
+void eagle_post_free(EaglePostTable* t);
+int eagle_post_shape(const EaglePostTable* t, int32_t* rows, int32_t* cols, int32_t* flags);                 /* any pointer may be NULL */
+int eagle_post_layout(const EaglePostTable* t, int32_t* frames /* rows: kept frame numbers */, EaglePostColumn* columns /* cols, table order */);
+int eagle_post_values(EaglePostTable* t, double* values /* [cols][rows][2] = x, y; NaN = missing */);        /* copies the table to the host */
+int eagle_post_device_values(const EaglePostTable* t, const double** d_values);                              /* the same layout, in HBM */
+/* The overlay main.py:44-77 draws for processed row `row` (no launch; the table is copied to the host once): per video column in table order the
+ * foot arc and id at (int(x), int(y)) — goalkeepers green, team 0 red, other teams blue, players without a team skipped (white without a mapping) —
+ * the marker above the interpolated ball, then, with rec != NULL, that record's key-point discs (the three sources of eagle_overlay_from_record). */
+int eagle_overlay_from_table(EaglePostTable* t, int row, const EagleFrameResult* rec, EaglePrim* out, int cap, int* n_out);
+
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
  * flags[i] = 0 keep the record, 1 re-project foot points and boundaries with Hs[9*i..], 2 no homography available yet. */
