@@ -7,13 +7,16 @@ the GPU path and write ``raw_coordinates.json`` exactly the way the reference's 
 
     python -m eagle_amd.cli --frames 10 --fps 5 --out output/synthetic --annotated      # + annotated.y4m and the team mapping
     python -m eagle_amd.cli --frames 30 --fps 5 --out output/synthetic --processed      # + raw_data.json, processed_data.json and the team mapping
+    python -m eagle_amd.cli --frames 30 --fps 5 --out output/synthetic --processed --minimap --minimap-voronoi      # + minimap.y4m
 
 ``--annotated`` writes the annotated video of ``main.py:43-81`` as ``annotated.y4m`` (YUV4MPEG2: uncompressed I420, which common players open
 without a codec), drawn on the GPU from the raw records, and ``metadata.json`` then carries the ``team_mapping`` like the reference's
 (``main.py:37-38``).  ``--processed`` runs the reference's post-processor (``main.py:34-41``: ``Processor.process_data`` and ``format_data``) on
 the GPU (eagle_amd/postprocess.py) and writes ``raw_data.json`` (the table, one record per kept frame), ``processed_data.json`` and the
 ``team_mapping`` into ``metadata.json``; together with ``--annotated`` the video is then drawn from the processed table (kept frames only,
-interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  ``--minimap`` (with ``--processed``) writes ``minimap.y4m``: the processed table as
+a top-down video of the pitch at the clip's fps (eagle_amd/minimap.py; ``--minimap-voronoi`` tints the areas each team controls, ``--minimap-scale``
+sets the pixels per metre).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -84,7 +87,12 @@ def main(argv=None):
                     help="also run the post-processor of main.py:34-41 on the GPU: write <out>/raw_data.json and <out>/processed_data.json, put the team mapping into "
                          "metadata.json, and draw --annotated from the processed table")
     ap.add_argument("--smooth", action="store_true", help="with --processed: process_data(smooth=True)")
+    ap.add_argument("--minimap", action="store_true", help="with --processed: also write <out>/minimap.y4m, the processed table as a top-down video of the pitch")
+    ap.add_argument("--minimap-voronoi", action="store_true", help="with --minimap: tint the pitch by the team whose player is nearest")
+    ap.add_argument("--minimap-scale", type=int, default=8, help="with --minimap: pixels per metre (even, 2 .. 32)")
     a = ap.parse_args(argv)
+    if a.minimap and not a.processed:
+        ap.error("--minimap draws the processed table: it needs --processed")
 
     from . import synth
     from .coordinate_model import CoordinateModel
@@ -133,6 +141,9 @@ def main(argv=None):
             json.dump(postprocess.json_rows(postprocess.format_data(table)), f)
         if a.annotated:
             write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420", table=table), a.fps)
+        if a.minimap:
+            from .minimap import minimap
+            write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420"), a.fps)
         table.close()
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
     elif a.annotated:

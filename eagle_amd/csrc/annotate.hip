@@ -11,21 +11,18 @@
 // of a source row.  Tail strips and addresses without the alignment go byte by byte.  The source is never written; no annotated BGR
 // intermediate goes through HBM unless BGR is the requested output.
 //
+// The "out" part is pix_out.h's write_strip, shared with minimap.hip (K21).
+//
 // The host side of the same file: overlay_from_record (the ONE place that decides what a record's picture is), the argument checks and the
 // eagle_annotate_* / eagle_op_annotate entries.
 #include "runtime.h"
 #include "annot_font.h"
+#include "pix_out.h"
 
 namespace eagle {
 
-static constexpr int AN_STRIP = 8, AN_TW = 256, AN_TH = 16;
-static constexpr int AN_SX = AN_TW / AN_STRIP, AN_THREADS = AN_SX * (AN_TH / 2);      // 32 strips x 8 row pairs = 256 threads
 static constexpr int ARC_A = 35, ARC_B = 18, GLYPH_W = 10, GLYPH_H = 14, GLYPH_ADV = 12;
 static constexpr int COORD_MAX = 1 << 20, RADIUS_MAX = 1 << 14, LABEL_MAX_ID = 99999, AN_MAX_DIM = 32767;     // (tile-clamped boxes are packed as 16-bit pairs)
-// OpenCV's BGR -> YUV 4:2:0 coefficients (color_yuv.simd.hpp), 20-bit fixed point
-static constexpr int AN_SHIFT = 20, AN_RY = 269484, AN_GY = 528482, AN_BY = 102760, AN_RU = -155188, AN_GU = -305135, AN_BU = 460324,
-                     AN_RV = 460324, AN_GV = -385875, AN_BV = -74448;
-
 __constant__ uint8_t c_font[10][ANNOT_FONT_ROWS] = {ANNOT_FONT_TABLE};
 
 // a primitive as the tile keeps it: LABEL carries its digits (a[3] = count, a[4] = 4 bits per digit, first digit lowest), every kind its bounding box
@@ -97,26 +94,6 @@ __device__ __forceinline__ void unpack8(const uint32_t* w, uint32_t* px)
         px[4 * q] = w0 & 0xffffffu; px[4 * q + 1] = (w0 >> 24) | (w1 & 0xffffu) << 8; px[4 * q + 2] = (w1 >> 16) | (w2 & 0xffu) << 16; px[4 * q + 3] = w2 >> 8;
     }
 }
-__device__ __forceinline__ void pack8(const uint32_t* px, uint32_t* w)
-{
-    #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const uint32_t* p = px + 4 * q;
-        w[3 * q] = p[0] | p[1] << 24; w[3 * q + 1] = p[1] >> 8 | p[2] << 16; w[3 * q + 2] = p[2] >> 16 | p[3] << 8;
-    }
-}
-__device__ __forceinline__ uint32_t luma(uint32_t p)
-{
-    const int b = p & 255, g = (p >> 8) & 255, r = (p >> 16) & 255;
-    return (uint32_t)((AN_RY * r + AN_GY * g + AN_BY * b + (16 << AN_SHIFT) + (1 << (AN_SHIFT - 1))) >> AN_SHIFT);
-}
-__device__ __forceinline__ void chroma(uint32_t p, uint32_t& u, uint32_t& v)
-{
-    const int b = p & 255, g = (p >> 8) & 255, r = (p >> 16) & 255;
-    u = (uint32_t)((AN_RU * r + AN_GU * g + AN_BU * b + (128 << AN_SHIFT) + (1 << (AN_SHIFT - 1))) >> AN_SHIFT);
-    v = (uint32_t)((AN_RV * r + AN_GV * g + AN_BV * b + (128 << AN_SHIFT) + (1 << (AN_SHIFT - 1))) >> AN_SHIFT);
-}
-
 __global__ __launch_bounds__(AN_THREADS) void annotate_kernel(AnnotArgs a)
 {
     __shared__ TilePrim s_list[EAGLE_MAX_PRIMS];
@@ -207,63 +184,7 @@ __global__ __launch_bounds__(AN_THREADS) void annotate_kernel(AnnotArgs a)
         }
     }
 
-    // ---- out ----
-    uint8_t* fr = a.dst + (int64_t)f * a.frame_stride;
-    if (a.fmt == EAGLE_PIX_BGR) {
-        #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (r >= rows) continue;
-            uint8_t* d = fr + (int64_t)(y0 + r) * a.y_pitch + (int64_t)x0 * 3;
-            const uintptr_t da = (uintptr_t)d;
-            if (cnt == AN_STRIP && (da & 3) == 0) {
-                uint32_t w[6];
-                pack8(px[r], w);
-                if ((da & 7) == 0) {
-                    uint2* o = (uint2*)d;
-                    o[0] = make_uint2(w[0], w[1]); o[1] = make_uint2(w[2], w[3]); o[2] = make_uint2(w[4], w[5]);
-                } else {
-                    #pragma unroll
-                    for (int k = 0; k < 6; ++k) ((uint32_t*)d)[k] = w[k];
-                }
-            } else {
-                #pragma unroll
-                for (int k = 0; k < AN_STRIP; ++k)
-                    if (k < cnt) { d[3 * k] = (uint8_t)px[r][k]; d[3 * k + 1] = (uint8_t)(px[r][k] >> 8); d[3 * k + 2] = (uint8_t)(px[r][k] >> 16); }
-            }
-        }
-        return;
-    }
-    uint32_t u[AN_STRIP / 2], v[AN_STRIP / 2];
-    #pragma unroll
-    for (int k = 0; k < AN_STRIP / 2; ++k) chroma(px[0][2 * k], u[k], v[k]);        // the even-row, even-column pixel of each 2 x 2 block
-    const int64_t crow = (int64_t)(y0 >> 1) * a.c_pitch + (int64_t)(x0 >> 1) * a.c_step;
-    uint8_t* up = fr + a.c_offset + crow;
-    uint8_t* vp = fr + a.v_offset + crow;
-    #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        uint8_t* d = fr + (int64_t)(y0 + r) * a.y_pitch + x0;
-        uint32_t y[AN_STRIP];
-        #pragma unroll
-        for (int k = 0; k < AN_STRIP; ++k) y[k] = luma(px[r][k]);
-        if (cnt == AN_STRIP && a.vec) {
-            *(uint2*)d = make_uint2(y[0] | y[1] << 8 | y[2] << 16 | y[3] << 24, y[4] | y[5] << 8 | y[6] << 16 | y[7] << 24);
-        } else {
-            #pragma unroll
-            for (int k = 0; k < AN_STRIP; ++k) if (k < cnt) d[k] = (uint8_t)y[k];
-        }
-    }
-    if (cnt == AN_STRIP && a.vec) {
-        if (a.c_step == 2) {
-            *(uint2*)up = make_uint2(u[0] | v[0] << 8 | u[1] << 16 | v[1] << 24, u[2] | v[2] << 8 | u[3] << 16 | v[3] << 24);
-        } else {
-            *(uint32_t*)up = u[0] | u[1] << 8 | u[2] << 16 | u[3] << 24;
-            *(uint32_t*)vp = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
-        }
-    } else {
-        #pragma unroll
-        for (int k = 0; k < AN_STRIP / 2; ++k)
-            if (2 * k < cnt) { up[k * a.c_step] = (uint8_t)u[k]; vp[k * a.c_step] = (uint8_t)v[k]; }
-    }
+    write_strip(a, f, x0, y0, cnt, rows, px);
 }
 
 void annotate_launch(const AnnotArgs& args, int n, hipStream_t s)
@@ -359,7 +280,7 @@ void check_prims(const EaglePrim* prims, const int32_t* offs, int n)
 }
 
 // the kernel's view of an output layout the one check (yuv_geometry) has resolved
-static AnnotArgs annot_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst, const EaglePrim* prims, const int32_t* offs)
+AnnotArgs annot_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst, const EaglePrim* prims, const int32_t* offs)
 {
     if (g.h > AN_MAX_DIM || g.w > AN_MAX_DIM) fail(EAGLE_E_INVALID, "frames of %d x %d are beyond the %d pixels per side annotated output handles", g.w, g.h, AN_MAX_DIM);
     AnnotArgs a{};
@@ -429,6 +350,53 @@ static void annotate_device(EagleHandle* h, const uint8_t* d_bgr, int n, const E
     if (h->prof) collect_spans(h);
 }
 
+void frames_to_host(EagleHandle* h, int n, int fh, int fw, int batch, int out_format, const EagleYuvLayout* out_layout, uint8_t* out,
+                    const std::function<void(int, int, const YuvGeom&, uint8_t*)>& draw)
+{
+    const YuvGeom g = yuv_geometry(out_format, fh, fw, out_layout, true);          // the caller's layout
+    const YuvGeom dg = yuv_geometry(out_format, fh, fw, nullptr, true);            // what the kernel writes: dense frames in the handle's staging
+    const bool pinned = host_pinned(h, out);
+    const int B = std::max(1, batch);
+    const size_t fsz = (size_t)dg.dense_bytes, need = fsz * B;
+    if (need > h->annot_out_cap) {
+        if (h->annot_out) HIP_CHECK(hipFree(h->annot_out));
+        h->annot_out = nullptr; h->annot_out_cap = 0;
+        HIP_CHECK(hipMalloc((void**)&h->annot_out, need));
+        h->annot_out_cap = need;
+    }
+    if (!pinned && need > h->annot_ring_cap) {
+        if (h->annot_ring) HIP_CHECK(hipHostFree(h->annot_ring));
+        h->annot_ring = nullptr; h->annot_ring_cap = 0;
+        HIP_CHECK(hipHostMalloc((void**)&h->annot_ring, need, hipHostMallocDefault));
+        h->annot_ring_cap = need;
+    }
+    for (int i = 0; i < n; i += B) {
+        const int na = std::min(B, n - i);
+        draw(i, na, dg, h->annot_out);
+        uint8_t* dst = out + (size_t)i * g.frame_stride;
+        if (pinned && g.dense) {
+            HIP_CHECK(hipMemcpyAsync(dst, h->annot_out, fsz * na, hipMemcpyDeviceToHost, h->s_main));
+        } else if (pinned) {
+            for (int k = 0; k < na; ++k)
+                for (int q = 0; q < g.nplanes; ++q)
+                    HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)k * g.frame_stride + g.pl[q].off, (size_t)g.pl[q].pitch, h->annot_out + (size_t)k * fsz + g.pl[q].dense_off,
+                                               (size_t)g.pl[q].row_bytes, (size_t)g.pl[q].row_bytes, (size_t)g.pl[q].rows, hipMemcpyDeviceToHost, h->s_main));
+        } else {
+            HIP_CHECK(hipMemcpyAsync(h->annot_ring, h->annot_out, fsz * na, hipMemcpyDeviceToHost, h->s_main));
+        }
+        HIP_CHECK(hipStreamSynchronize(h->s_main));
+        if (!pinned)
+            h->pool->run(na * g.nplanes, [&](int t) {
+                const int k = t / g.nplanes;
+                const HostPlane& p = g.pl[t % g.nplanes];
+                const uint8_t* s0 = h->annot_ring + (size_t)k * fsz + p.dense_off;
+                uint8_t* d0 = dst + (size_t)k * g.frame_stride + p.off;
+                if (p.pitch == p.row_bytes) memcpy(d0, s0, (size_t)(p.rows * p.row_bytes));
+                else for (int64_t r = 0; r < p.rows; ++r) memcpy(d0 + r * p.pitch, s0 + r * p.row_bytes, (size_t)p.row_bytes);
+            });
+    }
+}
+
 }  // namespace eagle
 
 extern "C" {
@@ -463,48 +431,9 @@ int eagle_annotate_device_frames(EagleHandle* h, const void* d_bgr, int n, const
 static void annotate_to_host(EagleHandle* h, const void* d_bgr, int n, const EaglePrim* dp, const int32_t* dof, int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
 {
     const int fh = h->cfg.frame_h, fw = h->cfg.frame_w;
-    const YuvGeom g = yuv_geometry(out_format, fh, fw, out_layout, true);          // the caller's layout
-    const YuvGeom dg = yuv_geometry(out_format, fh, fw, nullptr, true);            // what the kernel writes: dense frames in the handle's staging
-    const bool pinned = host_pinned(h, out);
-    const int B = h->cfg.batch;
-    const size_t fsz = (size_t)dg.dense_bytes, need = fsz * B;
-    if (need > h->annot_out_cap) {
-        if (h->annot_out) HIP_CHECK(hipFree(h->annot_out));
-        h->annot_out = nullptr; h->annot_out_cap = 0;
-        HIP_CHECK(hipMalloc((void**)&h->annot_out, need));
-        h->annot_out_cap = need;
-    }
-    if (!pinned && need > h->annot_ring_cap) {
-        if (h->annot_ring) HIP_CHECK(hipHostFree(h->annot_ring));
-        h->annot_ring = nullptr; h->annot_ring_cap = 0;
-        HIP_CHECK(hipHostMalloc((void**)&h->annot_ring, need, hipHostMallocDefault));
-        h->annot_ring_cap = need;
-    }
-    for (int i = 0; i < n; i += B) {
-        const int na = std::min(B, n - i);
-        annotate_device(h, (const uint8_t*)d_bgr + (size_t)i * fh * fw * 3, na, dp, dof + i, dg, h->annot_out);
-        uint8_t* dst = out + (size_t)i * g.frame_stride;
-        if (pinned && g.dense) {
-            HIP_CHECK(hipMemcpyAsync(dst, h->annot_out, fsz * na, hipMemcpyDeviceToHost, h->s_main));
-        } else if (pinned) {
-            for (int k = 0; k < na; ++k)
-                for (int q = 0; q < g.nplanes; ++q)
-                    HIP_CHECK(hipMemcpy2DAsync(dst + (size_t)k * g.frame_stride + g.pl[q].off, (size_t)g.pl[q].pitch, h->annot_out + (size_t)k * fsz + g.pl[q].dense_off,
-                                               (size_t)g.pl[q].row_bytes, (size_t)g.pl[q].row_bytes, (size_t)g.pl[q].rows, hipMemcpyDeviceToHost, h->s_main));
-        } else {
-            HIP_CHECK(hipMemcpyAsync(h->annot_ring, h->annot_out, fsz * na, hipMemcpyDeviceToHost, h->s_main));
-        }
-        HIP_CHECK(hipStreamSynchronize(h->s_main));
-        if (!pinned)
-            h->pool->run(na * g.nplanes, [&](int t) {
-                const int k = t / g.nplanes;
-                const HostPlane& p = g.pl[t % g.nplanes];
-                const uint8_t* s0 = h->annot_ring + (size_t)k * fsz + p.dense_off;
-                uint8_t* d0 = dst + (size_t)k * g.frame_stride + p.off;
-                if (p.pitch == p.row_bytes) memcpy(d0, s0, (size_t)(p.rows * p.row_bytes));
-                else for (int64_t r = 0; r < p.rows; ++r) memcpy(d0 + r * p.pitch, s0 + r * p.row_bytes, (size_t)p.row_bytes);
-            });
-    }
+    frames_to_host(h, n, fh, fw, h->cfg.batch, out_format, out_layout, out, [&](int i, int na, const YuvGeom& dg, uint8_t* d_dst) {
+        annotate_device(h, (const uint8_t*)d_bgr + (size_t)i * fh * fw * 3, na, dp, dof + i, dg, d_dst);
+    });
 }
 
 int eagle_annotate_frames(EagleHandle* h, const void* d_bgr, int n, const EagleFrameResult* recs, const int32_t* team_ids, const int32_t* team_vals, int n_team,

@@ -1,0 +1,513 @@
+// K21 — the minimap: rows of a processed table resident in HBM (post.hip) -> top-down pictures of the pitch, written as BGR, NV12 or I420 in the layout a
+// video encoder takes: the camera's footprint, the players in team colours, the ball and, on request, the Voronoi areas of the players (what the
+// reference's examples/minimap.py and examples/voronoi.py plot through matplotlib).  tests/minimap_ref.py is the written definition of every output byte
+// (own rasterisation; one float64 quantisation to 1/16 pixel, integer arithmetic after it).
+//
+// Two launches per call, no host round trip for the data:
+//   minimap_sites_kernel  one thread per table row walks the drawable pitch columns (the host decides per COLUMN what is drawn and in which colour: the
+//                         team lookup does not depend on the row) and writes the row's compacted draw list in drawing order (discs in column order, then the
+//                         balls): quantised position + colour / kind / is-a-Voronoi-site, 16 bytes per entry, behind a header of the entry count and the four
+//                         quantised footprint corners.  The table is [column][row][2]: a wave's loads are contiguous along rows.  Its stores are not:
+//                         each thread writes its own row's list, `stride` x 16 bytes from its neighbour's (16 B per lane and instruction, uncoalesced).  Against
+//                         the draw pass this is nothing at tens of columns; a table of thousands of columns would want the list transposed.
+//   minimap_kernel        annotate_kernel's shape: a workgroup owns an AN_TH x AN_TW tile of one picture, a thread a 2-row strip of AN_STRIP pixels in
+//                         registers; the row's list goes through LDS in chunks of MM_CHUNK entries (any length is exact), once for the Voronoi labelling
+//                         (every site counts for every pixel) and once for the discs and rings (culled against the tile by bounding box, list order kept);
+//                         the markings are a bit mask built once per (scale, margin) by markings_mask below; the strip leaves through pix_out.h's writer.
+// Voronoi without 64-bit multiplies per pixel: (16X - qx)^2 + (16Y - qy)^2 = 256 (X^2 + Y^2) + [qx^2 + qy^2 - 32 X qx - 32 Y qy]; the first term is the
+// same for every site, so the sites are compared by the bracket: its constant is formed once per staged entry, the Y term once per strip row, and along a
+// row it changes by the 32-bit amount 32 qx per pixel.  Exact: |q| < 2^20 and 32 X < 2^17 keep everything below 2^42.
+#include "runtime.h"
+#include "pix_out.h"
+
+namespace eagle {
+
+static constexpr int MM_CHUNK = AN_THREADS;            // list entries staged per trip: one per thread
+static constexpr int MM_HEAD = 3;                      // header slots of a row's list: {count, footprint ok}, {BL, TL}, {TR, BR}
+static constexpr int MM_KIND_SHIFT = 24, MM_SITE_BIT = 1 << 28;
+static constexpr int MM_TINT_A = 51, MM_FOOT_A = 77;
+static constexpr double MM_DOMAIN = 1024.0, MM_CIRCLE_R = 9.15;
+static constexpr uint32_t MM_WHITE = 0xffffffu, MM_NONE = 0xffffffffu;
+
+struct MmCol { int32_t col; uint32_t kc; };            // a drawable table column: B | G << 8 | R << 16 | kind << 24 | site << 28
+
+struct MinimapArgs {
+    AnnotArgs out;               // (src, prims, offs unused)
+    const double2* values;       // the table, [column][row]
+    const MmCol* cols;           // drawable columns in drawing order
+    int4* lists;                 // [n][stride]
+    const uint8_t* mask;         // markings: bit (x & 7) of byte y * mask_pitch + (x >> 3)
+    int rows, row0, n, ncols, stride, mask_pitch;
+    int corner[4];               // table columns of Bottom_Left, Top_Left, Top_Right, Bottom_Right (-1: none)
+    int scale, margin, voronoi, footprint;
+    int r16, rb16, rbi16;        // 16 x the disc radius, the ring's outer and inner radius
+};
+
+__device__ __forceinline__ bool mm_quantise(double2 v, double K, int ox, int oy, int& qx, int& qy)
+{
+    if (!(fabs(v.x) <= MM_DOMAIN) || !(fabs(v.y) <= MM_DOMAIN)) return false;          // NaN, +-inf and the far field
+    qx = ox + (int)floor(v.x * K + 0.5);
+    qy = oy - (int)floor(v.y * K + 0.5);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void minimap_sites_kernel(MinimapArgs m)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m.n) return;
+    const size_t row = (size_t)(m.row0 + i);
+    const double K = (double)(16 * m.scale);
+    const int ox = 16 * m.margin, oy = 16 * m.margin + 16 * 68 * m.scale;
+    int4* L = m.lists + (size_t)i * m.stride;
+    int cnt = 0;
+    for (int c = 0; c < m.ncols; ++c) {
+        const MmCol d = m.cols[c];
+        int qx, qy;
+        if (!mm_quantise(m.values[(size_t)d.col * m.rows + row], K, ox, oy, qx, qy)) continue;
+        L[MM_HEAD + cnt++] = make_int4(qx, qy, (int)d.kc, 0);
+    }
+    int q[8];
+    bool ok = true;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        q[2 * k] = q[2 * k + 1] = 0;
+        ok = ok && m.corner[k] >= 0 && mm_quantise(m.values[(size_t)max(m.corner[k], 0) * m.rows + row], K, ox, oy, q[2 * k], q[2 * k + 1]);
+    }
+    L[0] = make_int4(cnt, ok ? 1 : 0, 0, 0);
+    L[1] = make_int4(q[0], q[1], q[2], q[3]);
+    L[2] = make_int4(q[4], q[5], q[6], q[7]);
+}
+
+__device__ __forceinline__ uint32_t mm_blend(uint32_t bg, uint32_t c, int a)
+{
+    uint32_t o = 0;
+    #pragma unroll
+    for (int s = 0; s < 24; s += 8) o |= ((((c >> s) & 255u) * a + ((bg >> s) & 255u) * (256 - a) + 128u) >> 8) << s;
+    return o;
+}
+
+// the pixels of the strip at (x0, y0) a triangle covers (bit r * AN_STRIP + k): annot_ref's inclusive TRI rule on 1/16 px vertices at the pixel centres.
+// The edge functions are affine: evaluated once in 64 bits at the strip's origin, stepped by additions
+__device__ __forceinline__ uint32_t mm_tri_strip(int ax, int ay, int bx, int by, int cx, int cy, int x0, int y0)
+{
+    const int lx = min(ax, min(bx, cx)), hx = max(ax, max(bx, cx)), ly = min(ay, min(by, cy)), hy = max(ay, max(by, cy));
+    const int X = 16 * x0, Y = 16 * y0;
+    if (X + 16 * (AN_STRIP - 1) < lx || X > hx || Y + 16 < ly || Y > hy) return 0;
+    const long long sg = (long long)(bx - ax) * (cy - ay) - (long long)(by - ay) * (cx - ax) < 0 ? -1 : 1;
+    const int vx[3] = {ax, bx, cx}, vy[3] = {ay, by, cy};
+    long long e[3], sx[3], sy[3];
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int ux = vx[(k + 1) % 3] - vx[k], uy = vy[(k + 1) % 3] - vy[k];
+        e[k] = sg * ((long long)ux * (Y - vy[k]) - (long long)uy * (X - vx[k]));
+        sx[k] = -sg * 16 * (long long)uy;
+        sy[k] = sg * 16 * (long long)ux;
+    }
+    uint32_t bits = 0;
+    #pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (Y + 16 * r < ly || Y + 16 * r > hy) continue;
+        #pragma unroll
+        for (int k = 0; k < AN_STRIP; ++k) {
+            const int px = X + 16 * k;
+            if (px >= lx && px <= hx && e[0] + r * sy[0] + k * sx[0] >= 0 && e[1] + r * sy[1] + k * sx[1] >= 0 && e[2] + r * sy[2] + k * sx[2] >= 0)
+                bits |= 1u << (r * AN_STRIP + k);
+        }
+    }
+    return bits;
+}
+
+__global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m)
+{
+    __shared__ int4 s_e[MM_CHUNK];
+    __shared__ long long s_n[MM_CHUNK];
+    const AnnotArgs& a = m.out;
+    const int tiles_x = (a.w + AN_TW - 1) / AN_TW;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x, f = blockIdx.y;
+    const int tx0 = tx * AN_TW, ty0 = ty * AN_TH, tx1 = min(tx0 + AN_TW, a.w) - 1, ty1 = min(ty0 + AN_TH, a.h) - 1;
+    const int4* L = m.lists + (size_t)f * m.stride;
+    const int4 head = L[0];
+    const int count = head.x, tid = threadIdx.x;
+    const int sx = tid % AN_SX, sy = tid / AN_SX;
+    const int x0 = tx0 + sx * AN_STRIP, y0 = ty0 + 2 * sy;
+    const bool live = x0 < a.w && y0 < a.h;            // (no early return: the workgroup meets at the barriers of the staging loops)
+    const int cnt = min(AN_STRIP, a.w - x0), rows = min(2, a.h - y0);
+    uint32_t px[2][AN_STRIP];
+    #pragma unroll
+    for (int r = 0; r < 2; ++r)
+        #pragma unroll
+        for (int k = 0; k < AN_STRIP; ++k) px[r][k] = 0;
+
+    // ---- 2. Voronoi tint: every site of the row against every pixel of the pitch rectangle ----
+    const int px_lo = m.margin, px_hi = m.margin + 105 * m.scale, py_lo = m.margin, py_hi = m.margin + 68 * m.scale;      // [lo, hi)
+    if (m.voronoi && tx0 < px_hi && tx1 >= px_lo && ty0 < py_hi && ty1 >= py_lo) {      // (uniform)
+        long long best[2][AN_STRIP];
+        uint32_t who[2][AN_STRIP];
+        #pragma unroll
+        for (int r = 0; r < 2; ++r)
+            #pragma unroll
+            for (int k = 0; k < AN_STRIP; ++k) { best[r][k] = 0x7fffffffffffffffLL; who[r][k] = MM_NONE; }
+        for (int base = 0; base < count; base += MM_CHUNK) {
+            const int nc = min(MM_CHUNK, count - base);
+            __syncthreads();                           // the previous chunk has been consumed
+            if (tid < nc) {
+                const int4 e = L[MM_HEAD + base + tid];
+                s_e[tid] = e;
+                s_n[tid] = (long long)e.x * e.x + (long long)e.y * e.y;
+            }
+            __syncthreads();
+            if (!live) continue;
+            for (int j = 0; j < nc; ++j) {
+                const int4 e = s_e[j];                 // (one address for the whole wave: an LDS broadcast)
+                if (!(e.z & MM_SITE_BIT)) continue;
+                const long long kx = s_n[j] - (long long)(32 * x0) * e.x;
+                const int step = 32 * e.x;
+                #pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const long long kr = kx - (long long)(32 * (y0 + r)) * e.y;
+                    #pragma unroll
+                    for (int k = 0; k < AN_STRIP; ++k) {
+                        const long long key = kr - (long long)(k * step);
+                        if (key < best[r][k]) { best[r][k] = key; who[r][k] = (uint32_t)e.z & MM_WHITE; }       // (strict: a tie stays with the earlier column)
+                    }
+                }
+            }
+        }
+        #pragma unroll
+        for (int r = 0; r < 2; ++r)
+            #pragma unroll
+            for (int k = 0; k < AN_STRIP; ++k)
+                if (who[r][k] != MM_NONE && x0 + k >= px_lo && x0 + k < px_hi && y0 + r >= py_lo && y0 + r < py_hi) px[r][k] = mm_blend(px[r][k], who[r][k], MM_TINT_A);
+    }
+
+    // ---- 3. the camera's footprint ----
+    if (m.footprint && head.y && live) {
+        const int4 c0 = L[1], c1 = L[2];               // BL, TL | TR, BR
+        const uint32_t bits = mm_tri_strip(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, x0, y0) | mm_tri_strip(c0.x, c0.y, c1.x, c1.y, c1.z, c1.w, x0, y0);
+        if (bits) {
+            #pragma unroll
+            for (int r = 0; r < 2; ++r)
+                #pragma unroll
+                for (int k = 0; k < AN_STRIP; ++k)
+                    if (bits >> (r * AN_STRIP + k) & 1) px[r][k] = mm_blend(px[r][k], MM_WHITE, MM_FOOT_A);
+        }
+    }
+
+    // ---- 4. the markings ----
+    if (live) {
+        #pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r >= rows) continue;
+            const uint32_t b = m.mask[(size_t)(y0 + r) * m.mask_pitch + (x0 >> 3)];
+            #pragma unroll
+            for (int k = 0; k < AN_STRIP; ++k)
+                if (b >> k & 1) px[r][k] = MM_WHITE;
+        }
+    }
+
+    // ---- 5. + 6. discs and ball rings in list order, culled against the tile ----
+    for (int base = 0; base < count; base += MM_CHUNK) {
+        const int nc = min(MM_CHUNK, count - base);
+        __syncthreads();
+        if (tid < nc) {
+            int4 e = L[MM_HEAD + base + tid];
+            const int rr = ((uint32_t)e.z >> MM_KIND_SHIFT & 15) == EAGLE_POST_BALL ? m.rb16 : m.r16;
+            // pixels with |16 X - qx| <= rr: ceil((qx - rr) / 16) .. floor((qx + rr) / 16)
+            e.w = ((e.x - rr + 15) >> 4) <= tx1 && ((e.x + rr) >> 4) >= tx0 && ((e.y - rr + 15) >> 4) <= ty1 && ((e.y + rr) >> 4) >= ty0;
+            s_e[tid] = e;
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int j = 0; j < nc; ++j) {
+            const int4 e = s_e[j];
+            if (!e.w) continue;                        // (uniform)
+            const bool ball = ((uint32_t)e.z >> MM_KIND_SHIFT & 15) == EAGLE_POST_BALL;
+            const int rr = ball ? m.rb16 : m.r16;
+            const int dx0 = 16 * x0 - e.x, dy0 = 16 * y0 - e.y;
+            if (dx0 > rr || dx0 + 16 * (AN_STRIP - 1) < -rr || dy0 > rr || dy0 + 16 < -rr) continue;
+            const int hi = rr * rr, lo = ball ? m.rbi16 * m.rbi16 : -1;
+            const uint32_t color = ball ? MM_WHITE : (uint32_t)e.z & MM_WHITE;
+            #pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int dy = dy0 + 16 * r;
+                #pragma unroll
+                for (int k = 0; k < AN_STRIP; ++k) {
+                    const int dx = dx0 + 16 * k, d2 = dx * dx + dy * dy;      // (|dx|, |dy| <= rr + 112 here: 32 bits hold it)
+                    if (d2 <= hi && d2 > lo) px[r][k] = color;
+                }
+            }
+        }
+    }
+
+    if (live) write_strip(a, f, x0, y0, cnt, rows, px);
+}
+
+// rows row0 .. row0 + n - 1 -> n pictures; the lists buffer holds min(n, MM_PASS) rows and is reused pass by pass (same stream: ordered)
+static constexpr int MM_PASS = 65535;                  // gridDim.y limit
+static constexpr int64_t MM_STAGING = (int64_t)32 << 20;      // eagle_minimap_frames: device + pinned staging per pass (21 BGR pictures at 8 px per metre; a pass
+                                                              // of that size moves for a millisecond or more, against which its two launches and one wait vanish)
+static void minimap_launch(const MinimapArgs& args, hipStream_t s)
+{
+    MinimapArgs m = args;
+    const int tiles = (m.out.w + AN_TW - 1) / AN_TW * ((m.out.h + AN_TH - 1) / AN_TH);
+    for (int f0 = 0; f0 < args.n; f0 += MM_PASS) {
+        m.n = std::min(args.n - f0, MM_PASS);
+        m.row0 = args.row0 + f0;
+        m.out.dst = args.out.dst + (int64_t)f0 * args.out.frame_stride;
+        hipLaunchKernelGGL(minimap_sites_kernel, dim3((m.n + 255) / 256), dim3(256), 0, s, m);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(minimap_kernel, dim3(tiles, m.n), dim3(AN_THREADS), 0, s, m);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------------
+struct MmPlan { int S, M, w, h, r, rb, t; };
+
+static MmPlan minimap_plan(const EagleMinimapParams* p)
+{
+    if (!p) fail(EAGLE_E_INVALID, "minimap: params is NULL");
+    if (p->scale < 2 || p->scale > 32 || (p->scale & 1)) fail(EAGLE_E_INVALID, "minimap: scale %d must be even and within 2 .. 32 pixels per metre", p->scale);
+    if (p->margin < 0 || p->margin > 64 || (p->margin & 1)) fail(EAGLE_E_INVALID, "minimap: margin %d must be even and within 0 .. 64 pixels", p->margin);
+    if (p->player_radius < 0 || p->player_radius > 4 * p->scale || p->ball_radius < 0 || p->ball_radius > 4 * p->scale)
+        fail(EAGLE_E_INVALID, "minimap: radii %d / %d must lie within 0 .. 4 x scale = %d (0: the default)", p->player_radius, p->ball_radius, 4 * p->scale);
+    MmPlan pl;
+    pl.S = p->scale; pl.M = p->margin;
+    pl.w = 105 * pl.S + 2 * pl.M; pl.h = 68 * pl.S + 2 * pl.M;
+    pl.r = p->player_radius ? p->player_radius : std::max(2, pl.S);
+    pl.rb = p->ball_radius ? p->ball_radius : std::max(3, pl.S / 2 + 1);
+    pl.t = std::max(1, pl.rb / 3);
+    return pl;
+}
+
+// the white pitch markings of a (scale, margin) as a bit mask, rows of (w + 7) / 8 bytes: tests/minimap_ref.py::markings, dimension by dimension
+static std::vector<uint8_t> markings_mask(const MmPlan& pl, int* pitch)
+{
+    const int S = pl.S, M = pl.M, w = pl.w, h = pl.h, hw = std::max(1, S / 4), mp = (w + 7) / 8;
+    std::vector<uint8_t> bits((size_t)mp * h, 0);
+    const double K = (double)(16 * S);
+    auto u = [&](double d) { return (int)std::floor(d * K + 0.5); };
+    auto qx = [&](double x) { return 16 * M + u(x); };
+    auto qy = [&](double y) { return 16 * M + 16 * 68 * S - u(y); };
+    auto P = [](int q) { return (q + 8) >> 4; };
+    auto set = [&](int x, int y) { bits[(size_t)y * mp + (x >> 3)] |= (uint8_t)(1u << (x & 7)); };
+    auto rect = [&](int xa, int xb, int ya, int yb) {
+        const int x0 = std::max(std::min(xa, xb) - hw, 0), x1 = std::min(std::max(xa, xb) + hw, w - 1), y0 = std::max(std::min(ya, yb) - hw, 0), y1 = std::min(std::max(ya, yb) + hw, h - 1);
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0; x <= x1; ++x) set(x, y);
+    };
+    auto vline = [&](double x, double ya, double yb) { rect(P(qx(x)), P(qx(x)), P(qy(ya)), P(qy(yb))); };
+    auto hline = [&](double y, double xa, double xb) { rect(P(qx(xa)), P(qx(xb)), P(qy(y)), P(qy(y))); };
+    const double PW = 105.0, PH = 68.0, MIDX = 52.5, MIDY = 34.0, PMX = 11.0;
+    const double box[2][3] = {{16.5, 13.84, 54.16}, {5.5, 24.84, 43.16}};          // pitch.py: penalty area, goal area (depth, y0, y1)
+    vline(0.0, 0.0, PH); vline(MIDX, 0.0, PH); vline(PW, 0.0, PH);
+    hline(0.0, 0.0, PW); hline(PH, 0.0, PW);
+    for (const auto& b : box) {
+        vline(b[0], b[1], b[2]); vline(PW - b[0], b[1], b[2]);
+        for (int k = 1; k <= 2; ++k) { hline(b[k], 0.0, b[0]); hline(b[k], PW - b[0], PW); }
+    }
+    const long long R = u(MM_CIRCLE_R), t = 16 * hw;
+    // side: 0 whole ring, +1 only 16 X > lim, -1 only 16 X < lim; r_out < 0: the disc of radius -r_out
+    auto round_shape = [&](double cxm, double cym, long long r_in, long long r_out, int side, int lim) {
+        const long long cx = qx(cxm), cy = qy(cym);
+        const int x0 = std::max((int)((cx - r_out) >> 4) - 1, 0), x1 = std::min((int)((cx + r_out) >> 4) + 1, w - 1);
+        const int y0 = std::max((int)((cy - r_out) >> 4) - 1, 0), y1 = std::min((int)((cy + r_out) >> 4) + 1, h - 1);
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0; x <= x1; ++x) {
+                const long long dx = 16LL * x - cx, dy = 16LL * y - cy, d = dx * dx + dy * dy;
+                if (d > r_out * r_out || (r_in >= 0 && d < r_in * r_in)) continue;
+                if ((side > 0 && !(16 * x > lim)) || (side < 0 && !(16 * x < lim))) continue;
+                set(x, y);
+            }
+    };
+    round_shape(MIDX, MIDY, R - t, R + t, 0, 0);
+    round_shape(PMX, MIDY, R - t, R + t, 1, qx(box[0][0]));
+    round_shape(PW - PMX, MIDY, R - t, R + t, -1, qx(PW - box[0][0]));
+    for (double cx : {MIDX, PMX, PW - PMX}) round_shape(cx, MIDY, -1, 2 * t, 0, 0);
+    *pitch = mp;
+    return bits;
+}
+
+// which table columns are drawn, in drawing order, and the four corner columns: eagle_overlay_from_table's walk on the pitch columns
+static void minimap_columns(const EaglePostColumn* columns, int ncols, bool has_team, const int32_t* team_ids, const int32_t* team_vals, size_t n_team,
+                            std::vector<MmCol>& out, int corner[4])
+{
+    const uint32_t green = 0x00ff00u, red = 0xff0000u, blue = 0x0000ffu;      // B | G << 8 | R << 16
+    for (int k = 0; k < 4; ++k) corner[k] = -1;
+    std::vector<MmCol> balls;
+    for (int c = 0; c < ncols; ++c) {
+        const EaglePostColumn& col = columns[c];
+        if (col.video) continue;
+        if (col.kind == EAGLE_POST_BOUNDARY) {
+            if (col.id >= 0 && col.id < 4 && corner[col.id] < 0) corner[col.id] = c;
+            continue;
+        }
+        if (col.kind == EAGLE_POST_BALL) { balls.push_back(MmCol{c, MM_WHITE | (uint32_t)EAGLE_POST_BALL << MM_KIND_SHIFT}); continue; }
+        if (col.kind != EAGLE_POST_PLAYER && col.kind != EAGLE_POST_GOALKEEPER) fail(EAGLE_E_INVALID, "minimap: column %d has unknown kind %d", c, col.kind);
+        uint32_t color = green, site = 0;
+        if (col.kind == EAGLE_POST_PLAYER) {
+            site = MM_SITE_BIT;
+            if (!has_team) color = MM_WHITE;
+            else {
+                size_t k = 0;
+                while (k < n_team && team_ids[k] != col.id) ++k;
+                if (k == n_team) continue;
+                color = team_vals[k] == 0 ? red : blue;
+            }
+        }
+        out.push_back(MmCol{c, color | (uint32_t)col.kind << MM_KIND_SHIFT | site});
+    }
+    out.insert(out.end(), balls.begin(), balls.end());
+}
+
+static void minimap_window(int rows, int row0, int n)
+{
+    if (n < 0) fail(EAGLE_E_INVALID, "minimap: n = %d is negative", n);
+    if (n > 0 && rows == 0) fail(EAGLE_E_INVALID, "minimap: the table has no rows");
+    if (row0 < 0 || row0 > rows || n > rows - row0) fail(EAGLE_E_INVALID, "minimap: rows %d .. %d lie outside the table's %d rows", row0, row0 + n - 1, rows);
+}
+
+// everything of a call's kernel arguments that does not depend on the output buffer
+static MinimapArgs minimap_args(const MmPlan& pl, const EagleMinimapParams* p)
+{
+    MinimapArgs m{};
+    m.scale = pl.S; m.margin = pl.M; m.voronoi = p->voronoi != 0; m.footprint = p->footprint != 0;
+    m.r16 = 16 * pl.r; m.rb16 = 16 * pl.rb; m.rbi16 = 16 * (pl.rb - pl.t);
+    m.mask_pitch = (pl.w + 7) / 8;
+    return m;
+}
+
+static void grow(void** buf, size_t* cap, size_t need)
+{
+    if (need <= *cap) return;
+    if (*buf) HIP_CHECK(hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    HIP_CHECK(hipMalloc(buf, need));
+    *cap = need;
+}
+
+// bytes a call writes (the pictures) and reads (the pitch cells of its rows)
+static double minimap_bytes(const MinimapArgs& m, const YuvGeom& g) { return (double)m.n * ((double)g.dense_bytes + 16.0 * (m.ncols + 4)); }
+
+// Once per call of a handle entry: which columns are drawn (uploaded), the corner columns, the marking mask of this (scale, margin), and list space for
+// passes of up to max_pass rows.  The result lacks only the rows and the output of a pass (minimap_pass)
+static MinimapArgs minimap_prepare(EagleHandle* h, EaglePostTable* t, const MmPlan& pl, const EagleMinimapParams* p, int max_pass)
+{
+    std::vector<MmCol> cols;
+    MinimapArgs m = minimap_args(pl, p);
+    minimap_columns(t->columns.data(), t->cols, t->has_team, t->team_ids.data(), t->team_vals.data(), t->team_ids.size(), cols, m.corner);
+    m.values = (const double2*)t->d_values; m.rows = t->rows; m.ncols = (int)cols.size(); m.stride = MM_HEAD + m.ncols;
+    grow(&h->mm_list, &h->mm_list_cap, (size_t)std::min(max_pass, MM_PASS) * m.stride * sizeof(int4));
+    grow(&h->mm_cols, &h->mm_cols_cap, std::max<size_t>(cols.size() * sizeof(MmCol), 16));
+    if (h->mm_mask_scale != pl.S || h->mm_mask_margin != pl.M) {
+        int mp = 0;
+        const std::vector<uint8_t> bits = markings_mask(pl, &mp);
+        grow((void**)&h->mm_mask, &h->mm_mask_cap, bits.size());
+        h->mm_mask_scale = 0;
+        HIP_CHECK(hipMemcpyAsync(h->mm_mask, bits.data(), bits.size(), hipMemcpyHostToDevice, h->s_main));
+        HIP_CHECK(hipStreamSynchronize(h->s_main));        // (a pageable source: it has left the vector before the vector goes)
+        h->mm_mask_scale = pl.S; h->mm_mask_margin = pl.M;
+    }
+    if (!cols.empty()) HIP_CHECK(hipMemcpyAsync(h->mm_cols, cols.data(), cols.size() * sizeof(MmCol), hipMemcpyHostToDevice, h->s_main));
+    HIP_CHECK(hipStreamSynchronize(h->s_main));            // (pageable sources: they have left the vectors)
+    m.lists = (int4*)h->mm_list; m.cols = (const MmCol*)h->mm_cols; m.mask = h->mm_mask;
+    return m;
+}
+
+// rows row0 .. row0 + n - 1 -> n pictures at d_out (layout g) on s_main; returns when they are complete
+static void minimap_pass(EagleHandle* h, const MinimapArgs& prepared, int row0, int n, const YuvGeom& g, uint8_t* d_out)
+{
+    MinimapArgs m = prepared;
+    m.out = annot_args(g, nullptr, d_out, nullptr, nullptr);
+    m.row0 = row0; m.n = n;
+    timed_launch(h, "minimap", minimap_bytes(m, g), h->s_main, [&] { minimap_launch(m, h->s_main); });
+    HIP_CHECK(hipStreamSynchronize(h->s_main));
+    if (h->prof) collect_spans(h);
+}
+
+static MmPlan minimap_begin(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleMinimapParams* p, const void* out)
+{
+    if (!t || !out) fail(EAGLE_E_INVALID, "minimap: bad argument (table %p, out %p)", (const void*)t, out);
+    if (t->h != h) fail(EAGLE_E_INVALID, "minimap: the table belongs to another handle");
+    const MmPlan pl = minimap_plan(p);
+    if (p->voronoi && !t->has_team) fail(EAGLE_E_INVALID, "minimap: voronoi needs a table with a team mapping (the areas are coloured by team)");
+    minimap_window(t->rows, row0, n);
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    return pl;
+}
+
+}  // namespace eagle
+
+extern "C" {
+
+int eagle_minimap_size(const EagleMinimapParams* p, int* w, int* h)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!w || !h) fail(EAGLE_E_INVALID, "eagle_minimap_size: w or h is NULL");
+    const MmPlan pl = minimap_plan(p);
+    *w = pl.w; *h = pl.h;
+    API_END(hh)
+}
+
+int eagle_minimap_device_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleMinimapParams* p, int out_format, const EagleYuvLayout* out_layout, void* d_out)
+{
+    API_BEGIN_H(h)
+    const MmPlan pl = minimap_begin(h, t, row0, n, p, d_out);
+    const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
+    if (n == 0) return EAGLE_OK;
+    minimap_pass(h, minimap_prepare(h, t, pl, p, n), row0, n, g, (uint8_t*)d_out);
+    API_END(h)
+}
+
+int eagle_minimap_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleMinimapParams* p, int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    API_BEGIN_H(h)
+    const MmPlan pl = minimap_begin(h, t, row0, n, p, out);
+    const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
+    if (n == 0) return EAGLE_OK;
+    // pictures per pass: what MM_STAGING bytes of staging hold (the handle's batch is about 720p frames through two networks, not about these pictures)
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n, MM_STAGING / g.dense_bytes));
+    const MinimapArgs m = minimap_prepare(h, t, pl, p, batch);
+    frames_to_host(h, n, pl.h, pl.w, batch, out_format, out_layout, out,
+                   [&](int i, int na, const YuvGeom& dg, uint8_t* d_dst) { minimap_pass(h, m, row0 + i, na, dg, d_dst); });
+    API_END(h)
+}
+
+int eagle_op_minimap(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
+                     const EagleMinimapParams* p, int row0, int n, int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!values || !columns || !out || rows < 0 || cols < 0 || n_team < 0 || (team_ids && n_team > 0 && !team_vals))
+        fail(EAGLE_E_INVALID, "eagle_op_minimap: bad argument (values %p, columns %p, out %p, %d rows, %d columns, %d teams)", (const void*)values, (const void*)columns,
+             (const void*)out, rows, cols, n_team);
+    const MmPlan pl = minimap_plan(p);
+    if (p->voronoi && !team_ids) fail(EAGLE_E_INVALID, "minimap: voronoi needs a table with a team mapping (the areas are coloured by team)");
+    minimap_window(rows, row0, n);
+    const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
+    std::vector<MmCol> dc;
+    MinimapArgs m = minimap_args(pl, p);
+    minimap_columns(columns, cols, team_ids != nullptr, team_ids, team_vals, (size_t)n_team, dc, m.corner);
+    m.ncols = (int)dc.size();
+    if (n == 0) return EAGLE_OK;
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const size_t span = (size_t)((n - 1) * g.frame_stride + g.extent);
+    int mp = 0;
+    const std::vector<uint8_t> bits = markings_mask(pl, &mp);
+    uint8_t* d_out = (uint8_t*)net.upload(out, span);                        // bytes the layout does not cover come back as they were
+    m.out = annot_args(g, nullptr, d_out, nullptr, nullptr);                 // (alignment is judged on the pointer that is written)
+    m.values = (const double2*)net.upload(values, (size_t)cols * rows * 2 * sizeof(double));
+    dc.resize(std::max<size_t>(dc.size(), 2), MmCol{0, 0});                  // (a table without a drawable column still uploads 16 bytes; ncols says how many count)
+    m.cols = (const MmCol*)net.upload(dc.data(), dc.size() * sizeof(MmCol));
+    m.mask = (const uint8_t*)net.upload(bits.data(), bits.size());
+    m.rows = rows; m.row0 = row0; m.n = n; m.stride = MM_HEAD + m.ncols;
+    m.lists = (int4*)net.get((size_t)std::min(n, MM_PASS) * m.stride * sizeof(int4));
+    minimap_launch(m, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, d_out, span, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
+}  // extern "C"

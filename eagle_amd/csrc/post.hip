@@ -11,18 +11,6 @@
 #include "runtime.h"
 #include <climits>
 
-struct EaglePostTable {
-    EagleHandle* h = nullptr;
-    int rows = 0, cols = 0, flags = 0;
-    std::vector<int32_t> frames;
-    std::vector<EaglePostColumn> columns;
-    std::vector<int32_t> team_ids, team_vals;
-    bool has_team = false;
-    double* d_values = nullptr;          // [cols][rows][2], resident until eagle_post_free
-    std::vector<double> host;            // the same on the host, fetched on first use (getters, overlays)
-    bool host_ok = false;
-};
-
 namespace eagle {
 
 static constexpr int PS_THREADS = 256, PS_WAVES = PS_THREADS / 64, SC_ROWS = 1024;

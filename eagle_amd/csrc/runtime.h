@@ -255,6 +255,23 @@ struct EagleHandle {
     void* annot_prims = nullptr; size_t annot_prims_cap = 0;
     uint8_t* annot_out = nullptr; size_t annot_out_cap = 0;
     uint8_t* annot_ring = nullptr; size_t annot_ring_cap = 0;
+    // minimap (minimap.hip): the draw lists of the call being run, the drawable columns and the marking mask of the last (scale, margin); grown on demand
+    void* mm_list = nullptr; size_t mm_list_cap = 0;
+    void* mm_cols = nullptr; size_t mm_cols_cap = 0;
+    uint8_t* mm_mask = nullptr; size_t mm_mask_cap = 0; int mm_mask_scale = 0, mm_mask_margin = -1;
+};
+
+// A processed clip table (post.hip builds it; minimap.hip draws it)
+struct EaglePostTable {
+    EagleHandle* h = nullptr;
+    int rows = 0, cols = 0, flags = 0;
+    std::vector<int32_t> frames;
+    std::vector<EaglePostColumn> columns;
+    std::vector<int32_t> team_ids, team_vals;
+    bool has_team = false;
+    double* d_values = nullptr;          // [cols][rows][2], resident until eagle_post_free
+    std::vector<double> host;            // the same on the host, fetched on first use (getters, overlays)
+    bool host_ok = false;
 };
 
 namespace eagle {
@@ -280,6 +297,12 @@ struct YuvGeom {
 // The one argument check of every entry that takes an EagleYuvLayout: fills the dense defaults and rejects what a kernel cannot read or write safely.
 YuvGeom yuv_geometry(int fmt, int h, int w, const EagleYuvLayout* L, bool output = false);      // output: EAGLE_PIX_BGR is a format too
 bool host_pinned(EagleHandle* h, const void* p);
+// annotate.hip: the kernel's view of an output layout the one check (yuv_geometry) has resolved
+AnnotArgs annot_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst, const EaglePrim* prims, const int32_t* offs);
+// n pictures of fh x fw -> host memory in the caller's layout: draw(first, count, dense geometry, d_dst) renders `count` (<= batch) of them into the handle's
+// device staging and returns when they are complete; a pinned destination is DMA'd, a pageable one goes through the handle's pinned ring
+void frames_to_host(EagleHandle* h, int n, int fh, int fw, int batch, int out_format, const EagleYuvLayout* out_layout, uint8_t* out,
+                    const std::function<void(int, int, const YuvGeom&, uint8_t*)>& draw);
 void clip_close(EagleHandle* h);                                                // clip.hip
 }  // namespace eagle
 

@@ -162,6 +162,9 @@ void eagle_destroy(EagleHandle* h)
     if (h->annot_prims) (void)hipFree(h->annot_prims);
     if (h->annot_out) (void)hipFree(h->annot_out);
     if (h->annot_ring) (void)hipHostFree(h->annot_ring);
+    if (h->mm_list) (void)hipFree(h->mm_list);
+    if (h->mm_cols) (void)hipFree(h->mm_cols);
+    if (h->mm_mask) (void)hipFree(h->mm_mask);
     if (h->reid_crops_h) (void)hipHostFree(h->reid_crops_h);
     if (h->reid_feats_h) (void)hipHostFree(h->reid_feats_h);
     if (h->clip_sat_h) (void)hipHostFree(h->clip_sat_h);

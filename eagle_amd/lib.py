@@ -68,6 +68,12 @@ class EaglePostParams(C.Structure):
                 ("team_vals", C.c_void_p), ("n_team", C.c_int32), ("reserved", C.c_int32), ("max_bytes", C.c_int64)]
 
 
+class EagleMinimapParams(C.Structure):
+    """include/eagle.h EagleMinimapParams: pixels per metre, margin, the two optional layers, radii in pixels (0 = the default)."""
+    _fields_ = [("scale", C.c_int32), ("margin", C.c_int32), ("voronoi", C.c_int32), ("footprint", C.c_int32), ("player_radius", C.c_int32),
+                ("ball_radius", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 POST_PLAYER, POST_GOALKEEPER, POST_BALL, POST_BOUNDARY = 0, 1, 2, 3    # include/eagle.h EAGLE_POST_*
 POST_NO_BALL = 1                                                       # ... flag: fewer than two ball sightings
 POSTCOL_DTYPE = np.dtype([("kind", "<i4"), ("id", "<i4"), ("video", "<i4"), ("reserved", "<i4")])      # EaglePostColumn
@@ -190,6 +196,11 @@ def load():
     L.eagle_post_values.argtypes = [vp, vp]
     L.eagle_post_device_values.argtypes = [vp, C.POINTER(vp)]
     L.eagle_overlay_from_table.argtypes = [vp, i32, vp, vp, i32, C.POINTER(i32)]
+    mp = C.POINTER(EagleMinimapParams)
+    L.eagle_minimap_size.argtypes = [mp, C.POINTER(i32), C.POINTER(i32)]
+    L.eagle_minimap_device_frames.argtypes = [vp, vp, i32, i32, mp, i32, yl, vp]
+    L.eagle_minimap_frames.argtypes = [vp, vp, i32, i32, mp, i32, yl, vp]
+    L.eagle_op_minimap.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, mp, i32, i32, i32, yl, vp]
     _lib = L
     return L
 
@@ -203,7 +214,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
            "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate",
            "eagle_annotate_frames_prims", "eagle_postprocess", "eagle_post_free", "eagle_post_shape", "eagle_post_layout", "eagle_post_values",
-           "eagle_post_device_values", "eagle_overlay_from_table"]
+           "eagle_post_device_values", "eagle_overlay_from_table", "eagle_minimap_size", "eagle_minimap_device_frames", "eagle_minimap_frames",
+           "eagle_op_minimap"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -504,6 +516,32 @@ class Handle:
         t = C.c_void_p()
         self._check(self.L.eagle_postprocess(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), C.byref(p), C.byref(t)), "postprocess")
         return PostTable(self, t, team_mapping)
+
+    # --- the minimap (include/eagle.h, eagle_minimap_*) ------------------------------------------------------------
+    def minimap_device(self, table, d_out, params, row0=0, n=None, fmt="bgr", layout=None):
+        """Rows row0 .. row0 + n - 1 of a PostTable of this handle -> n minimap pictures at ``d_out`` (device memory of this handle or an encoder's
+        surface) as "bgr", "nv12" or "i420" in ``layout`` (None = dense).  params: EagleMinimapParams (minimap_params)."""
+        n = len(table.rows) - row0 if n is None else n
+        lay = _yuv_layout(layout)
+        self._check(self.L.eagle_minimap_device_frames(self._h, table._t, int(row0), int(n), C.byref(params), _out_pix(fmt), None if lay is None else C.byref(lay), d_out),
+                    "minimap_device_frames")
+
+    def minimap(self, table, params, row0=0, n=None, fmt="bgr", layout=None, out=None):
+        """As minimap_device, the result in host memory: uint8 [n, h, w, 3] ("bgr") or [n, 3h/2, w] ("nv12" / "i420") with (w, h) = minimap_size(params);
+        with a ``layout`` a flat uint8 buffer of the layout's span (``out``: the caller's buffer; bytes the layout does not cover are left alone)."""
+        n = len(table.rows) - row0 if n is None else n
+        w, h = minimap_size(params)
+        lay = _yuv_layout(layout)
+        need = out_span(fmt, h, w, lay, n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+            if lay is None:
+                out = out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise EagleError(f"minimap: out must be a contiguous uint8 array of at least {need} bytes")
+        self._check(self.L.eagle_minimap_frames(self._h, table._t, int(row0), int(n), C.byref(params), _out_pix(fmt), None if lay is None else C.byref(lay),
+                                                out.ctypes.data_as(C.c_void_p)), "minimap_frames")
+        return out
 
     def reproject(self, recs, Hs, flags):
         """In place: re-project foot points / boundaries of the flagged records with the given homographies (cadence mode)."""
@@ -1018,6 +1056,56 @@ def op_annotate(frames, prims, offsets, fmt="bgr", layout=None, out=None, device
                              _out_pix(fmt), None if lay is None else C.byref(lay), out.ctypes.data_as(C.POINTER(C.c_uint8)))
     if rc:
         raise EagleError(f"eagle_op_annotate failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if lay is None:
+        return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+    return out
+
+
+# --- the minimap ------------------------------------------------------------------------------------------------
+def minimap_params(scale=8, margin=None, voronoi=False, footprint=True, player_radius=0, ball_radius=0):
+    """EagleMinimapParams; margin None: two metres' worth of pixels, at most 64."""
+    if margin is None:
+        margin = min(64, 2 * int(scale))
+    return EagleMinimapParams(int(scale), int(margin), int(bool(voronoi)), int(bool(footprint)), int(player_radius), int(ball_radius))
+
+
+def minimap_size(params):
+    """(w, h) of the pictures these parameters give (include/eagle.h eagle_minimap_size; no GPU involved)."""
+    w, h = C.c_int(0), C.c_int(0)
+    L = load()
+    rc = L.eagle_minimap_size(C.byref(params), C.byref(w), C.byref(h))
+    if rc:
+        raise EagleError(f"eagle_minimap_size failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return w.value, h.value
+
+
+def op_minimap(values, columns, team_mapping, params, row0=0, n=None, fmt="bgr", layout=None, out=None, device=0):
+    """The two minimap launches on a constructed table (include/eagle.h eagle_op_minimap): values float64 [cols][rows][2], columns POSTCOL_DTYPE (or
+    (kind, id, video) tuples), team_mapping {id: team} or None -> the pictures: [n, h, w, 3] / [n, 3h/2, w] when dense, else the flat buffer ``out``
+    (or a zeroed one) written in ``layout``."""
+    L = load()
+    values = np.ascontiguousarray(values, np.float64)
+    cols, rows = values.shape[0], values.shape[1]
+    if not (isinstance(columns, np.ndarray) and columns.dtype == POSTCOL_DTYPE):
+        columns = np.array([(k, i, v, 0) for k, i, v in columns], POSTCOL_DTYPE)
+    columns = np.ascontiguousarray(columns)
+    if len(columns) != cols or values.shape[2:] != (2,):
+        raise EagleError("op_minimap: values must be [cols][rows][2] with one column descriptor per column")
+    ids, vals, nt = _team_arrays(team_mapping)
+    n = rows - row0 if n is None else n
+    w, h = minimap_size(params)
+    lay = _yuv_layout(layout)
+    need = out_span(fmt, h, w, lay, n)
+    if out is None:
+        out = np.zeros(need, np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+        raise EagleError(f"op_minimap: out must be a contiguous uint8 array of at least {need} bytes")
+    keep = np.zeros(4, np.float64)                       # (a table without cells still hands the library a valid pointer)
+    rc = L.eagle_op_minimap(device, (values if values.size else keep).ctypes.data_as(C.c_void_p), (columns if len(columns) else keep).ctypes.data_as(C.c_void_p), rows, cols,
+                            None if ids is None else (ids if len(ids) else keep).ctypes.data_as(C.c_void_p), None if vals is None else (vals if len(vals) else keep).ctypes.data_as(C.c_void_p),
+                            nt, C.byref(params), int(row0), int(n), _out_pix(fmt), None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_minimap failed ({rc}): {L.eagle_last_error(None).decode()}")
     if lay is None:
         return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
     return out

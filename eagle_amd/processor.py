@@ -51,3 +51,8 @@ class Processor:
         """The annotated frames of a clip (the reference's annotated video, main.py:43-81), drawn on the GPU: see CoordinateModel.annotate.
         ``table``: draw the processed table (process_data above) instead of the raw records."""
         return self.model.annotate(frames, coords_or_records, team_mapping, pixel_format, out_format, table=table)
+
+    def minimap(self, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None):
+        """The minimap pictures of a processed table (process_data above), drawn on the GPU: see eagle_amd/minimap.py."""
+        from . import minimap as mm
+        return mm.minimap(self.model.handle, table, scale, margin, voronoi, footprint, pixel_format, rows)

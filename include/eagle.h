@@ -300,6 +300,40 @@ int eagle_post_device_values(const EaglePostTable* t, const double** d_values); 
  * the marker above the interpolated ball, then, with rec != NULL, that record's key-point discs (the three sources of eagle_overlay_from_record). */
 int eagle_overlay_from_table(EaglePostTable* t, int row, const EagleFrameResult* rec, EaglePrim* out, int cap, int* n_out);
 
+/* ---- the minimap: rows of a processed table as top-down pictures of the pitch (the reference's examples/minimap.py and examples/voronoi.py) ------------
+ * Per row: a black canvas of w = 105 scale + 2 margin by h = 68 scale + 2 margin pixels (pitch y up, so the canvas flips it); with `voronoi` the pitch
+ * rectangle tinted by the team colour of the nearest Player column (goalkeepers are not sites; exact integer distances, ties to the earlier column); with
+ * `footprint` the camera's view (the triangles Bottom_Left, Top_Left, Top_Right and Bottom_Left, Top_Right, Bottom_Right of the boundary columns)
+ * blended with white; the pitch markings; a disc per Player / Goalkeeper pitch column in table order in the colours of the annotated video (goalkeepers
+ * green, team 0 red, any other team blue, players without a mapping entry not drawn, white without a mapping); the ball as a white ring, last.
+ * Positions are quantised once to 1/16 pixel in float64; cells that are NaN, infinite or further than 1024 m from the origin are absent, any absent
+ * corner drops the footprint of that row.  The rasterisation is this library's own: tests/minimap_ref.py defines every output byte, the 4:2:0
+ * conversion and the output layouts are those of the annotated output above.  Two launches (minimap.hip) on the handle's main stream read the table
+ * where eagle_postprocess left it; the handle's records, staging buffers and graphs are not involved.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, scale odd or outside 2 .. 32, margin odd or outside 0 .. 64, a radius negative or
+ * above 4 scale, voronoi with a table that has no team mapping, n < 0, a row window outside the table (a table of 0 rows with n > 0), and every layout
+ * error eagle_annotate_* refuses.  n == 0 is success and writes nothing. */
+typedef struct EagleMinimapParams {
+    int32_t scale;                 /* pixels per metre: even, 2 .. 32 */
+    int32_t margin;                /* pixels around the pitch: even, 0 .. 64 */
+    int32_t voronoi, footprint;    /* != 0: draw that layer */
+    int32_t player_radius;         /* pixels, 0 .. 4 scale; 0 = max(2, scale) */
+    int32_t ball_radius;           /* outer radius of the ring, pixels, 0 .. 4 scale; 0 = max(3, scale / 2 + 1); the ring is max(1, radius / 3) thick */
+    int32_t reserved[2];
+} EagleMinimapParams;
+int eagle_minimap_size(const EagleMinimapParams* p, int* w, int* h);
+/* rows row0 .. row0 + n - 1 -> n pictures in HBM (a buffer of the caller: eagle_device_alloc, or an encoder's input surface with its layout); returns when
+ * the output is complete */
+int eagle_minimap_device_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleMinimapParams* p, int out_format, const EagleYuvLayout* out_layout,
+                                void* d_out);
+/* Same, the result copied to host memory (pinned: DMA'd; pageable: through a pinned ring of the handle). */
+int eagle_minimap_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleMinimapParams* p, int out_format, const EagleYuvLayout* out_layout,
+                         uint8_t* out);
+/* Operator entry (host buffers in / out, no handle) for constructed tables: values [cols][rows][2], columns as eagle_post_layout gives them, the team
+ * mapping as two arrays (team_ids NULL: no mapping).  `out` is read first, so bytes the layout does not cover come back as they were. */
+int eagle_op_minimap(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
+                     int n_team, const EagleMinimapParams* p, int row0, int n, int out_format, const EagleYuvLayout* out_layout, uint8_t* out);
+
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
  * flags[i] = 0 keep the record, 1 re-project foot points and boundaries with Hs[9*i..], 2 no homography available yet. */
