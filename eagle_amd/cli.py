@@ -90,9 +90,17 @@ def main(argv=None):
     ap.add_argument("--minimap", action="store_true", help="with --processed: also write <out>/minimap.y4m, the processed table as a top-down video of the pitch")
     ap.add_argument("--minimap-voronoi", action="store_true", help="with --minimap: tint the pitch by the team whose player is nearest")
     ap.add_argument("--minimap-scale", type=int, default=8, help="with --minimap: pixels per metre (even, 2 .. 32)")
+    ap.add_argument("--kinematics", action="store_true", help="with --processed: also write <out>/kinematics.json, per id the distance covered (m) and the top speed (m/s)")
+    ap.add_argument("--minimap-control", action="store_true", help="with --processed: write <out>/minimap.y4m with the pitch-control layer (not together with --minimap-voronoi)")
+    ap.add_argument("--control-grid", type=int, default=None, choices=[1, 2, 4], metavar="R",
+                    help="with --processed: also write <out>/control.npy (uint8 [rows, 68 R, 105 R]) and <out>/control_share.json, team 0's share of the pitch per row")
     a = ap.parse_args(argv)
     if a.minimap and not a.processed:
         ap.error("--minimap draws the processed table: it needs --processed")
+    if (a.kinematics or a.minimap_control or a.control_grid) and not a.processed:
+        ap.error("--kinematics, --minimap-control and --control-grid work on the processed table: they need --processed")
+    if a.minimap_control and a.minimap_voronoi:
+        ap.error("--minimap-control and --minimap-voronoi draw in the same slot: choose one")
 
     from . import synth
     from .coordinate_model import CoordinateModel
@@ -141,9 +149,21 @@ def main(argv=None):
             json.dump(postprocess.json_rows(postprocess.format_data(table)), f)
         if a.annotated:
             write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420", table=table), a.fps)
-        if a.minimap:
+        if a.kinematics or a.minimap_control or a.control_grid:
+            from . import control as ct
+            kin = ct.kinematics(model.handle, table, a.fps)
+            if a.kinematics:
+                with open(os.path.join(a.out, "kinematics.json"), "w") as f:
+                    json.dump({"fps": a.fps, "players": kin["players"]}, f)
+            if a.control_grid:
+                grids, share = ct.control(model.handle, table, a.control_grid)
+                np.save(os.path.join(a.out, "control.npy"), grids)
+                with open(os.path.join(a.out, "control_share.json"), "w") as f:
+                    json.dump({"cells_per_metre": a.control_grid, "frames": [int(r) for r in table.rows], "team0_share": [float(v) for v in share]}, f)
+        if a.minimap or a.minimap_control:
             from .minimap import minimap
-            write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420"), a.fps)
+            write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420",
+                                                                   control=lib.control_params(min(4, a.minimap_scale)) if a.minimap_control else None), a.fps)
         table.close()
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
     elif a.annotated:

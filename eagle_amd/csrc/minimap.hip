@@ -41,6 +41,8 @@ struct MinimapArgs {
     int corner[4];               // table columns of Bottom_Left, Top_Left, Top_Right, Bottom_Right (-1: none)
     int scale, margin, voronoi, footprint;
     int r16, rb16, rbi16;        // 16 x the disc radius, the ring's outer and inner radius
+    const uint8_t* grid;         // control layer: [n][gh][gw] bytes of control.hip for the rows of this launch (nullptr: layer off)
+    int ctl_R, ctl_gw, ctl_gh;   // cells per metre and the grid's size
 };
 
 __device__ __forceinline__ bool mm_quantise(double2 v, double K, int ox, int oy, int& qx, int& qy)
@@ -180,6 +182,26 @@ __global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m)
                 if (who[r][k] != MM_NONE && x0 + k >= px_lo && x0 + k < px_hi && y0 + r >= py_lo && y0 + r < py_hi) px[r][k] = mm_blend(px[r][k], who[r][k], MM_TINT_A);
     }
 
+    // ---- 2'. the pitch-control tint (in Voronoi's slot; never both): the byte of the pixel's cell, read from HBM (neighbouring pixels share cells and lines) ----
+    if (m.grid && live && tx0 < px_hi && tx1 >= px_lo && ty0 < py_hi && ty1 >= py_lo) {
+        const uint8_t* G = m.grid + (size_t)f * m.ctl_gw * m.ctl_gh;
+        #pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int Y = y0 + r;
+            if (Y < py_lo || Y >= py_hi) continue;
+            const uint8_t* Gr = G + (size_t)(m.ctl_gh - 1 - (Y - m.margin) * m.ctl_R / m.scale) * m.ctl_gw;
+            #pragma unroll
+            for (int k = 0; k < AN_STRIP; ++k) {
+                const int X = x0 + k;
+                if (X < px_lo || X >= px_hi) continue;
+                const uint32_t c = Gr[(X - m.margin) * m.ctl_R / m.scale], al = c + (c >> 7);
+                // red a + blue (256 - a): B = (255 (256 - a) + 128) >> 8, G = 128 >> 8 = 0, R = (255 a + 128) >> 8
+                const uint32_t color = ((255u * (256u - al) + 128u) >> 8) | ((255u * al + 128u) >> 8) << 16;
+                px[r][k] = mm_blend(px[r][k], color, MM_TINT_A);
+            }
+        }
+    }
+
     // ---- 3. the camera's footprint ----
     if (m.footprint && head.y && live) {
         const int4 c0 = L[1], c1 = L[2];               // BL, TL | TR, BR
@@ -254,6 +276,7 @@ static void minimap_launch(const MinimapArgs& args, hipStream_t s)
         m.n = std::min(args.n - f0, MM_PASS);
         m.row0 = args.row0 + f0;
         m.out.dst = args.out.dst + (int64_t)f0 * args.out.frame_stride;
+        if (args.grid) m.grid = args.grid + (size_t)f0 * args.ctl_gw * args.ctl_gh;
         hipLaunchKernelGGL(minimap_sites_kernel, dim3((m.n + 255) / 256), dim3(256), 0, s, m);
         HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(minimap_kernel, dim3(tiles, m.n), dim3(AN_THREADS), 0, s, m);
@@ -271,6 +294,7 @@ static MmPlan minimap_plan(const EagleMinimapParams* p)
     if (p->margin < 0 || p->margin > 64 || (p->margin & 1)) fail(EAGLE_E_INVALID, "minimap: margin %d must be even and within 0 .. 64 pixels", p->margin);
     if (p->player_radius < 0 || p->player_radius > 4 * p->scale || p->ball_radius < 0 || p->ball_radius > 4 * p->scale)
         fail(EAGLE_E_INVALID, "minimap: radii %d / %d must lie within 0 .. 4 x scale = %d (0: the default)", p->player_radius, p->ball_radius, 4 * p->scale);
+    if (p->control && p->voronoi) fail(EAGLE_E_INVALID, "minimap: control and voronoi draw in the same slot: choose one");
     MmPlan pl;
     pl.S = p->scale; pl.M = p->margin;
     pl.w = 105 * pl.S + 2 * pl.M; pl.h = 68 * pl.S + 2 * pl.M;
@@ -415,11 +439,12 @@ static MinimapArgs minimap_prepare(EagleHandle* h, EaglePostTable* t, const MmPl
 }
 
 // rows row0 .. row0 + n - 1 -> n pictures at d_out (layout g) on s_main; returns when they are complete
-static void minimap_pass(EagleHandle* h, const MinimapArgs& prepared, int row0, int n, const YuvGeom& g, uint8_t* d_out)
+static void minimap_pass(EagleHandle* h, const MinimapArgs& prepared, int row0, int n, const YuvGeom& g, uint8_t* d_out, const ControlArgs* ctl = nullptr)
 {
     MinimapArgs m = prepared;
     m.out = annot_args(g, nullptr, d_out, nullptr, nullptr);
     m.row0 = row0; m.n = n;
+    if (ctl) control_rows(h, *ctl, row0, n, (uint8_t*)h->ct_grid, nullptr);      // the grids of these rows, on the same stream in front of the draw
     timed_launch(h, "minimap", minimap_bytes(m, g), h->s_main, [&] { minimap_launch(m, h->s_main); });
     HIP_CHECK(hipStreamSynchronize(h->s_main));
     if (h->prof) collect_spans(h);
@@ -431,9 +456,23 @@ static MmPlan minimap_begin(EagleHandle* h, EaglePostTable* t, int row0, int n, 
     if (t->h != h) fail(EAGLE_E_INVALID, "minimap: the table belongs to another handle");
     const MmPlan pl = minimap_plan(p);
     if (p->voronoi && !t->has_team) fail(EAGLE_E_INVALID, "minimap: voronoi needs a table with a team mapping (the areas are coloured by team)");
+    if (p->control) {
+        if (!t->has_team) fail(EAGLE_E_INVALID, "minimap: control needs a table with a team mapping (team 0 is counted against the others)");
+        if (!t->d_vel) fail(EAGLE_E_INVALID, "minimap: control needs the table's velocities (eagle_post_velocities comes first)");
+        if (!t->has_control) fail(EAGLE_E_INVALID, "minimap: control needs its parameters (eagle_minimap_set_control comes first)");
+    }
     minimap_window(t->rows, row0, n);
     HIP_CHECK(hipSetDevice(h->cfg.device));
     return pl;
+}
+
+// the control layer of a handle call: grid space for passes of up to max_pass rows in the handle, the prepared site columns; m learns where the grids are
+static ControlArgs minimap_control(EagleHandle* h, EaglePostTable* t, MinimapArgs& m, int max_pass)
+{
+    const ControlArgs c = control_prepare(h, t, &t->control, max_pass);
+    grow(&h->ct_grid, &h->ct_grid_cap, (size_t)max_pass * c.gw * c.gh);
+    m.grid = (const uint8_t*)h->ct_grid; m.ctl_R = c.R; m.ctl_gw = c.gw; m.ctl_gh = c.gh;
+    return c;
 }
 
 }  // namespace eagle
@@ -456,7 +495,17 @@ int eagle_minimap_device_frames(EagleHandle* h, EaglePostTable* t, int row0, int
     const MmPlan pl = minimap_begin(h, t, row0, n, p, d_out);
     const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
     if (n == 0) return EAGLE_OK;
-    minimap_pass(h, minimap_prepare(h, t, pl, p, n), row0, n, g, (uint8_t*)d_out);
+    if (!p->control) {
+        minimap_pass(h, minimap_prepare(h, t, pl, p, n), row0, n, g, (uint8_t*)d_out);
+        return EAGLE_OK;
+    }
+    // with the control layer the rows go in passes of what MM_STAGING bytes of grids hold (grids, then their draw), so the handle keeps one pass of grids
+    const int64_t cells = (int64_t)7140 * t->control.cells_per_metre * t->control.cells_per_metre;
+    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n, MM_STAGING / cells));
+    MinimapArgs m = minimap_prepare(h, t, pl, p, batch);
+    const ControlArgs ctl = minimap_control(h, t, m, batch);
+    for (int i = 0; i < n; i += batch)
+        minimap_pass(h, m, row0 + i, std::min(batch, n - i), g, (uint8_t*)d_out + (int64_t)i * g.frame_stride, &ctl);
     API_END(h)
 }
 
@@ -468,29 +517,35 @@ int eagle_minimap_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, con
     if (n == 0) return EAGLE_OK;
     // pictures per pass: what MM_STAGING bytes of staging hold (the handle's batch is about 720p frames through two networks, not about these pictures)
     const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(n, MM_STAGING / g.dense_bytes));
-    const MinimapArgs m = minimap_prepare(h, t, pl, p, batch);
+    MinimapArgs m = minimap_prepare(h, t, pl, p, batch);
+    ControlArgs ctl{};
+    if (p->control) ctl = minimap_control(h, t, m, batch);
     frames_to_host(h, n, pl.h, pl.w, batch, out_format, out_layout, out,
-                   [&](int i, int na, const YuvGeom& dg, uint8_t* d_dst) { minimap_pass(h, m, row0 + i, na, dg, d_dst); });
+                   [&](int i, int na, const YuvGeom& dg, uint8_t* d_dst) { minimap_pass(h, m, row0 + i, na, dg, d_dst, p->control ? &ctl : nullptr); });
     API_END(h)
 }
 
-int eagle_op_minimap(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
-                     const EagleMinimapParams* p, int row0, int n, int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
+static void op_minimap(const char* who, int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                       const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleControlParams* cp, int row0, int n, int out_format,
+                       const EagleYuvLayout* out_layout, uint8_t* out)
 {
-    EagleHandle* hh = nullptr;
-    API_BEGIN
     if (!values || !columns || !out || rows < 0 || cols < 0 || n_team < 0 || (team_ids && n_team > 0 && !team_vals))
-        fail(EAGLE_E_INVALID, "eagle_op_minimap: bad argument (values %p, columns %p, out %p, %d rows, %d columns, %d teams)", (const void*)values, (const void*)columns,
+        fail(EAGLE_E_INVALID, "%s: bad argument (values %p, columns %p, out %p, %d rows, %d columns, %d teams)", who, (const void*)values, (const void*)columns,
              (const void*)out, rows, cols, n_team);
     const MmPlan pl = minimap_plan(p);
     if (p->voronoi && !team_ids) fail(EAGLE_E_INVALID, "minimap: voronoi needs a table with a team mapping (the areas are coloured by team)");
+    if (p->control) {
+        if (!team_ids) fail(EAGLE_E_INVALID, "minimap: control needs a table with a team mapping (team 0 is counted against the others)");
+        if (!velocities) fail(EAGLE_E_INVALID, "minimap: control needs velocities (eagle_op_minimap_control takes them)");
+        control_check(cp);
+    }
     minimap_window(rows, row0, n);
     const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
     std::vector<MmCol> dc;
     MinimapArgs m = minimap_args(pl, p);
     minimap_columns(columns, cols, team_ids != nullptr, team_ids, team_vals, (size_t)n_team, dc, m.corner);
     m.ncols = (int)dc.size();
-    if (n == 0) return EAGLE_OK;
+    if (n == 0) return;
     HIP_CHECK(hipSetDevice(device));
     Net net;
     const size_t span = (size_t)((n - 1) * g.frame_stride + g.extent);
@@ -504,9 +559,46 @@ int eagle_op_minimap(int device, const double* values, const EaglePostColumn* co
     m.mask = (const uint8_t*)net.upload(bits.data(), bits.size());
     m.rows = rows; m.row0 = row0; m.n = n; m.stride = MM_HEAD + m.ncols;
     m.lists = (int4*)net.get((size_t)std::min(n, MM_PASS) * m.stride * sizeof(int4));
+    if (p->control) {                                                        // the grids of the window, in front of the draw on the same (null) stream
+        std::vector<CtCol> sc;
+        control_columns(columns, cols, team_ids, team_vals, (size_t)n_team, sc);
+        ControlArgs c{};
+        c.R = cp->cells_per_metre; c.gw = 105 * c.R; c.gh = 68 * c.R; c.t_react = cp->t_react; c.v_max = cp->v_max; c.beta = cp->beta;
+        c.ncols = (int)sc.size(); c.stride = 1 + c.ncols; c.rows = rows; c.values = m.values;
+        c.vel = (const double2*)net.upload(velocities, (size_t)cols * rows * 2 * sizeof(double));
+        sc.resize(std::max<size_t>(sc.size(), 2), CtCol{0, 0});
+        c.cols = (const CtCol*)net.upload(sc.data(), sc.size() * sizeof(CtCol));
+        c.lists = (float4*)net.get((size_t)std::min(n, CT_PASS) * c.stride * sizeof(float4));
+        const size_t cells = (size_t)c.gw * c.gh;
+        uint8_t* d_g = (uint8_t*)net.get((size_t)n * cells);
+        for (int f0 = 0; f0 < n; f0 += CT_PASS) {
+            ControlArgs b = c;
+            b.n = std::min(n - f0, CT_PASS); b.row0 = row0 + f0; b.out = d_g + (size_t)f0 * cells;
+            control_launch(b, nullptr);
+        }
+        m.grid = d_g; m.ctl_R = c.R; m.ctl_gw = c.gw; m.ctl_gh = c.gh;
+    }
     minimap_launch(m, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, d_out, span, hipMemcpyDeviceToHost));
+}
+
+int eagle_op_minimap(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
+                     const EagleMinimapParams* p, int row0, int n, int out_format, const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    op_minimap("eagle_op_minimap", device, values, nullptr, columns, rows, cols, team_ids, team_vals, n_team, p, nullptr, row0, n, out_format, out_layout, out);
+    API_END(hh)
+}
+
+int eagle_op_minimap_control(int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                             const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleControlParams* cp, int row0, int n, int out_format,
+                             const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    op_minimap("eagle_op_minimap_control", device, values, velocities, columns, rows, cols, team_ids, team_vals, n_team, p, cp, row0, n, out_format, out_layout, out);
     API_END(hh)
 }
 

@@ -189,6 +189,54 @@ __global__ __launch_bounds__(PS_THREADS) void post_series_kernel(const double2* 
     }
 }
 
+// K22a — velocities of every cell of a table: one thread per (column, row), the differences of tests/control_ref.py in float64, each operation single and in
+// the order written there.  Memory-bound: 16 bytes per cell in (neighbours come from the same cache lines), 16 out.
+__device__ __forceinline__ bool cell_finite(double2 v) { return fabs(v.x) <= 1.7976931348623157e308 && fabs(v.y) <= 1.7976931348623157e308; }
+
+__global__ __launch_bounds__(PS_THREADS) void post_velocity_kernel(const double2* values, const int32_t* frames, double2* out, int rows, int cols, double fps, int max_gap,
+                                                                   double cap)
+{
+    const int r = blockIdx.x * PS_THREADS + threadIdx.x;
+    if (r >= rows) return;
+    const long long fr = frames[r];
+    const long long fa = r > 0 ? frames[r - 1] : 0, fb = r + 1 < rows ? frames[r + 1] : 0;
+    const bool near_a = r > 0 && fr - fa <= max_gap, near_b = r + 1 < rows && fb - fr <= max_gap;
+    for (int c = blockIdx.y; c < cols; c += gridDim.y) {
+        const double2* A = values + (size_t)c * rows;
+        const double2 p = A[r];
+        double2 v = make_double2(post_nan(), post_nan());
+        if (cell_finite(p)) {
+            double2 lo = p, hi = p;
+            long long flo = fr, fhi = fr;
+            if (near_a) { const double2 q = A[r - 1]; if (cell_finite(q)) { lo = q; flo = fa; } }
+            if (near_b) { const double2 q = A[r + 1]; if (cell_finite(q)) { hi = q; fhi = fb; } }
+            v = make_double2(0.0, 0.0);
+            if (fhi != flo) {
+                const double dt = (double)(fhi - flo) / fps;
+                v.x = (hi.x - lo.x) / dt;
+                v.y = (hi.y - lo.y) / dt;
+            }
+            const double s = sqrt(v.x * v.x + v.y * v.y);
+            if (s > cap) { const double k = cap / s; v.x = v.x * k; v.y = v.y * k; }
+        }
+        out[(size_t)c * rows + r] = v;
+    }
+}
+
+static void velocity_check(const EagleKinematicsParams* p)
+{
+    if (!p) fail(EAGLE_E_INVALID, "velocities: params is NULL");
+    if (p->fps <= 0 || p->max_gap <= 0 || !(p->speed_cap > 0) || !std::isfinite(p->speed_cap))
+        fail(EAGLE_E_INVALID, "velocities: fps %d, max_gap %d and speed_cap %g must be positive (and finite)", p->fps, p->max_gap, p->speed_cap);
+}
+
+static void velocity_launch(const double2* values, const int32_t* frames, double2* out, int rows, int cols, const EagleKinematicsParams* p, hipStream_t s)
+{
+    const dim3 grid((unsigned)((rows + PS_THREADS - 1) / PS_THREADS), (unsigned)std::min(cols, 65535));
+    hipLaunchKernelGGL(post_velocity_kernel, grid, dim3(PS_THREADS), 0, s, values, frames, out, rows, cols, (double)p->fps, p->max_gap, p->speed_cap);
+    HIP_CHECK(hipGetLastError());
+}
+
 // ---- host: the sequential part ------------------------------------------------------------------------------------------------------
 struct BallCand { double ix, iy, rx, ry, conf; };
 
@@ -448,8 +496,85 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
 void eagle_post_free(EaglePostTable* t)
 {
     if (!t) return;
-    if (t->d_values) { (void)hipSetDevice(t->h->cfg.device); (void)hipFree(t->d_values); }
+    if (t->d_values || t->d_vel) (void)hipSetDevice(t->h->cfg.device);
+    if (t->d_values) (void)hipFree(t->d_values);
+    if (t->d_vel) (void)hipFree(t->d_vel);
     delete t;
+}
+
+int eagle_post_velocities(EagleHandle* h, EaglePostTable* t, const EagleKinematicsParams* p)
+{
+    API_BEGIN_H(h)
+    if (!t) fail(EAGLE_E_INVALID, "eagle_post_velocities: table is NULL");
+    if (t->h != h) fail(EAGLE_E_INVALID, "eagle_post_velocities: the table belongs to another handle");
+    velocity_check(p);
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    const size_t cells = (size_t)t->cols * t->rows;
+    t->host_vel_ok = false;
+    if (!t->d_vel) HIP_CHECK(hipMalloc((void**)&t->d_vel, std::max<size_t>(cells * sizeof(double2), 16)));
+    t->kin = *p;
+    if (cells) {
+        std::vector<void*> owned;
+        const hipStream_t s = h->s_main;
+        try {
+            const int32_t* d_frames = dev_upload(owned, t->frames, s);
+            timed_launch(h, "post_velocity", 32.0 * (double)cells, s, [&] { velocity_launch((const double2*)t->d_values, d_frames, (double2*)t->d_vel, t->rows, t->cols, p, s); });
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (h->prof) collect_spans(h);
+        } catch (...) {
+            for (void* q : owned) (void)hipFree(q);
+            throw;
+        }
+        for (void* q : owned) HIP_CHECK(hipFree(q));
+    }
+    API_END(h)
+}
+
+int eagle_post_velocity_values(EaglePostTable* t, double* values)
+{
+    if (!t || !values) return EAGLE_E_INVALID;
+    EagleHandle* h = t->h;
+    API_BEGIN
+    if (!t->d_vel) fail(EAGLE_E_INVALID, "eagle_post_velocity_values: the table has no velocities (eagle_post_velocities)");
+    if (!t->host_vel_ok) {
+        t->host_vel.resize((size_t)t->cols * t->rows * 2);
+        if (!t->host_vel.empty()) {
+            HIP_CHECK(hipSetDevice(h->cfg.device));
+            HIP_CHECK(hipMemcpy(t->host_vel.data(), t->d_vel, t->host_vel.size() * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        t->host_vel_ok = true;
+    }
+    std::copy(t->host_vel.begin(), t->host_vel.end(), values);
+    API_END(h)
+}
+
+int eagle_post_device_velocity_values(const EaglePostTable* t, const double** d_values)
+{
+    if (!t || !d_values) return EAGLE_E_INVALID;
+    *d_values = t->d_vel;
+    return EAGLE_OK;
+}
+
+int eagle_op_velocities(int device, const double* values, const int32_t* frames, int rows, int cols, const EagleKinematicsParams* p, double* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!values || !frames || !out || rows < 0 || cols < 0)
+        fail(EAGLE_E_INVALID, "eagle_op_velocities: bad argument (values %p, frames %p, out %p, %d rows, %d columns)", (const void*)values, (const void*)frames, (const void*)out, rows, cols);
+    velocity_check(p);
+    for (int r = 1; r < rows; ++r)
+        if (frames[r] <= frames[r - 1]) fail(EAGLE_E_INVALID, "eagle_op_velocities: frame numbers must ascend (row %d: %d after %d)", r, frames[r], frames[r - 1]);
+    const size_t cells = (size_t)rows * cols;
+    if (cells == 0) return EAGLE_OK;
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const double2* d_v = (const double2*)net.upload(values, cells * sizeof(double2));
+    const int32_t* d_f = (const int32_t*)net.upload(frames, (size_t)rows * sizeof(int32_t));
+    double2* d_o = (double2*)net.get(cells * sizeof(double2));
+    velocity_launch(d_v, d_f, d_o, rows, cols, p, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, d_o, cells * sizeof(double2), hipMemcpyDeviceToHost));
+    API_END(hh)
 }
 
 int eagle_post_shape(const EaglePostTable* t, int32_t* rows, int32_t* cols, int32_t* flags)

@@ -259,6 +259,10 @@ struct EagleHandle {
     void* mm_list = nullptr; size_t mm_list_cap = 0;
     void* mm_cols = nullptr; size_t mm_cols_cap = 0;
     uint8_t* mm_mask = nullptr; size_t mm_mask_cap = 0; int mm_mask_scale = 0, mm_mask_margin = -1;
+    // pitch control (control.hip): the site lists and site columns of the call being run, and the grids the minimap's control layer reads; grown on demand
+    void* ct_list = nullptr; size_t ct_list_cap = 0;
+    void* ct_cols = nullptr; size_t ct_cols_cap = 0;
+    void* ct_grid = nullptr; size_t ct_grid_cap = 0;
 };
 
 // A processed clip table (post.hip builds it; minimap.hip draws it)
@@ -272,6 +276,12 @@ struct EaglePostTable {
     double* d_values = nullptr;          // [cols][rows][2], resident until eagle_post_free
     std::vector<double> host;            // the same on the host, fetched on first use (getters, overlays)
     bool host_ok = false;
+    double* d_vel = nullptr;             // velocities, same layout (eagle_post_velocities), resident until eagle_post_free
+    EagleKinematicsParams kin{};
+    std::vector<double> host_vel;
+    bool host_vel_ok = false;
+    bool has_control = false;            // eagle_minimap_set_control
+    EagleControlParams control{};
 };
 
 namespace eagle {
@@ -304,6 +314,24 @@ AnnotArgs annot_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst, const E
 void frames_to_host(EagleHandle* h, int n, int fh, int fw, int batch, int out_format, const EagleYuvLayout* out_layout, uint8_t* out,
                     const std::function<void(int, int, const YuvGeom&, uint8_t*)>& draw);
 void clip_close(EagleHandle* h);                                                // clip.hip
+// control.hip: what the minimap's control layer needs from it
+struct CtCol { int32_t col; int32_t team0; };              // a site column of the table: a mapped Player pitch column, and whether its team is 0
+struct ControlArgs {
+    const double2* values;       // the table and its velocities, [column][row]
+    const double2* vel;
+    const CtCol* cols;           // site columns in table order
+    float4* lists;               // [n][stride]: {count}, then per site {qx, qy, team 0 ? 1 : 0}
+    uint8_t* out;                // [n][gh][gw]
+    unsigned long long* share;   // [n] sums of the bytes (zeroed in front of the launch), or nullptr
+    int rows, row0, n, ncols, stride, R, gw, gh;
+    float t_react, v_max, beta;
+};
+static constexpr int CT_PASS = 65535;                      // gridDim.y limit
+void control_check(const EagleControlParams* p);                                // EAGLE_E_INVALID unless the parameters are in range
+void control_columns(const EaglePostColumn* columns, int ncols, const int32_t* team_ids, const int32_t* team_vals, size_t n_team, std::vector<CtCol>& out);
+void control_launch(const ControlArgs& a, hipStream_t s);                       // n <= CT_PASS rows: (share memset,) sites, grids
+ControlArgs control_prepare(EagleHandle* h, EaglePostTable* t, const EagleControlParams* p, int max_pass);      // site columns uploaded, list space for max_pass rows
+void control_rows(EagleHandle* h, const ControlArgs& prepared, int row0, int n, uint8_t* d_out, int64_t* d_share);   // enqueued on s_main, not awaited
 }  // namespace eagle
 
 // ---- C ABI: the body of every entry runs between API_BEGIN and API_END ---------------------------------------

@@ -165,6 +165,9 @@ void eagle_destroy(EagleHandle* h)
     if (h->mm_list) (void)hipFree(h->mm_list);
     if (h->mm_cols) (void)hipFree(h->mm_cols);
     if (h->mm_mask) (void)hipFree(h->mm_mask);
+    if (h->ct_list) (void)hipFree(h->ct_list);
+    if (h->ct_cols) (void)hipFree(h->ct_cols);
+    if (h->ct_grid) (void)hipFree(h->ct_grid);
     if (h->reid_crops_h) (void)hipHostFree(h->reid_crops_h);
     if (h->reid_feats_h) (void)hipHostFree(h->reid_feats_h);
     if (h->clip_sat_h) (void)hipHostFree(h->clip_sat_h);

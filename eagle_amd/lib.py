@@ -71,7 +71,17 @@ class EaglePostParams(C.Structure):
 class EagleMinimapParams(C.Structure):
     """include/eagle.h EagleMinimapParams: pixels per metre, margin, the two optional layers, radii in pixels (0 = the default)."""
     _fields_ = [("scale", C.c_int32), ("margin", C.c_int32), ("voronoi", C.c_int32), ("footprint", C.c_int32), ("player_radius", C.c_int32),
-                ("ball_radius", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("ball_radius", C.c_int32), ("control", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EagleKinematicsParams(C.Structure):
+    """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
+    _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
+
+
+class EagleControlParams(C.Structure):
+    """include/eagle.h EagleControlParams: cells per metre (1, 2, 4), reaction time (s), top speed (m/s), softmin sharpness (1/s)."""
+    _fields_ = [("cells_per_metre", C.c_int32), ("t_react", C.c_float), ("v_max", C.c_float), ("beta", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
 POST_PLAYER, POST_GOALKEEPER, POST_BALL, POST_BOUNDARY = 0, 1, 2, 3    # include/eagle.h EAGLE_POST_*
@@ -201,6 +211,17 @@ def load():
     L.eagle_minimap_device_frames.argtypes = [vp, vp, i32, i32, mp, i32, yl, vp]
     L.eagle_minimap_frames.argtypes = [vp, vp, i32, i32, mp, i32, yl, vp]
     L.eagle_op_minimap.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, mp, i32, i32, i32, yl, vp]
+    kp, cp = C.POINTER(EagleKinematicsParams), C.POINTER(EagleControlParams)
+    L.eagle_post_velocities.argtypes = [vp, vp, kp]
+    L.eagle_post_velocity_values.argtypes = [vp, vp]
+    L.eagle_post_device_velocity_values.argtypes = [vp, C.POINTER(vp)]
+    L.eagle_control_size.argtypes = [cp, C.POINTER(i32), C.POINTER(i32)]
+    L.eagle_control_device_grids.argtypes = [vp, vp, i32, i32, cp, vp, vp]
+    L.eagle_control_grids.argtypes = [vp, vp, i32, i32, cp, vp, vp]
+    L.eagle_minimap_set_control.argtypes = [vp, cp]
+    L.eagle_op_velocities.argtypes = [i32, vp, vp, i32, i32, kp, vp]
+    L.eagle_op_control.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, cp, i32, i32, vp, vp]
+    L.eagle_op_minimap_control.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, cp, i32, i32, i32, yl, vp]
     _lib = L
     return L
 
@@ -215,7 +236,9 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate",
            "eagle_annotate_frames_prims", "eagle_postprocess", "eagle_post_free", "eagle_post_shape", "eagle_post_layout", "eagle_post_values",
            "eagle_post_device_values", "eagle_overlay_from_table", "eagle_minimap_size", "eagle_minimap_device_frames", "eagle_minimap_frames",
-           "eagle_op_minimap"]
+           "eagle_op_minimap", "eagle_post_velocities", "eagle_post_velocity_values", "eagle_post_device_velocity_values", "eagle_control_size",
+           "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
+           "eagle_op_minimap_control"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -542,6 +565,36 @@ class Handle:
         self._check(self.L.eagle_minimap_frames(self._h, table._t, int(row0), int(n), C.byref(params), _out_pix(fmt), None if lay is None else C.byref(lay),
                                                 out.ctypes.data_as(C.c_void_p)), "minimap_frames")
         return out
+
+    # --- kinematics and pitch control (include/eagle.h, eagle_post_velocities / eagle_control_*) -------------------
+    def velocities(self, table, fps, max_gap=None, speed_cap=12.0):
+        """The velocity of every cell of a PostTable of this handle, computed on the GPU and kept with the table -> float64 [columns][rows][2]
+        (NaN where the cell is missing; m/s, px/s for video columns).  max_gap None: fps frames."""
+        p = kinematics_params(fps, max_gap, speed_cap)
+        self._check(self.L.eagle_post_velocities(self._h, table._t, C.byref(p)), "post_velocities")
+        v = np.zeros((len(table.columns), len(table.rows), 2), np.float64)
+        self._check(self.L.eagle_post_velocity_values(table._t, v.ctypes.data_as(C.c_void_p)), "post_velocity_values")
+        table.kinematics_params = p
+        return v
+
+    def control_device(self, table, d_out, params, row0=0, n=None, d_share=None):
+        """Rows row0 .. row0 + n - 1 -> n control grids [n][gh][gw] at ``d_out`` (device memory) and, with ``d_share``, n int64 byte sums."""
+        n = len(table.rows) - row0 if n is None else n
+        self._check(self.L.eagle_control_device_grids(self._h, table._t, int(row0), int(n), C.byref(params), d_out, d_share), "control_device_grids")
+
+    def control(self, table, params, row0=0, n=None):
+        """As control_device, to host memory -> (uint8 [n, gh, gw], int64 [n] sums of each grid's bytes); team 0's area share is sums / (255 gw gh)."""
+        n = len(table.rows) - row0 if n is None else n
+        gw, gh = control_size(params)
+        out, share = np.zeros((max(n, 0), gh, gw), np.uint8), np.zeros(max(n, 0), np.int64)
+        keep = np.zeros(2, np.int64)
+        self._check(self.L.eagle_control_grids(self._h, table._t, int(row0), int(n), C.byref(params), (out if out.size else keep).ctypes.data_as(C.c_void_p),
+                                               (share if share.size else keep).ctypes.data_as(C.c_void_p)), "control_grids")
+        return out, share
+
+    def minimap_set_control(self, table, params):
+        """The parameters the minimap's ``control`` layer of this table is computed with (None: forget them)."""
+        self._check(self.L.eagle_minimap_set_control(table._t, None if params is None else C.byref(params)), "minimap_set_control")
 
     def reproject(self, recs, Hs, flags):
         """In place: re-project foot points / boundaries of the flagged records with the given homographies (cadence mode)."""
@@ -1062,11 +1115,12 @@ def op_annotate(frames, prims, offsets, fmt="bgr", layout=None, out=None, device
 
 
 # --- the minimap ------------------------------------------------------------------------------------------------
-def minimap_params(scale=8, margin=None, voronoi=False, footprint=True, player_radius=0, ball_radius=0):
-    """EagleMinimapParams; margin None: two metres' worth of pixels, at most 64."""
+def minimap_params(scale=8, margin=None, voronoi=False, footprint=True, player_radius=0, ball_radius=0, control=False):
+    """EagleMinimapParams; margin None: two metres' worth of pixels, at most 64.  control: the pitch-control layer (Handle.minimap_set_control /
+    op_minimap_control say with which parameters)."""
     if margin is None:
         margin = min(64, 2 * int(scale))
-    return EagleMinimapParams(int(scale), int(margin), int(bool(voronoi)), int(bool(footprint)), int(player_radius), int(ball_radius))
+    return EagleMinimapParams(int(scale), int(margin), int(bool(voronoi)), int(bool(footprint)), int(player_radius), int(ball_radius), int(bool(control)))
 
 
 def minimap_size(params):
@@ -1106,6 +1160,105 @@ def op_minimap(values, columns, team_mapping, params, row0=0, n=None, fmt="bgr",
                             nt, C.byref(params), int(row0), int(n), _out_pix(fmt), None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p))
     if rc:
         raise EagleError(f"eagle_op_minimap failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if lay is None:
+        return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+    return out
+
+
+# --- kinematics and pitch control ---------------------------------------------------------------------------------
+def kinematics_params(fps, max_gap=None, speed_cap=12.0):
+    """EagleKinematicsParams; max_gap None: fps frames (a neighbour row more than a second away is not differenced)."""
+    return EagleKinematicsParams(int(fps), int(fps if max_gap is None else max_gap), float(speed_cap), 0)
+
+
+def control_params(cells_per_metre=1, t_react=0.7, v_max=5.0, beta=4.0):
+    """EagleControlParams: the conventional constants of the time-to-intercept model (not fitted to data)."""
+    return EagleControlParams(int(cells_per_metre), float(t_react), float(v_max), float(beta))
+
+
+def control_size(params):
+    """(gw, gh) of the grids these parameters give (include/eagle.h eagle_control_size; no GPU involved)."""
+    gw, gh = C.c_int(0), C.c_int(0)
+    L = load()
+    rc = L.eagle_control_size(C.byref(params), C.byref(gw), C.byref(gh))
+    if rc:
+        raise EagleError(f"eagle_control_size failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return gw.value, gh.value
+
+
+def _table_args(what, values, columns):
+    values = np.ascontiguousarray(values, np.float64)
+    if not (isinstance(columns, np.ndarray) and columns.dtype == POSTCOL_DTYPE):
+        columns = np.array([(k, i, v, 0) for k, i, v in columns], POSTCOL_DTYPE)
+    columns = np.ascontiguousarray(columns)
+    if values.ndim != 3 or len(columns) != values.shape[0] or values.shape[2] != 2:
+        raise EagleError(f"{what}: values must be [cols][rows][2] with one column descriptor per column")
+    return values, columns
+
+
+def _ptr(a, keep):
+    return None if a is None else (a if a.size else keep).ctypes.data_as(C.c_void_p)
+
+
+def op_velocities(values, frames, params, device=0):
+    """post_velocity_kernel on a constructed table (include/eagle.h eagle_op_velocities): values float64 [cols][rows][2], frames int32 [rows]
+    ascending, params EagleKinematicsParams -> float64 [cols][rows][2]."""
+    L = load()
+    values = np.ascontiguousarray(values, np.float64)
+    frames = np.ascontiguousarray(frames, np.int32)
+    if values.ndim != 3 or values.shape[2] != 2 or len(frames) != values.shape[1]:
+        raise EagleError("op_velocities: values must be [cols][rows][2] with one frame number per row")
+    out = np.zeros(values.shape, np.float64)
+    keep = np.zeros(4, np.float64)
+    rc = L.eagle_op_velocities(device, _ptr(values, keep), _ptr(frames, keep), values.shape[1], values.shape[0], C.byref(params), _ptr(out, keep))
+    if rc:
+        raise EagleError(f"eagle_op_velocities failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
+
+
+def op_control(values, velocities, columns, team_mapping, params, row0=0, n=None, device=0):
+    """The two control launches on a constructed table (include/eagle.h eagle_op_control) -> (uint8 [n, gh, gw], int64 [n] byte sums)."""
+    L = load()
+    values, columns = _table_args("op_control", values, columns)
+    velocities = np.ascontiguousarray(velocities, np.float64)
+    if velocities.shape != values.shape:
+        raise EagleError("op_control: velocities must have the shape of values")
+    cols, rows = values.shape[:2]
+    ids, vals, nt = _team_arrays(team_mapping)
+    n = rows - row0 if n is None else n
+    gw, gh = control_size(params)
+    out, share = np.zeros((max(n, 0), gh, gw), np.uint8), np.zeros(max(n, 0), np.int64)
+    keep = np.zeros(4, np.float64)
+    rc = L.eagle_op_control(device, _ptr(values, keep), _ptr(velocities, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(params),
+                            int(row0), int(n), _ptr(out, keep), _ptr(share, keep))
+    if rc:
+        raise EagleError(f"eagle_op_control failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out, share
+
+
+def op_minimap_control(values, velocities, columns, team_mapping, params, control, row0=0, n=None, fmt="bgr", layout=None, out=None, device=0):
+    """op_minimap with the ``control`` layer drawn from given velocities (include/eagle.h eagle_op_minimap_control); params: minimap_params(...,
+    control=True), control: control_params(...)."""
+    L = load()
+    values, columns = _table_args("op_minimap_control", values, columns)
+    velocities = np.ascontiguousarray(velocities, np.float64)
+    if velocities.shape != values.shape:
+        raise EagleError("op_minimap_control: velocities must have the shape of values")
+    cols, rows = values.shape[:2]
+    ids, vals, nt = _team_arrays(team_mapping)
+    n = rows - row0 if n is None else n
+    w, h = minimap_size(params)
+    lay = _yuv_layout(layout)
+    need = out_span(fmt, h, w, lay, n)
+    if out is None:
+        out = np.zeros(need, np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+        raise EagleError(f"op_minimap_control: out must be a contiguous uint8 array of at least {need} bytes")
+    keep = np.zeros(4, np.float64)
+    rc = L.eagle_op_minimap_control(device, _ptr(values, keep), _ptr(velocities, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt,
+                                    C.byref(params), C.byref(control), int(row0), int(n), _out_pix(fmt), None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_minimap_control failed ({rc}): {L.eagle_last_error(None).decode()}")
     if lay is None:
         return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
     return out

@@ -8,11 +8,14 @@ mplsoccer is not claimed).  ``annotate.write_y4m`` writes the I420 result as a v
 from . import lib
 
 
-def minimap(handle, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, player_radius=0, ball_radius=0):
+def minimap(handle, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, player_radius=0, ball_radius=0, control=None):
     """A lib.PostTable of ``handle`` -> its minimap pictures on the host: uint8 [n, h, w, 3] ("bgr") or [n, 3h/2, w] ("nv12" / "i420"), one per table
     row, with w = 105 scale + 2 margin and h = 68 scale + 2 margin (margin None: two metres' worth of pixels).  ``rows``: (first row, count) to draw
-    a window of the table.  voronoi needs a table with a team mapping."""
-    params = lib.minimap_params(scale, margin, voronoi, footprint, player_radius, ball_radius)
+    a window of the table.  voronoi needs a table with a team mapping.  ``control``: a lib.control_params(...) draws the pitch-control layer in
+    Voronoi's place (not both); the table needs velocities (Handle.velocities) and a team mapping."""
+    params = lib.minimap_params(scale, margin, voronoi, footprint, player_radius, ball_radius, control is not None)
+    if control is not None:
+        handle.minimap_set_control(table, control)
     row0, n = (0, len(table.rows)) if rows is None else (int(rows[0]), int(rows[1]))
     return handle.minimap(table, params, row0, n, pixel_format)
 

@@ -52,7 +52,17 @@ class Processor:
         ``table``: draw the processed table (process_data above) instead of the raw records."""
         return self.model.annotate(frames, coords_or_records, team_mapping, pixel_format, out_format, table=table)
 
-    def minimap(self, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None):
+    def minimap(self, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, control=None):
         """The minimap pictures of a processed table (process_data above), drawn on the GPU: see eagle_amd/minimap.py."""
         from . import minimap as mm
-        return mm.minimap(self.model.handle, table, scale, margin, voronoi, footprint, pixel_format, rows)
+        return mm.minimap(self.model.handle, table, scale, margin, voronoi, footprint, pixel_format, rows, control=control)
+
+    def kinematics(self, table, fps, max_gap=None, speed_cap=12.0):
+        """Velocities of a processed table (computed on the GPU, kept with the table) plus per id distance covered and top speed: see eagle_amd/control.py."""
+        from . import control as ct
+        return ct.kinematics(self.model.handle, table, fps, max_gap, speed_cap)
+
+    def control(self, table, cells_per_metre=1, t_react=0.7, v_max=5.0, beta=4.0, rows=None):
+        """The pitch-control grids of a processed table with velocities (kinematics above) and team 0's area share per row: see eagle_amd/control.py."""
+        from . import control as ct
+        return ct.control(self.model.handle, table, cells_per_metre, t_react, v_max, beta, rows)

@@ -311,7 +311,7 @@ int eagle_overlay_from_table(EaglePostTable* t, int row, const EagleFrameResult*
  * conversion and the output layouts are those of the annotated output above.  Two launches (minimap.hip) on the handle's main stream read the table
  * where eagle_postprocess left it; the handle's records, staging buffers and graphs are not involved.
  * EAGLE_E_INVALID with a message, before any launch: NULL pointers, scale odd or outside 2 .. 32, margin odd or outside 0 .. 64, a radius negative or
- * above 4 scale, voronoi with a table that has no team mapping, n < 0, a row window outside the table (a table of 0 rows with n > 0), and every layout
+ * above 4 scale, voronoi with a table that has no team mapping, control together with voronoi or without what it needs (below), n < 0, a row window outside the table (a table of 0 rows with n > 0), and every layout
  * error eagle_annotate_* refuses.  n == 0 is success and writes nothing. */
 typedef struct EagleMinimapParams {
     int32_t scale;                 /* pixels per metre: even, 2 .. 32 */
@@ -319,7 +319,8 @@ typedef struct EagleMinimapParams {
     int32_t voronoi, footprint;    /* != 0: draw that layer */
     int32_t player_radius;         /* pixels, 0 .. 4 scale; 0 = max(2, scale) */
     int32_t ball_radius;           /* outer radius of the ring, pixels, 0 .. 4 scale; 0 = max(3, scale / 2 + 1); the ring is max(1, radius / 3) thick */
-    int32_t reserved[2];
+    int32_t control;               /* != 0: draw the pitch-control layer in Voronoi's slot (below: eagle_minimap_set_control); refused together with voronoi */
+    int32_t reserved;
 } EagleMinimapParams;
 int eagle_minimap_size(const EagleMinimapParams* p, int* w, int* h);
 /* rows row0 .. row0 + n - 1 -> n pictures in HBM (a buffer of the caller: eagle_device_alloc, or an encoder's input surface with its layout); returns when
@@ -333,6 +334,52 @@ int eagle_minimap_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, con
  * mapping as two arrays (team_ids NULL: no mapping).  `out` is read first, so bytes the layout does not cover come back as they were. */
 int eagle_op_minimap(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
                      int n_team, const EagleMinimapParams* p, int row0, int n, int out_format, const EagleYuvLayout* out_layout, uint8_t* out);
+
+/* ---- kinematics and pitch control: what a processed table says about movement (own specification: tests/control_ref.py defines every output bit) -------
+ * VELOCITIES, float64 without contraction, for every column of the table in its layout [cols][rows][2] (video columns in px/s).  A cell is present
+ * when x and y are finite; the neighbour row r - 1 (r + 1) is usable when it is present and at most max_gap frames away; both usable: the central
+ * difference (p[r + 1] - p[r - 1]) / ((f[r + 1] - f[r - 1]) / fps); one: the one-sided difference; none: (0, 0); an absent cell: (NaN, NaN); a speed
+ * above speed_cap is scaled back to it.  One launch (post.hip); the result is kept with the table until eagle_post_free and replaces an earlier one.
+ * CONTROL GRID, float32 without contraction: per row cells_per_metre (1, 2 or 4) cells per metre, gw = 105 R by gh = 68 R bytes, grid row 0 at pitch
+ * y = 0.  The sites are the minimap's Voronoi sites (Player pitch columns with a team entry, present, within 1024 m; a mapping is required).  A site
+ * reacts for t_react seconds at its velocity (q = p + v t_react in fp32, a non-finite velocity component counts as 0, q clamped to +-2^20) and then
+ * runs at v_max: t_i = t_react + |cell - q| / v_max.  A cell's byte is floor(255 num / den + 0.5) with w_i = exp(-beta (t_i - min t)), num the sum of w_i
+ * over team 0 and den over all sites in table order; 128 everywhere for a row without sites.  d_share[i] is the exact sum of row i's bytes (the team-0
+ * area share is that over 255 gw gh).  Two launches (control.hip) on the handle's main stream.  The constants are conventional choices (0.7 s, 5 m/s,
+ * 4 / s, a 12 m/s cap), not fitted to data.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, fps, max_gap or speed_cap not positive (or speed_cap not finite), cells_per_metre
+ * outside {1, 2, 4}, t_react outside 0 .. 1000, v_max outside 0.001 .. 1e6, beta outside (0, 1e6], a table without a team mapping, a table without
+ * velocities, a row window outside the table, frames of an operator entry that do not ascend.  n == 0 is success and writes nothing. */
+typedef struct EagleKinematicsParams {
+    int32_t fps;                   /* > 0: frames per second of the frame numbers */
+    int32_t max_gap;               /* > 0: a neighbour row further than this many frames away is not differenced (a usual choice: fps) */
+    double speed_cap;              /* > 0, finite: m/s (px/s for video columns) */
+    int64_t reserved;
+} EagleKinematicsParams;
+typedef struct EagleControlParams {
+    int32_t cells_per_metre;       /* 1, 2 or 4 */
+    float t_react, v_max, beta;    /* seconds, m/s, 1/s */
+    int32_t reserved[4];
+} EagleControlParams;
+int eagle_post_velocities(EagleHandle* h, EaglePostTable* t, const EagleKinematicsParams* p);
+int eagle_post_velocity_values(EaglePostTable* t, double* values /* [cols][rows][2] */);                     /* copies the velocities to the host */
+int eagle_post_device_velocity_values(const EaglePostTable* t, const double** d_values);                     /* NULL before eagle_post_velocities */
+int eagle_control_size(const EagleControlParams* p, int* gw, int* gh);
+/* rows row0 .. row0 + n - 1 -> n grids [n][gh][gw] and, with d_share != NULL, n sums in HBM; returns when they are complete */
+int eagle_control_device_grids(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleControlParams* p, uint8_t* d_out, int64_t* d_share);
+/* Same, to host memory, in passes of what 32 MB of device staging hold. */
+int eagle_control_grids(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleControlParams* p, uint8_t* out, int64_t* share);
+/* The parameters the minimap's `control` layer is computed with (kept with the table; p NULL: forget them).  The layer needs them, the table's
+ * velocities and a team mapping; the grids of a call's rows are computed on its stream in front of the draw launch.  A pixel of the pitch rectangle
+ * takes its cell's byte c and, with a = c + (c >> 7), the colour (red a + blue (256 - a) + 128) >> 8, tinted like a Voronoi area. */
+int eagle_minimap_set_control(EaglePostTable* t, const EagleControlParams* p);
+/* Operator entries (host buffers in / out, no handle) for constructed tables. */
+int eagle_op_velocities(int device, const double* values, const int32_t* frames, int rows, int cols, const EagleKinematicsParams* p, double* out);
+int eagle_op_control(int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                     const int32_t* team_vals, int n_team, const EagleControlParams* p, int row0, int n, uint8_t* out_grid, int64_t* out_share /* may be NULL */);
+int eagle_op_minimap_control(int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                             const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleControlParams* cp, int row0, int n, int out_format,
+                             const EagleYuvLayout* out_layout, uint8_t* out);
 
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
