@@ -14,7 +14,8 @@ without a codec), drawn on the GPU from the raw records, and ``metadata.json`` t
 (``main.py:37-38``).  ``--processed`` runs the reference's post-processor (``main.py:34-41``: ``Processor.process_data`` and ``format_data``) on
 the GPU (eagle_amd/postprocess.py) and writes ``raw_data.json`` (the table, one record per kept frame), ``processed_data.json`` and the
 ``team_mapping`` into ``metadata.json``; together with ``--annotated`` the video is then drawn from the processed table (kept frames only,
-interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  ``--minimap`` (with ``--processed``) writes ``minimap.y4m``: the processed table as
+interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  ``--merge-ids`` (with ``--processed``) stitches the fragments of one person
+under several tracker ids into one id first and lists the joins as ``merges`` in ``metadata.json``.  ``--minimap`` (with ``--processed``) writes ``minimap.y4m``: the processed table as
 a top-down video of the pitch at the clip's fps (eagle_amd/minimap.py; ``--minimap-voronoi`` tints the areas each team controls, ``--minimap-scale``
 sets the pixels per metre).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
@@ -87,6 +88,9 @@ def main(argv=None):
                     help="also run the post-processor of main.py:34-41 on the GPU: write <out>/raw_data.json and <out>/processed_data.json, put the team mapping into "
                          "metadata.json, and draw --annotated from the processed table")
     ap.add_argument("--smooth", action="store_true", help="with --processed: process_data(smooth=True)")
+    ap.add_argument("--merge-ids", action="store_true",
+                    help="with --processed: stitch the fragments of one person under several tracker ids into one id (off: the reference as written, which never "
+                         "merges); metadata.json then lists the joins as \"merges\" and its team_mapping holds the teams the merged ids inherit")
     ap.add_argument("--minimap", action="store_true", help="with --processed: also write <out>/minimap.y4m, the processed table as a top-down video of the pitch")
     ap.add_argument("--minimap-voronoi", action="store_true", help="with --minimap: tint the pitch by the team whose player is nearest")
     ap.add_argument("--minimap-scale", type=int, default=8, help="with --minimap: pixels per metre (even, 2 .. 32)")
@@ -99,6 +103,8 @@ def main(argv=None):
         ap.error("--minimap draws the processed table: it needs --processed")
     if (a.kinematics or a.minimap_control or a.control_grid) and not a.processed:
         ap.error("--kinematics, --minimap-control and --control-grid work on the processed table: they need --processed")
+    if a.merge_ids and not a.processed:
+        ap.error("--merge-ids works on the processed table: it needs --processed")
     if a.minimap_control and a.minimap_voronoi:
         ap.error("--minimap-control and --minimap-voronoi draw in the same slot: choose one")
 
@@ -142,7 +148,8 @@ def main(argv=None):
         from . import postprocess
         from .annotate import write_y4m
         from .processor import Processor
-        table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth)
+        table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids)
+        merges = table.merges
         with open(os.path.join(a.out, "raw_data.json"), "w") as f:
             json.dump(postprocess.json_rows(postprocess.raw_data_rows(table)), f)
         with open(os.path.join(a.out, "processed_data.json"), "w") as f:
@@ -166,6 +173,8 @@ def main(argv=None):
                                                                    control=lib.control_params(min(4, a.minimap_scale)) if a.minimap_control else None), a.fps)
         table.close()
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
+        if a.merge_ids:
+            meta["merges"] = merges
     elif a.annotated:
         from .annotate import write_y4m
         from .processor import Processor

@@ -4,8 +4,11 @@
 // Host part (sequential and tiny, like tracker.hip's): column discovery in first-appearance order, the kept frames, the two ball walks, the list
 // of (row, column, x, y) entries, the 1 % filter and the goalkeeper fold's pairing.  Device part, two launches on the handle's main stream:
 //   post_scatter_kernel  the raw [column][row] table: NaN, then the entries (grouped by column; a workgroup fills and then scatters its own chunk)
-//   post_series_kernel   one workgroup per raw column, rows in blocks of 256: statistics, goalkeeper fold, previous / next valid row by wave scans
-//                        carried between blocks through LDS, np.interp's gap fill in double, the every-other-row smoothing; 16-byte stores.
+//   post_series_kernel   one workgroup per raw column, rows in blocks of 256: statistics, the fold of the column's chain (goalkeeper fold and, with
+//                        merge_ids, the stitched fragments of one track), previous / next valid row by wave scans carried between blocks through
+//                        LDS, np.interp's gap fill in double, the every-other-row smoothing; 16-byte stores.
+// An output column is an ordered chain of members, each a raw column plus the Player column folded in front of it, with the rows the member spans;
+// spans ascend and do not overlap, so a row belongs to at most one member and costs at most two raw cells, whatever the chain's length.
 // Arithmetic: pandas' method="linear" is np.interp over row positions, slope * (x - x0) + y0 in float64 without contraction (the library is
 // built with -ffp-contract=off).  x and y of a cell are interpolated as two series that share their rows.
 #include "runtime.h"
@@ -16,7 +19,9 @@ namespace eagle {
 static constexpr int PS_THREADS = 256, PS_WAVES = PS_THREADS / 64, SC_ROWS = 1024;
 static constexpr int PS_MAX_BLOCKS = 4096;        // dynamic LDS of the series kernel: 8 bytes per 256-row block -> at most 2^20 rows (11 hours at 25 frames/s)
 
-struct PostCol { int32_t out, pair, fill, pad; };           // per raw column: output column (-1: dropped or folded away), Player column folded in first (-1: none), ball rule
+static constexpr int PS_MAX_CHAIN = 100;          // members of a chain: each holds >= 1 % of the rows and their spans are disjoint
+struct PostCol { int32_t out, mem0, nmem, fill; };          // per raw column: output column (-1: dropped, folded or stitched away), its chain = members[mem0 .. mem0 + nmem), ball rule
+struct PostMember { int32_t first, last, col, pair; };      // rows the member spans, its raw column, the Player column folded in first (-1: none)
 struct PostStat { int32_t count, first, last, keep; };      // per raw column, before the fold: valid cells, first / last valid row, count >= 0.01 * rows
 
 __device__ __forceinline__ double post_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
@@ -58,9 +63,26 @@ __device__ __forceinline__ int wave_scan_min_rev(int v, int lane)
     return v;
 }
 
-// the cell of row r after the goalkeeper fold: Player.combine_first(Goalkeeper)
-__device__ __forceinline__ double2 folded(const double2* A, const double2* P, int r)
+// the chain of an output column: its members (in LDS), and the only member's two raw columns when there is just one
+struct Chain { const double2* raw; const PostMember* mem; const double2* A; const double2* P; int rows, n; };
+
+// the cell of row r after the fold: inside a member Player.combine_first(Goalkeeper); across members the one whose span covers the row
+__device__ __forceinline__ double2 folded(const Chain& ch, int r)
 {
+    const double2* A = ch.A;
+    const double2* P = ch.P;
+    if (ch.n > 1) {                                    // (uniform) the last member that starts at or before row r
+        int lo = 0, hi = ch.n;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ch.mem[mid].first <= r) lo = mid + 1; else hi = mid;
+        }
+        if (lo == 0) return make_double2(post_nan(), post_nan());
+        const PostMember m = ch.mem[lo - 1];
+        if (r > m.last) return make_double2(post_nan(), post_nan());
+        A = ch.raw + (size_t)m.col * ch.rows;
+        P = m.pair >= 0 ? ch.raw + (size_t)m.pair * ch.rows : nullptr;
+    }
     double2 v = A[r];
     if (P) { const double2 p = P[r]; if (cell_present(p)) v = p; }
     return v;
@@ -80,28 +102,38 @@ __device__ __forceinline__ double lerp_np(double y0, double y1, double x0, doubl
 }
 
 // component k of row r after the gap fill: p = latest valid row <= r (-1: none), n = earliest valid row >= r (INT_MAX: none)
-__device__ __forceinline__ double filled(const double2* A, const double2* P, int k, int r, int p, int n, bool fill)
+__device__ __forceinline__ double filled(const Chain& ch, int k, int r, int p, int n, bool fill)
 {
-    if (p == r) return comp(folded(A, P, r), k);
+    if (p == r) return comp(folded(ch, r), k);
     if (p < 0 || n == INT_MAX) {                       // outside the valid span: the ball's bfill / ffill, or left missing (limit_area="inside")
         if (!fill || (p < 0 && n == INT_MAX)) return post_nan();
-        return comp(folded(A, P, p < 0 ? n : p), k);
+        return comp(folded(ch, p < 0 ? n : p), k);
     }
-    return lerp_np(comp(folded(A, P, p), k), comp(folded(A, P, n), k), (double)p, (double)n, (double)r);
+    return lerp_np(comp(folded(ch, p), k), comp(folded(ch, n), k), (double)p, (double)n, (double)r);
 }
 
-__global__ __launch_bounds__(PS_THREADS) void post_series_kernel(const double2* raw, double2* out, const PostCol* cols, PostStat* stats, int rows, int nblk, int smooth)
+__global__ __launch_bounds__(PS_THREADS) void post_series_kernel(const double2* raw, double2* out, const PostCol* cols, const PostMember* members, PostStat* stats, int rows, int nblk,
+                                                                 int smooth)
 {
     extern __shared__ int blk_first[];                 // [nblk][2]: first valid row of the block per component; then the earliest valid row at or behind the block's start
     __shared__ int s_red[3][PS_WAVES];
     __shared__ int s_scan[2][2][PS_WAVES];
     __shared__ double s_f[2][PS_THREADS + 2];
+    __shared__ PostMember s_mem[PS_MAX_CHAIN];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const PostCol d = cols[c];
     const double2* A = raw + (size_t)c * rows;
-    const double2* P = d.pair >= 0 ? raw + (size_t)d.pair * rows : nullptr;
+    const int nmem = d.out >= 0 ? min(d.nmem, PS_MAX_CHAIN) : 0;      // (the host refuses longer chains)
+    if (tid < nmem) s_mem[tid] = members[d.mem0 + tid];
     for (int i = tid; i < 2 * nblk; i += PS_THREADS) blk_first[i] = INT_MAX;
     __syncthreads();
+    Chain ch{raw, s_mem, A, nullptr, rows, nmem};
+    if (nmem == 1) {
+        const PostMember m = s_mem[0];
+        ch.A = raw + (size_t)m.col * rows;
+        ch.P = m.pair >= 0 ? raw + (size_t)m.pair * rows : nullptr;
+    }
+    const bool own = nmem == 1 && ch.A == A;           // (uniform) the chain is this raw column alone: its cell is read once for both uses
     // (a) statistics of the raw column, and per block the first valid row of the folded series
     int cnt = 0, first = INT_MAX, last = -1;
     for (int b = 0; b < nblk; ++b) {
@@ -110,7 +142,8 @@ __global__ __launch_bounds__(PS_THREADS) void post_series_kernel(const double2* 
         if (r < rows) {
             double2 v = A[r];
             if (cell_present(v)) { ++cnt; first = min(first, r); last = r; }
-            if (P) { const double2 p = P[r]; if (cell_present(p)) v = p; }
+            if (own) { if (ch.P) { const double2 p = ch.P[r]; if (cell_present(p)) v = p; } }
+            else if (nmem) v = folded(ch, r);
             if (!is_nan(v.x)) fx = r;
             if (!is_nan(v.y)) fy = r;
         }
@@ -143,7 +176,7 @@ __global__ __launch_bounds__(PS_THREADS) void post_series_kernel(const double2* 
         const int r0 = b * PS_THREADS, r = r0 + tid;
         const bool in = r < rows;
         double2 v = make_double2(post_nan(), post_nan());
-        if (in) v = folded(A, P, r);                    // (b) the fold
+        if (in) v = folded(ch, r);                      // (b) the fold
         int p[2], n[2];
         for (int k = 0; k < 2; ++k) {                   // (c) neighbours: forward max-scan, backward min-scan
             const bool ok = in && !is_nan(comp(v, k));
@@ -163,13 +196,13 @@ __global__ __launch_bounds__(PS_THREADS) void post_series_kernel(const double2* 
                 tot = max(tot, s_scan[0][k][w]);
             }
             carry[k] = tot;
-            f[k] = in ? filled(A, P, k, r, pk, nk, fill) : post_nan();      // (d) gap fill
+            f[k] = in ? filled(ch, k, r, pk, nk, fill) : post_nan();      // (d) gap fill
             if (smooth) {                               // (e) the filled series of this block and of the row on either side of it
                 s_f[k][tid + 1] = f[k];
-                if (tid == 0) s_f[k][0] = b > 0 ? filled(A, P, k, r0 - 1, carry_in, carry_in == r0 - 1 ? r0 - 1 : nk, fill) : post_nan();
+                if (tid == 0) s_f[k][0] = b > 0 ? filled(ch, k, r0 - 1, carry_in, carry_in == r0 - 1 ? r0 - 1 : nk, fill) : post_nan();
                 if (tid == PS_THREADS - 1) {
                     const int rn = r0 + PS_THREADS;
-                    s_f[k][PS_THREADS + 1] = rn < rows ? filled(A, P, k, rn, next_in == rn ? rn : pk, next_in, fill) : post_nan();
+                    s_f[k][PS_THREADS + 1] = rn < rows ? filled(ch, k, rn, next_in == rn ? rn : pk, next_in, fill) : post_nan();
                 }
             }
         }
@@ -291,6 +324,64 @@ template <typename T> static T* dev_upload(std::vector<void*>& owned, const std:
     return (T*)p;
 }
 
+static int team_of(const EaglePostTable* t, int id)
+{
+    if (t->has_team)
+        for (size_t k = 0; k < t->team_ids.size(); ++k)
+            if (t->team_ids[k] == id) return t->team_vals[k];
+    return -1;
+}
+
+// merge_ids = 1: the fragments of one person under several tracker ids become one chain (rule and contract: tests/stitch_ref.py).  A track is a
+// person video column after the goalkeeper fold.  A link a -> b needs the same kind, last(a) < first(b), a frame gap g <= int(fps * 1.1), the end
+// points at most 10 g pixels apart and no two different known teams; the admissible links, ascending by (distance, gap, column of a, column of b),
+// are accepted while a has no successor, b no predecessor and the two chains' teams agree.
+struct PostTrack { int col, pair, kind, id, first, last; double fx, fy, lx, ly; int succ, pred, root, team; };
+struct PostLink { double d; int g, a, b; };
+
+static void stitch_tracks(std::vector<PostTrack>& tr, const std::vector<int32_t>& frames, int fps, EaglePostTable* t)
+{
+    const int nt = (int)tr.size(), limit = (int)((double)fps * 1.1);
+    std::vector<int> by_first(nt);
+    for (int i = 0; i < nt; ++i) by_first[i] = i;
+    std::stable_sort(by_first.begin(), by_first.end(), [&](int x, int y) { return tr[x].first < tr[y].first; });
+    std::vector<PostLink> links;
+    for (int a = 0; a < nt; ++a) {                      // the window of tracks that start behind last(a), within the temporal threshold
+        const PostTrack& A = tr[a];
+        auto it = std::upper_bound(by_first.begin(), by_first.end(), A.last, [&](int row, int x) { return row < tr[x].first; });
+        for (; it != by_first.end(); ++it) {
+            const PostTrack& B = tr[*it];
+            const int g = frames[B.first] - frames[A.last];
+            if (g > limit) break;
+            if (B.kind != A.kind) continue;
+            const double dx = B.fx - A.lx, dy = B.fy - A.ly;
+            const double xx = dx * dx, yy = dy * dy, d = std::sqrt(xx + yy);
+            if (d > 10.0 * (double)g) continue;
+            if (A.team >= 0 && B.team >= 0 && A.team != B.team) continue;
+            links.push_back(PostLink{d, g, a, *it});
+        }
+    }
+    std::sort(links.begin(), links.end(), [&](const PostLink& x, const PostLink& y) {
+        if (x.d != y.d) return x.d < y.d;
+        if (x.g != y.g) return x.g < y.g;
+        if (tr[x.a].col != tr[y.a].col) return tr[x.a].col < tr[y.a].col;
+        return tr[x.b].col < tr[y.b].col;
+    });
+    auto find = [&](int x) { while (tr[x].root != x) x = tr[x].root = tr[tr[x].root].root; return x; };
+    for (const PostLink& l : links) {
+        if (tr[l.a].succ >= 0 || tr[l.b].pred >= 0) continue;
+        const int ra = find(l.a);                       // (b has no predecessor: it heads its chain)
+        if (tr[ra].team >= 0 && tr[l.b].team >= 0 && tr[ra].team != tr[l.b].team) continue;
+        tr[l.a].succ = l.b; tr[l.b].pred = l.a; tr[l.b].root = ra;
+        if (tr[ra].team < 0) tr[ra].team = tr[l.b].team;
+        t->merges.push_back(EaglePostMerge{tr[l.a].kind, tr[l.a].id, tr[l.b].id, ra, l.g, -1, l.d});
+    }
+    for (EaglePostMerge& m : t->merges) {               // head and team of the finished chain
+        const PostTrack& H = tr[find(m.head_id)];
+        m.head_id = H.id; m.team = H.team;
+    }
+}
+
 static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, EaglePostTable* t)
 {
     t->h = h;
@@ -379,29 +470,78 @@ static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, con
     for (const PostEntry& e : ent) ++count[e.col];
     std::vector<PostCol> desc(nraw);
     std::vector<char> keep(nraw);
+    std::vector<int> pair(nraw, -1);
+    std::vector<std::vector<PostMember>> chain(nraw);   // per raw column that is an output column: its members
     for (int c = 0; c < nraw; ++c) {
         keep[c] = raw_cols[c].kind >= EAGLE_POST_BALL || (double)count[c] >= 0.01 * (double)rows;
-        desc[c] = PostCol{keep[c] ? 0 : -1, -1, raw_cols[c].kind == EAGLE_POST_BALL ? 1 : 0, 0};
+        desc[c] = PostCol{keep[c] ? 0 : -1, 0, 0, raw_cols[c].kind == EAGLE_POST_BALL ? 1 : 0};
         col_off[c + 1] = col_off[c] + count[c];
     }
     for (int c = 0; c < nraw; ++c) {
         if (raw_cols[c].kind != EAGLE_POST_GOALKEEPER || !raw_cols[c].video || !keep[c] || !keep[c - 1]) continue;
         auto it = col_of.find(std::make_pair(0, raw_cols[c].id));
         if (it == col_of.end() || !keep[it->second] || !keep[it->second + 1]) continue;
-        desc[c - 1].pair = it->second; desc[c].pair = it->second + 1;
+        pair[c - 1] = it->second; pair[c] = it->second + 1;
         desc[it->second].out = desc[it->second + 1].out = -1;
     }
-    int ncols = 0;
-    for (int c = 0; c < nraw; ++c)
-        if (desc[c].out >= 0) { desc[c].out = ncols++; t->columns.push_back(raw_cols[c]); }
-    t->cols = ncols;
     // entries grouped by column (stable: rows ascend inside a column)
     std::vector<int32_t> ent_row(ent.size()), fill_at(col_off.begin(), col_off.end() - 1);
     std::vector<double2> ent_xy(ent.size());
     for (const PostEntry& e : ent) { const int k = fill_at[e.col]++; ent_row[k] = e.row; ent_xy[k] = make_double2(e.x, e.y); }
+    for (int c = 0; c < nraw; ++c)
+        if (desc[c].out >= 0) chain[c].push_back(PostMember{0, rows - 1, c, pair[c]});
+    if (p->merge_ids) {
+        // 3b. the id merge: tracks = the person video columns after the fold, their spans and end points from the grouped entries
+        std::vector<PostTrack> tr;
+        for (int c = 0; c < nraw; ++c) {
+            if (raw_cols[c].kind >= EAGLE_POST_BALL || !raw_cols[c].video || desc[c].out < 0) continue;
+            PostTrack k{c, pair[c], raw_cols[c].kind, raw_cols[c].id, 0, 0, 0, 0, 0, 0, -1, -1, (int)tr.size(), team_of(t, raw_cols[c].id)};
+            int ef = col_off[c], el = col_off[c + 1] - 1;          // (a kept column holds at least one entry)
+            if (k.pair >= 0) {                                      // Player.combine_first(Goalkeeper): the Player cell wins a shared row
+                const int pf = col_off[k.pair], pl = col_off[k.pair + 1] - 1;
+                if (ent_row[pf] <= ent_row[ef]) ef = pf;
+                if (ent_row[pl] >= ent_row[el]) el = pl;
+            }
+            k.first = ent_row[ef]; k.fx = ent_xy[ef].x; k.fy = ent_xy[ef].y;
+            k.last = ent_row[el]; k.lx = ent_xy[el].x; k.ly = ent_xy[el].y;
+            tr.push_back(k);
+        }
+        stitch_tracks(tr, kept, p->fps, t);
+        for (size_t i = 0; i < tr.size(); ++i) {
+            if (tr[i].pred >= 0) continue;                          // a head: its chain in time order, for the video and the pitch column
+            const int hc = tr[i].col;
+            std::vector<PostMember> vid, pit;
+            for (int m = (int)i; m >= 0; m = tr[m].succ) {
+                const PostTrack& M = tr[m];
+                vid.push_back(PostMember{M.first, M.last, M.col, M.pair});
+                if (keep[M.col - 1]) pit.push_back(PostMember{M.first, M.last, M.col - 1, M.pair >= 0 ? M.pair - 1 : -1});
+                desc[M.col].out = desc[M.col - 1].out = -1;
+            }
+            if (vid.size() > (size_t)PS_MAX_CHAIN)
+                fail(EAGLE_E_STATE, "post-processor: a chain of %zu tracks (each holds 1 %% of the rows and their spans are disjoint: at most %d)", vid.size(), PS_MAX_CHAIN);
+            desc[hc].out = 0; chain[hc] = vid;
+            chain[hc - 1] = pit;
+            if (!pit.empty()) desc[hc - 1].out = 0;
+            if (vid.size() > 1 && t->has_team && tr[i].team >= 0 && team_of(t, tr[i].id) < 0) {      // the head inherits the chain's team
+                size_t k = 0;                                       // (an entry below 0 is no team: replaced)
+                while (k < t->team_ids.size() && t->team_ids[k] != tr[i].id) ++k;
+                if (k < t->team_ids.size()) t->team_vals[k] = tr[i].team;
+                else { t->team_ids.push_back(tr[i].id); t->team_vals.push_back(tr[i].team); }
+            }
+        }
+    }
+    int ncols = 0;
+    std::vector<PostMember> members;
+    for (int c = 0; c < nraw; ++c)
+        if (desc[c].out >= 0) {
+            desc[c].out = ncols++; t->columns.push_back(raw_cols[c]);
+            desc[c].mem0 = (int32_t)members.size(); desc[c].nmem = (int32_t)chain[c].size();
+            members.insert(members.end(), chain[c].begin(), chain[c].end());
+        }
+    t->cols = ncols;
     // 4. the memory the call needs, against the budget: refused here, never inside a launch
     HIP_CHECK(hipSetDevice(h->cfg.device));
-    const double cell = 16.0, need = ((double)nraw + (double)ncols) * (double)rows * cell + (double)ent.size() * 20.0 + (double)nraw * 40.0;
+    const double cell = 16.0, need = ((double)nraw + (double)ncols) * (double)rows * cell + (double)ent.size() * 20.0 + (double)nraw * 40.0 + (double)members.size() * 16.0;
     double budget = (double)p->max_bytes;
     if (p->max_bytes <= 0) {
         size_t free_b = 0, total_b = 0;
@@ -421,6 +561,7 @@ static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, con
         const int32_t* d_row = dev_upload(owned, ent_row, s);
         const double2* d_xy = dev_upload(owned, ent_xy, s);
         const PostCol* d_desc = dev_upload(owned, desc, s);
+        const PostMember* d_mem = dev_upload(owned, members, s);
         std::vector<PostStat> stats(nraw);
         PostStat* d_stats = dev_upload(owned, stats, s);
         const int chunks = (rows + SC_ROWS - 1) / SC_ROWS;
@@ -430,8 +571,8 @@ static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, con
             HIP_CHECK(hipGetLastError());
         });
         timed_launch(h, "post_series", 2.0 * table_b + out_b, s, [&] {
-            hipLaunchKernelGGL(post_series_kernel, dim3((unsigned)nraw), dim3(PS_THREADS), (size_t)nblk * 2 * sizeof(int), s, d_raw, (double2*)t->d_values, d_desc, d_stats,
-                               rows, nblk, p->smooth ? 1 : 0);
+            hipLaunchKernelGGL(post_series_kernel, dim3((unsigned)nraw), dim3(PS_THREADS), (size_t)nblk * 2 * sizeof(int), s, d_raw, (double2*)t->d_values, d_desc, d_mem,
+                               d_stats, rows, nblk, p->smooth ? 1 : 0);
             HIP_CHECK(hipGetLastError());
         });
         HIP_CHECK(hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(PostStat), hipMemcpyDeviceToHost, s));
@@ -479,6 +620,8 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
     if (!p || n < 0 || (n > 0 && !recs)) fail(EAGLE_E_INVALID, "eagle_postprocess: bad argument (params %p, %d records at %p)", (const void*)p, n, (const void*)recs);
     if (p->filter_ball != 0)
         fail(EAGLE_E_INVALID, "eagle_postprocess: filter_ball = %d is refused: the reference's filter_ball_detections=True needs cv2's Kalman gain, which is not restated", p->filter_ball);
+    if (p->merge_ids != 0 && p->merge_ids != 1)
+        fail(EAGLE_E_INVALID, "eagle_postprocess: merge_ids = %d is refused: 0 keeps the reference's table (its id merge never merges), 1 stitches fragmented ids", p->merge_ids);
     if (p->fps <= 0 || p->frame_w <= 0) fail(EAGLE_E_INVALID, "eagle_postprocess: fps %d and frame_w %d must be positive", p->fps, p->frame_w);
     if (p->n_team < 0 || (p->n_team > 0 && p->team_ids && !p->team_vals)) fail(EAGLE_E_INVALID, "eagle_postprocess: bad team map (%d entries)", p->n_team);
     if (p->max_bytes < 0) fail(EAGLE_E_INVALID, "eagle_postprocess: max_bytes %lld is negative", (long long)p->max_bytes);
@@ -602,6 +745,14 @@ int eagle_post_values(EaglePostTable* t, double* values)
     fetch_host(t);
     std::copy(t->host.begin(), t->host.end(), values);
     API_END(h)
+}
+
+int eagle_post_merges(const EaglePostTable* t, EaglePostMerge* out, int cap, int* n)
+{
+    if (!t || !n || cap < 0 || (cap > 0 && !out)) return EAGLE_E_INVALID;
+    *n = (int)t->merges.size();
+    std::copy(t->merges.begin(), t->merges.begin() + std::min<size_t>(cap, t->merges.size()), out);
+    return EAGLE_OK;
 }
 
 int eagle_post_device_values(const EaglePostTable* t, const double** d_values)

@@ -273,6 +273,7 @@ struct EaglePostTable {
     std::vector<EaglePostColumn> columns;
     std::vector<int32_t> team_ids, team_vals;
     bool has_team = false;
+    std::vector<EaglePostMerge> merges;  // merge_ids = 1: the accepted links, in acceptance order
     double* d_values = nullptr;          // [cols][rows][2], resident until eagle_post_free
     std::vector<double> host;            // the same on the host, fetched on first use (getters, overlays)
     bool host_ok = false;

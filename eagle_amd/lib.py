@@ -87,6 +87,8 @@ class EagleControlParams(C.Structure):
 POST_PLAYER, POST_GOALKEEPER, POST_BALL, POST_BOUNDARY = 0, 1, 2, 3    # include/eagle.h EAGLE_POST_*
 POST_NO_BALL = 1                                                       # ... flag: fewer than two ball sightings
 POSTCOL_DTYPE = np.dtype([("kind", "<i4"), ("id", "<i4"), ("video", "<i4"), ("reserved", "<i4")])      # EaglePostColumn
+POSTMERGE_DTYPE = np.dtype([("kind", "<i4"), ("from_id", "<i4"), ("to_id", "<i4"), ("head_id", "<i4"), ("gap_frames", "<i4"), ("team", "<i4"),
+                            ("dist", "<f8")])                                                          # EaglePostMerge
 E_INVALID = -1
 
 
@@ -205,6 +207,7 @@ def load():
     L.eagle_post_layout.argtypes = [vp, vp, vp]
     L.eagle_post_values.argtypes = [vp, vp]
     L.eagle_post_device_values.argtypes = [vp, C.POINTER(vp)]
+    L.eagle_post_merges.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_overlay_from_table.argtypes = [vp, i32, vp, vp, i32, C.POINTER(i32)]
     mp = C.POINTER(EagleMinimapParams)
     L.eagle_minimap_size.argtypes = [mp, C.POINTER(i32), C.POINTER(i32)]
@@ -235,7 +238,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
            "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate",
            "eagle_annotate_frames_prims", "eagle_postprocess", "eagle_post_free", "eagle_post_shape", "eagle_post_layout", "eagle_post_values",
-           "eagle_post_device_values", "eagle_overlay_from_table", "eagle_minimap_size", "eagle_minimap_device_frames", "eagle_minimap_frames",
+           "eagle_post_device_values", "eagle_post_merges", "eagle_overlay_from_table", "eagle_minimap_size", "eagle_minimap_device_frames", "eagle_minimap_frames",
            "eagle_op_minimap", "eagle_post_velocities", "eagle_post_velocity_values", "eagle_post_device_velocity_values", "eagle_control_size",
            "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
            "eagle_op_minimap_control"]
@@ -530,12 +533,14 @@ class Handle:
         return out
 
     # --- the clip post-processor (include/eagle.h, eagle_postprocess) -------------------------------------------
-    def postprocess(self, recs, fps, frame_w, team_mapping=None, smooth=False, filter_ball=False, max_bytes=0):
-        """The records of a finished clip -> a PostTable (the reference's Processor.process_data table, built on the GPU and resident there)."""
+    def postprocess(self, recs, fps, frame_w, team_mapping=None, smooth=False, filter_ball=False, max_bytes=0, merge_ids=False):
+        """The records of a finished clip -> a PostTable (the reference's Processor.process_data table, built on the GPU and resident there).
+        merge_ids: stitch the fragments of one person under several tracker ids into one column (include/eagle.h; False, 0: the reference as written,
+        which never merges); the table's ``merges`` list what was joined and its ``team_mapping`` gains the teams the heads inherit."""
         recs = np.ascontiguousarray(recs, RESULT_DTYPE).reshape(-1)
         ids, vals, nt = _team_arrays(team_mapping)
         p = EaglePostParams(int(fps), int(frame_w), int(bool(smooth)), int(filter_ball), None if ids is None else ids.ctypes.data, None if vals is None else vals.ctypes.data,
-                            nt, 0, int(max_bytes))
+                            nt, int(merge_ids), int(max_bytes))                 # (the struct's ``reserved`` field carries merge_ids)
         t = C.c_void_p()
         self._check(self.L.eagle_postprocess(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), C.byref(p), C.byref(t)), "postprocess")
         return PostTable(self, t, team_mapping)
@@ -746,7 +751,7 @@ BOUNDARY_NAMES = ("Bottom_Left", "Top_Left", "Top_Right", "Bottom_Right")
 
 class PostTable:
     """A processed clip table (EaglePostTable): ``rows`` kept frame numbers, ``columns`` (POSTCOL_DTYPE, table order) and their reference ``names``,
-    ``flags``; ``values`` copies the table to the host once: float64 [columns][rows][2], NaN = missing.  close() frees the device memory."""
+    ``flags``, ``merges`` (the links of the id merge, one dict of POSTMERGE_DTYPE's fields each), ``team_mapping``; ``values`` copies the table to the host once: float64 [columns][rows][2], NaN = missing.  close() frees the device memory."""
 
     def __init__(self, handle, ptr, team_mapping=None):
         self.handle, self._t, self.team_mapping = handle, ptr, team_mapping
@@ -761,6 +766,17 @@ class PostTable:
                       ("Ball" if k["kind"] == POST_BALL else f"{'Player' if k['kind'] == POST_PLAYER else 'Goalkeeper'}_{int(k['id'])}") + ("_video" if k["video"] else "")
                       for k in self.columns]
         self._values = None
+        n = C.c_int(0)
+        L.eagle_post_merges(ptr, None, 0, C.byref(n))
+        m = np.zeros(n.value, POSTMERGE_DTYPE)
+        L.eagle_post_merges(ptr, m.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+        self.merges = [{k: (float(e[k]) if k == "dist" else int(e[k])) for k in POSTMERGE_DTYPE.names} for e in m]
+        if self.merges and team_mapping is not None:        # the heads' inherited teams (the library's own copy of the mapping holds them too)
+            self.team_mapping = dict(team_mapping)
+            heads = {(e["kind"], e["head_id"]): e["team"] for e in self.merges if e["team"] >= 0}
+            for k in self.columns:                          # in table order, as the library adds them
+                if k["video"] and (int(k["kind"]), int(k["id"])) in heads and self.team_mapping.get(int(k["id"]), -1) < 0:
+                    self.team_mapping[int(k["id"])] = heads[(int(k["kind"]), int(k["id"]))]            # (an entry below 0 is no team: replaced)
 
     @property
     def values(self):

@@ -35,17 +35,19 @@ class Processor:
         finally:
             self.model.handle.free(d)
 
-    def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr"):
+    def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False):
         """The reference post-processor's ``process_data`` (eagle/processor.py:73-87) for a clip and its ``get_coordinates`` output (or raw
         records): the team mapping (get_team_mapping above), then the interpolated, goalkeeper-folded, optionally smoothed table, built on the GPU
-        (eagle_amd/postprocess.py).  -> (table, team_mapping); postprocess.raw_data_rows / format_data turn the table into main.py's two JSON files."""
+        (eagle_amd/postprocess.py).  -> (table, team_mapping); postprocess.raw_data_rows / format_data turn the table into main.py's two JSON files.
+        merge_ids: stitch fragmented tracker ids (postprocess.process_data); the returned mapping then includes the teams the merged ids inherit."""
         from . import postprocess
         coords = coords_or_records
         if not isinstance(coords, dict):
             coords = {i: records.to_reference_dict(r, i, fps) for i, r in enumerate(np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1))}
         recs = self.model._records_of(coords_or_records)
         team_mapping = self.get_team_mapping(frames, coords, pixel_format) if len(recs) else {}
-        return postprocess.process_data(self.model.handle, recs, fps, self.model.handle.cfg.frame_w, team_mapping, smooth=smooth), team_mapping
+        table = postprocess.process_data(self.model.handle, recs, fps, self.model.handle.cfg.frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids)
+        return table, table.team_mapping if merge_ids else team_mapping
 
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The annotated frames of a clip (the reference's annotated video, main.py:43-81), drawn on the GPU: see CoordinateModel.annotate.

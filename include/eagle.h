@@ -258,7 +258,17 @@ int eagle_annotate_frames_prims(EagleHandle* h, const void* d_bgr, int n, const 
  * inside its valid span; with `smooth` every other row, from the first, replaced by the interpolation of its neighbours.  The arithmetic is pandas'
  * (np.interp in float64: slope * (x - x0) + y0, no contraction), pinned bit for bit by tests/golden/post_golden.json through tests/post_ref.py.  The
  * reference's pairwise id merge (proc.py:218-319) never merges as written (its overlap test holds for any two non-empty columns) and is reproduced
- * as that: nothing.  Host C++ discovers columns and walks the ball; two launches (post.hip) on the handle's main stream build the table, which stays
+ * as that by default: nothing.  merge_ids = 1 runs the merge it was meant to be, as a rule of this library's own (contract: tests/stitch_ref.py), at
+ * the reference's place: after the 1 % filter, the ball fill and the goalkeeper fold, before interpolation and smoothing.  A track is a person video
+ * column after the fold, first / last its first and last present row.  A link a -> b is admissible when both are of one kind, last(a) < first(b), the
+ * gap in FRAME numbers g = frame[first(b)] - frame[last(a)] is at most (int)(fps * 1.1), the video points p_last(a) and p_first(b) lie at most 10 g
+ * pixels apart (sqrt(dx*dx + dy*dy) in float64, no contraction) and the two ids do not have different teams in the mapping.  The admissible links
+ * are walked ascending by (distance, g, column of a, column of b); one is accepted when a has no successor, b no predecessor and the teams known
+ * for the two chains do not differ.  A chain becomes one pitch and one video column under the id, kind and position of its head (the member without
+ * predecessor; a pitch column exists when a member has one); a cell holds the value of the member present in that row; the other members' columns
+ * leave the table; interpolation fills the gaps between fragments linearly.  A head without a team entry inherits the team known for its chain
+ * (the table's mapping grows: eagle_overlay_from_table, the minimap and pitch control colour the whole track; an entry below 0 counts as none and is replaced).
+ * eagle_post_merges lists the accepted links.  Host C++ discovers columns and walks the ball; two launches (post.hip) on the handle's main stream build the table, which stays
  * resident in HBM until eagle_post_free.  The handle's records, staging buffers and graphs are not involved.
  * Where the reference raises or returns garbage, the library is defined instead:
  *   - fewer than two ball sightings (the reference hands its candidate lists on and fails later): Ball / Ball_video are all NaN, EAGLE_POST_NO_BALL is set;
@@ -278,14 +288,14 @@ int eagle_annotate_frames_prims(EagleHandle* h, const void* d_bgr, int n, const 
 #define EAGLE_POST_NO_BALL 1       /* flag: fewer than two ball sightings, the ball columns are all NaN */
 typedef struct EaglePostTable EaglePostTable;
 typedef struct EaglePostParams {
-    int32_t fps;                   /* > 0 (the reference's merge thresholds derive from it; its merge never fires) */
+    int32_t fps;                   /* > 0 (the id merge's temporal threshold is (int)(fps * 1.1) frames) */
     int32_t frame_w;               /* > 0 (the refused ball filter's threshold, 0.1 * width) */
     int32_t smooth;                /* process_data(smooth=...) */
     int32_t filter_ball;           /* must be 0 */
     const int32_t* team_ids;       /* Processor.get_team_mapping as two arrays of n_team entries: kept with the table for eagle_overlay_from_table; */
     const int32_t* team_vals;      /* team_ids NULL: no mapping (players drawn white) */
     int32_t n_team;
-    int32_t reserved;
+    int32_t merge_ids;             /* 0: the reference as written (no id ever merges); 1: stitch fragmented ids (rule above); else EAGLE_E_INVALID */
     int64_t max_bytes;             /* device-memory budget of the call, 0 = nine tenths of what is free */
 } EaglePostParams;
 typedef struct EaglePostColumn { int32_t kind /* EAGLE_POST_* */, id, video /* 1: the "_video" column */, reserved; } EaglePostColumn;
@@ -295,6 +305,10 @@ int eagle_post_shape(const EaglePostTable* t, int32_t* rows, int32_t* cols, int3
 int eagle_post_layout(const EaglePostTable* t, int32_t* frames /* rows: kept frame numbers */, EaglePostColumn* columns /* cols, table order */);
 int eagle_post_values(EaglePostTable* t, double* values /* [cols][rows][2] = x, y; NaN = missing */);        /* copies the table to the host */
 int eagle_post_device_values(const EaglePostTable* t, const double** d_values);                              /* the same layout, in HBM */
+/* The links the id merge accepted, in acceptance order: ids from_id -> to_id of `kind` were joined over gap_frames frames and dist pixels; head_id and
+ * team (-1: unknown) are those of the finished chain.  *n = their number (0 for a table built with merge_ids = 0); at most cap are written. */
+typedef struct EaglePostMerge { int32_t kind /* EAGLE_POST_PLAYER | _GOALKEEPER */, from_id, to_id, head_id, gap_frames, team; double dist; } EaglePostMerge;
+int eagle_post_merges(const EaglePostTable* t, EaglePostMerge* out, int cap, int* n);
 /* The overlay main.py:44-77 draws for processed row `row` (no launch; the table is copied to the host once): per video column in table order the
  * foot arc and id at (int(x), int(y)) — goalkeepers green, team 0 red, other teams blue, players without a team skipped (white without a mapping) —
  * the marker above the interpolated ball, then, with rec != NULL, that record's key-point discs (the three sources of eagle_overlay_from_record). */
