@@ -353,4 +353,158 @@ int eagle_op_conv2d_argmax(int device, int precision, const float* x, int n, int
     API_END(hh)
 }
 
+// ---- the OSNet (ReID) kernels of reid.hip one launch at a time (tests/test_gpu_reid_ops.py) ------------------------------------------------
+// Every activation operand is a slice view: `c` channels at channel `off` of a buffer with `cs` floats per pixel.  Whatever lies outside the
+// slice holds EAGLE_OP_SENTINEL_BITS (a quiet NaN) when the kernel starts, and output buffers come back whole: a read outside an input slice
+// shows as a NaN in the result, a write outside an output slice as an overwritten sentinel.
+static void reid_fill_sentinel(std::vector<float>& t)
+{
+    const uint32_t bits = EAGLE_OP_SENTINEL_BITS;
+    float s; memcpy(&s, &bits, 4);
+    std::fill(t.begin(), t.end(), s);
+}
+static TView reid_view(Net& net, const char* what, const float* src, int n, int h, int w, int c, int cs, int off)
+{
+    if (n < 1 || h < 1 || w < 1 || c < 4 || c % 4 || cs % 4 || off % 4 || off < 0 || cs < off + c)
+        fail(EAGLE_E_INVALID, "%s: [%d, %d, %d, %d] at channel %d of %d: sizes >= 1; c, cs, off multiples of 4; off + c <= cs", what, n, h, w, c, off, cs);
+    TView v; v.n = n; v.h = h; v.w = w; v.c = c; v.cs = cs; v.off = off; v.f32 = 1;
+    const size_t px = (size_t)n * h * w;
+    std::vector<float> t(px * cs);
+    reid_fill_sentinel(t);
+    if (src) for (size_t p = 0; p < px; ++p) for (int k = 0; k < c; ++k) t[p * cs + off + k] = src[p * c + k];
+    v.p = net.upload(t.data(), t.size() * 4);
+    return v;
+}
+static float* reid_flat(Net& net, size_t count)
+{
+    std::vector<float> t(count);
+    reid_fill_sentinel(t);
+    return (float*)net.upload(t.data(), t.size() * 4);
+}
+static void reid_whole(const TView& v, float* dst) { HIP_CHECK(hipMemcpy(dst, v.p, (size_t)v.n * v.h * v.w * v.cs * 4, hipMemcpyDeviceToHost)); }
+
+int eagle_op_reid_crop(int device, const uint8_t* bgr, int nf, int fh, int fw, const EagleCrop* crops, int n, int oh, int ow, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!bgr || !crops || !y || nf < 1 || fh < 1 || fw < 1) fail(EAGLE_E_INVALID, "eagle_op_reid_crop: bad argument");
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const uint8_t* d = (const uint8_t*)net.upload(bgr, (size_t)nf * fh * fw * 3);
+    const EagleCrop* dc = (const EagleCrop*)net.upload(crops, sizeof(EagleCrop) * (size_t)std::max(n, 1));
+    const TView o = reid_view(net, "eagle_op_reid_crop: y", nullptr, n, oh, ow, 4, y_cs, y_off);
+    reid_crop_launch(d, nf, fh, fw, dc, n, o, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    reid_whole(o, y);
+    API_END(hh)
+}
+
+int eagle_op_reid_conv7(int device, const float* x, int n, int h, int w, int x_cs, int x_off, const float* wt, const float* b, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!x || !wt || !b || !y) fail(EAGLE_E_INVALID, "eagle_op_reid_conv7: null argument");
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const TView xv = reid_view(net, "eagle_op_reid_conv7: x", x, n, h, w, 4, x_cs, x_off);
+    const TView yv = reid_view(net, "eagle_op_reid_conv7: y", nullptr, n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 16, y_cs, y_off);
+    const float* dw = (const float*)net.upload(wt, 7 * 7 * 3 * 16 * 4);
+    const float* db = (const float*)net.upload(b, 16 * 4);
+    reid_conv7_launch(xv, dw, db, yv, n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    reid_whole(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_reid_maxpool3s2(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!x || !y) fail(EAGLE_E_INVALID, "eagle_op_reid_maxpool3s2: null argument");
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const TView xv = reid_view(net, "eagle_op_reid_maxpool3s2: x", x, n, h, w, c, x_cs, x_off);
+    const TView yv = reid_view(net, "eagle_op_reid_maxpool3s2: y", nullptr, n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c, y_cs, y_off);
+    reid_maxpool3s2_launch(xv, yv, n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    reid_whole(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_reid_avgpool2(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!x || !y) fail(EAGLE_E_INVALID, "eagle_op_reid_avgpool2: null argument");
+    if (h < 2 || w < 2) fail(EAGLE_E_INVALID, "eagle_op_reid_avgpool2: a %d x %d map has no 2 x 2 window", h, w);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const TView xv = reid_view(net, "eagle_op_reid_avgpool2: x", x, n, h, w, c, x_cs, x_off);
+    const TView yv = reid_view(net, "eagle_op_reid_avgpool2: y", nullptr, n, h / 2, w / 2, c, y_cs, y_off);
+    reid_avgpool2_launch(xv, yv, n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    reid_whole(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_reid_dw3(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, const float* wt, const float* b, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!x || !wt || !b || !y) fail(EAGLE_E_INVALID, "eagle_op_reid_dw3: null argument");
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const TView xv = reid_view(net, "eagle_op_reid_dw3: x", x, n, h, w, c, x_cs, x_off);
+    const TView yv = reid_view(net, "eagle_op_reid_dw3: y", nullptr, n, h, w, c, y_cs, y_off);
+    const float* dw = (const float*)net.upload(wt, (size_t)9 * c * 4);
+    const float* db = (const float*)net.upload(b, (size_t)c * 4);
+    reid_dw3_launch(xv, dw, db, yv, n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    reid_whole(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_reid_gate(int device, const float* const* streams, int n, int h, int w, int c, int x_cs, int x_off, const float* w1, const float* b1,
+                       const float* w2, const float* b2, int c_real, int r, int y_cs, int y_off, float* g, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!streams || !streams[0] || !streams[1] || !streams[2] || !streams[3] || !w1 || !b1 || !w2 || !b2 || !g || !y) fail(EAGLE_E_INVALID, "eagle_op_reid_gate: null argument");
+    if (c < 16 || c > 128 || 256 % c || c_real < 1 || c_real > c || r < 1 || r > 8)
+        fail(EAGLE_E_INVALID, "eagle_op_reid_gate: c in {16, 32, 64, 128}, 1 <= c_real <= c and 1 <= r <= 8 required (c %d, c_real %d, r %d)", c, c_real, r);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    TView sv[4];
+    for (int k = 0; k < 4; ++k) sv[k] = reid_view(net, "eagle_op_reid_gate: stream", streams[k], n, h, w, c, x_cs, x_off);
+    const TView yv = reid_view(net, "eagle_op_reid_gate: y", nullptr, n, h, w, c, y_cs, y_off);
+    const float* d1 = (const float*)net.upload(w1, (size_t)r * c_real * 4);
+    const float* e1 = (const float*)net.upload(b1, (size_t)r * 4);
+    const float* d2 = (const float*)net.upload(w2, (size_t)c_real * r * 4);
+    const float* e2 = (const float*)net.upload(b2, (size_t)c_real * 4);
+    float* dg = reid_flat(net, (size_t)n * 4 * c);
+    reid_gate_launch(sv, d1, e1, d2, e2, c_real, r, dg, yv, n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(g, dg, (size_t)n * 4 * c * 4, hipMemcpyDeviceToHost));
+    reid_whole(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_reid_head(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, const float* wt, const float* b, int dim, float* feats)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!x || !wt || !b || !feats || dim < 1) fail(EAGLE_E_INVALID, "eagle_op_reid_head: bad argument");
+    if (c < 16 || c > 128 || 256 % c) fail(EAGLE_E_INVALID, "eagle_op_reid_head: c in {16, 32, 64, 128} required (c %d)", c);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const TView xv = reid_view(net, "eagle_op_reid_head: x", x, n, h, w, c, x_cs, x_off);
+    const float* dw = (const float*)net.upload(wt, (size_t)dim * c * 4);
+    const float* db = (const float*)net.upload(b, (size_t)dim * 4);
+    float* df = reid_flat(net, (size_t)n * dim);
+    reid_head_launch(xv, dw, db, df, dim, n, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(feats, df, (size_t)n * dim * 4, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
 }  // extern "C"

@@ -225,6 +225,13 @@ def load():
     L.eagle_op_velocities.argtypes = [i32, vp, vp, i32, i32, kp, vp]
     L.eagle_op_control.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, cp, i32, i32, vp, vp]
     L.eagle_op_minimap_control.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, cp, i32, i32, i32, yl, vp]
+    L.eagle_op_reid_crop.argtypes = [i32, u8p, i32, i32, i32, vp, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_reid_conv7.argtypes = [i32, fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
+    L.eagle_op_reid_maxpool3s2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_reid_avgpool2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_reid_dw3.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
+    L.eagle_op_reid_gate.argtypes = [i32, C.POINTER(fp), i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, i32, i32, i32, fp, fp]
+    L.eagle_op_reid_head.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, fp, fp, i32, fp]
     _lib = L
     return L
 
@@ -241,7 +248,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_device_values", "eagle_post_merges", "eagle_overlay_from_table", "eagle_minimap_size", "eagle_minimap_device_frames", "eagle_minimap_frames",
            "eagle_op_minimap", "eagle_post_velocities", "eagle_post_velocity_values", "eagle_post_device_velocity_values", "eagle_control_size",
            "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
-           "eagle_op_minimap_control"]
+           "eagle_op_minimap_control", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_op_reid_gate", "eagle_op_reid_head"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -1278,3 +1286,97 @@ def op_minimap_control(values, velocities, columns, team_mapping, params, contro
     if lay is None:
         return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
     return out
+
+
+# --- the OSNet (ReID) kernels one launch at a time (include/eagle.h eagle_op_reid_*; csrc/reid.hip) ------------------------------------------
+# Activations go in dense ([n, h, w, c], c the kernel's padded channel count) and are placed at channel ``off`` of a buffer with ``cs`` floats per
+# pixel; outputs come back whole ([n, ho, wo, cs]) with REID_OP_SENTINEL (a quiet NaN, compare through .view(np.uint32)) wherever the kernel did not write.
+REID_OP_SENTINEL = 0x7FC5E171
+
+
+def _reid_check(L, rc, what):
+    if rc:
+        raise EagleError(f"{what} failed ({rc}): {L.eagle_last_error(None).decode()}")
+
+
+def op_reid_crop(frames, crops, out_hw, y_cs=4, y_off=0, device=0):
+    """reid_crop_kernel: BGR uint8 frames [nf, fh, fw, 3], crops int32 [n, 5] (frame, x1, y1, x2, y2) -> float32 [n, oh, ow, y_cs]."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8); crops = np.ascontiguousarray(crops, np.int32).reshape(-1, 5)
+    nf, fh, fw, _ = frames.shape
+    y = np.empty((len(crops), out_hw[0], out_hw[1], y_cs), np.float32)
+    _reid_check(L, L.eagle_op_reid_crop(device, frames.ctypes.data_as(C.POINTER(C.c_uint8)), nf, fh, fw, crops.ctypes.data_as(C.c_void_p), len(crops), out_hw[0], out_hw[1],
+                                        y_cs, y_off, _fp(y)), "eagle_op_reid_crop")
+    return y
+
+
+def op_reid_conv7(x, w, b, x_cs=4, x_off=0, y_cs=16, y_off=0, device=0):
+    """reid_conv7_kernel: x [n, h, w, 4], w [7, 7, 3, 16] and b [16] (BatchNorm folded) -> [n, (h-1)//2+1, (w-1)//2+1, y_cs]."""
+    L = load()
+    x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32); b = np.ascontiguousarray(b, np.float32)
+    n, h, wd, c = x.shape
+    assert c == 4 and w.shape == (7, 7, 3, 16) and b.shape == (16,)
+    y = np.empty((n, (h - 1) // 2 + 1, (wd - 1) // 2 + 1, y_cs), np.float32)
+    _reid_check(L, L.eagle_op_reid_conv7(device, _fp(x), n, h, wd, x_cs, x_off, _fp(w), _fp(b), y_cs, y_off, _fp(y)), "eagle_op_reid_conv7")
+    return y
+
+
+def _op_reid_pool(name, x, out_hw, x_cs, x_off, y_cs, y_off, device):
+    L = load()
+    x = np.ascontiguousarray(x, np.float32)
+    n, h, w, c = x.shape
+    x_cs = c if x_cs is None else x_cs; y_cs = c if y_cs is None else y_cs
+    y = np.empty((n, out_hw[0], out_hw[1], y_cs), np.float32)
+    _reid_check(L, getattr(L, name)(device, _fp(x), n, h, w, c, x_cs, x_off, y_cs, y_off, _fp(y)), name)
+    return y
+
+
+def op_reid_maxpool3s2(x, x_cs=None, x_off=0, y_cs=None, y_off=0, device=0):
+    """MaxPool2d(3, 2, 1) on x [n, h, w, c] -> [n, (h-1)//2+1, (w-1)//2+1, y_cs]."""
+    return _op_reid_pool("eagle_op_reid_maxpool3s2", x, ((x.shape[1] - 1) // 2 + 1, (x.shape[2] - 1) // 2 + 1), x_cs, x_off, y_cs, y_off, device)
+
+
+def op_reid_avgpool2(x, x_cs=None, x_off=0, y_cs=None, y_off=0, device=0):
+    """AvgPool2d(2, 2) on x [n, h, w, c] -> [n, h//2, w//2, y_cs]; a map without a 2 x 2 window is an EagleError."""
+    return _op_reid_pool("eagle_op_reid_avgpool2", x, (x.shape[1] // 2, x.shape[2] // 2), x_cs, x_off, y_cs, y_off, device)
+
+
+def op_reid_dw3(x, w, b, x_cs=None, x_off=0, y_cs=None, y_off=0, device=0):
+    """depthwise 3 x 3 + bias + ReLU: x [n, h, w, c], w [9, c] and b [c] (BatchNorm folded) -> [n, h, w, y_cs]."""
+    L = load()
+    x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32); b = np.ascontiguousarray(b, np.float32)
+    n, h, wd, c = x.shape
+    assert w.shape == (9, c) and b.shape == (c,)
+    x_cs = c if x_cs is None else x_cs; y_cs = c if y_cs is None else y_cs
+    y = np.empty((n, h, wd, y_cs), np.float32)
+    _reid_check(L, L.eagle_op_reid_dw3(device, _fp(x), n, h, wd, c, x_cs, x_off, _fp(w), _fp(b), y_cs, y_off, _fp(y)), "eagle_op_reid_dw3")
+    return y
+
+
+def op_reid_gate(streams, w1, b1, w2, b2, x_cs=None, x_off=0, y_cs=None, y_off=0, device=0):
+    """reid_gate_kernel + the gated four-stream sum: streams 4 x [n, h, w, c], w1 [r, c_real], b1 [r], w2 [c_real, r], b2 [c_real]
+    -> (g [n, 4, c], y [n, h, w, y_cs])."""
+    L = load()
+    st = [np.ascontiguousarray(s, np.float32) for s in streams]
+    w1, b1, w2, b2 = (np.ascontiguousarray(a, np.float32) for a in (w1, b1, w2, b2))
+    n, h, wd, c = st[0].shape
+    r, c_real = w1.shape
+    assert len(st) == 4 and all(s.shape == st[0].shape for s in st) and b1.shape == (r,) and w2.shape == (c_real, r) and b2.shape == (c_real,)
+    x_cs = c if x_cs is None else x_cs; y_cs = c if y_cs is None else y_cs
+    g = np.empty((n, 4, c), np.float32); y = np.empty((n, h, wd, y_cs), np.float32)
+    ptrs = (C.POINTER(C.c_float) * 4)(*[_fp(s) for s in st])
+    _reid_check(L, L.eagle_op_reid_gate(device, ptrs, n, h, wd, c, x_cs, x_off, _fp(w1), _fp(b1), _fp(w2), _fp(b2), c_real, r, y_cs, y_off, _fp(g), _fp(y)), "eagle_op_reid_gate")
+    return g, y
+
+
+def op_reid_head(x, w, b, x_cs=None, x_off=0, device=0):
+    """reid_head_kernel: x [n, h, w, c], w [dim, c] and b [dim] (BatchNorm1d folded) -> relu(mean(x) @ w.T + b) [n, dim]."""
+    L = load()
+    x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32); b = np.ascontiguousarray(b, np.float32)
+    n, h, wd, c = x.shape
+    dim = len(b)
+    assert w.shape == (dim, c)
+    x_cs = c if x_cs is None else x_cs
+    feats = np.empty((n, dim), np.float32)
+    _reid_check(L, L.eagle_op_reid_head(device, _fp(x), n, h, wd, c, x_cs, x_off, _fp(w), _fp(b), dim, _fp(feats)), "eagle_op_reid_head")
+    return feats

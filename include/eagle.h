@@ -551,6 +551,27 @@ int eagle_op_post(int device, int n, int hm_h, int hm_w, int chunks, const float
 int eagle_op_conv2d_argmax(int device, int precision, const float* x, int n, int h, int w, int cin, const float* w_hwio, const float* bias, int cout, int ks, int stride,
                            float* logits, EagleArgmaxPart* parts, int* tiles, int* tile_h, int* tile_w);
 
+/* ---- the OSNet (ReID) kernels one launch at a time (reid.hip; tests/test_gpu_reid_ops.py).  Test surface only: each entry calls the network's own launch
+ * function.  Every activation operand is a slice view: its `c` channels start at channel `off` of a buffer with `cs` floats per pixel (c, cs, off multiples
+ * of 4, off + c <= cs).  Inputs are given dense ([n][h][w][c]) and placed into such a buffer by the entry; everything outside a slice holds the quiet NaN
+ * EAGLE_OP_SENTINEL_BITS when the kernel starts.  Output buffers come back WHOLE ([n][ho][wo][cs], sentinel included). */
+#define EAGLE_OP_SENTINEL_BITS 0x7fc5e171u
+/* crop + resize to oh x ow + RGB + ImageNet normalisation of crops[i] (EagleCrop) of nf dense BGR frames; 4 floats per pixel, the 4th 0; a rejected rectangle gives zeros */
+int eagle_op_reid_crop(int device, const uint8_t* bgr, int nf, int fh, int fw, const EagleCrop* crops, int n, int oh, int ow, int y_cs, int y_off, float* y);
+/* 7 x 7 / 2, pad 3, 3 -> 16 channels + bias + ReLU; x [n][h][w][4] (4th channel unused), wt [7][7][3][16] (BatchNorm folded), y [n][(h-1)/2+1][(w-1)/2+1][y_cs] */
+int eagle_op_reid_conv7(int device, const float* x, int n, int h, int w, int x_cs, int x_off, const float* wt, const float* b, int y_cs, int y_off, float* y);
+/* MaxPool2d(3, 2, 1): y [n][(h-1)/2+1][(w-1)/2+1][y_cs];  AvgPool2d(2, 2): y [n][h/2][w/2][y_cs], h, w >= 2 */
+int eagle_op_reid_maxpool3s2(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y);
+int eagle_op_reid_avgpool2(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y);
+/* depthwise 3 x 3, pad 1, + bias + ReLU; wt [9][c] (BatchNorm folded), b [c] */
+int eagle_op_reid_dw3(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, const float* wt, const float* b, int y_cs, int y_off, float* y);
+/* ChannelGate shared by four streams and their gated sum: streams[k] [n][h][w][c] (all in slices of the same cs / off), w1 [r][c_real], b1 [r], w2 [c_real][r],
+ * b2 [c_real]; g [n][4][c] (the gates; channels >= c_real are 0), y [n][h][w][y_cs] = sum_k streams[k] * g[., k, .] */
+int eagle_op_reid_gate(int device, const float* const* streams, int n, int h, int w, int c, int x_cs, int x_off, const float* w1, const float* b1,
+                       const float* w2, const float* b2, int c_real, int r, int y_cs, int y_off, float* g, float* y);
+/* global average -> Linear(c, dim) + bias -> ReLU; wt [dim][c] (BatchNorm1d folded), feats [n][dim] */
+int eagle_op_reid_head(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, const float* wt, const float* b, int dim, float* feats);
+
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
  * Keys: "lk_threads" (64 | 256), "lk_dbg" (1 trace, 2 LDS guard words, 4 end-of-level verification, 8 L1-bypassing loads), "lk_excl_lds" (bytes), "lk_trace", "lk_counters". */

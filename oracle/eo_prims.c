@@ -66,6 +66,8 @@ static inline float eo_q16(float v) { return _cvtsh_ss(_cvtss_sh(v, _MM_FROUND_T
 void eo_exp_array(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = eo_expf(x[i]); }
 void eo_sigmoid_array(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = eo_sigmoidf(x[i]); }
 void eo_round_f16_array(const float* x, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = eo_q16(x[i]); }
+/* y = fmaf(a, b, c), one rounding: the tests restate the kernels' spelled-out fmaf chains with it, step by step in the kernel's order (tests/reid_cases.py) */
+void eo_fmaf_array(const float* a, const float* b, const float* c, float* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = fmaf(a[i], b[i], c[i]); }
 
 /* ---------------------------------------------------------------------------------------------------- */
 /* convolution, NHWC, folded BN.  restates nn.Conv2d+BatchNorm2d(eval)+act (+residuals):                   */

@@ -81,6 +81,15 @@ def expf(x):
     return y
 
 
+def fmaf(a, b, c):
+    """elementwise float32 fmaf(a, b, c) (one rounding) of three arrays broadcast to a common shape"""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32))
+    a, b, c = _f32(a), _f32(b), _f32(c)
+    y = np.empty_like(a)
+    lib().eo_fmaf_array(_p(a), _p(b), _p(c), _p(y), C.c_int64(a.size))
+    return y
+
+
 def round_f16(x):
     x = _f32(x)
     y = np.empty_like(x)

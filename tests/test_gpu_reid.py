@@ -51,14 +51,18 @@ def test_reid_features_equal_the_torch_oracle():
     crops += [(0, 0, 0, 128, 256), (1, 100, 50, 356, 562), (0, 1200, 600, 1279, 719), (1, 5, 5, 7, 9)]      # identity / exact 2x / border / tiny crops
     h = _handle()
     d = h.upload(frames)
-    got = h.reid_features(d, len(frames), np.array(crops, np.int32))
+    got = h.reid_features(d, len(frames), np.array(crops + [(len(frames), 0, 0, 10, 10)], np.int32))      # ... and one the crop kernel rejects (frame == n_frames)
     h.free(d); h.close()
+    got, rejected = got[:-1], got[-1]
     ref = reid.embed(sd, np.stack([reid.prepare_crop(frames[c[0]], c[1:]) for c in crops]))
     assert got.shape == ref.shape == (len(crops), 512) and len(crops) > 64          # more than one pass of 64 crops
     scale = np.abs(ref).max()
     assert np.abs(got - ref).max() <= 2e-4 * scale, np.abs(got - ref).max() / scale
     gn, rn = got / np.linalg.norm(got, axis=1, keepdims=True), ref / np.linalg.norm(ref, axis=1, keepdims=True)
     assert np.abs((gn * rn).sum(1) - 1).max() < 1e-6                                 # cosine similarity GPU vs oracle per crop
+    assert np.isfinite(got[-4:]).all() and (np.abs(got[-4:]).max(1) > 0).all()       # the four hand-made crops
+    zero = reid.embed(sd, np.zeros((1, reid.CROP_H, reid.CROP_W, 3), np.float32))[0]   # a rejected crop is an all-zero input, not a skipped row
+    assert np.abs(rejected - zero).max() <= 2e-4 * scale, np.abs(rejected - zero).max() / scale
 
 
 def _crossing_clip(n=45):
