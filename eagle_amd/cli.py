@@ -17,7 +17,8 @@ the GPU (eagle_amd/postprocess.py) and writes ``raw_data.json`` (the table, one 
 interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  ``--merge-ids`` (with ``--processed``) stitches the fragments of one person
 under several tracker ids into one id first and lists the joins as ``merges`` in ``metadata.json``.  ``--minimap`` (with ``--processed``) writes ``minimap.y4m``: the processed table as
 a top-down video of the pitch at the clip's fps (eagle_amd/minimap.py; ``--minimap-voronoi`` tints the areas each team controls, ``--minimap-scale``
-sets the pixels per metre).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+sets the pixels per metre).  ``--possession`` (with ``--processed``) writes ``possession.json``: per kept frame who has the ball, the passes and
+turnovers, and what they add up to per id, per team and per pair of ids (eagle_amd/possession.py).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -98,7 +99,12 @@ def main(argv=None):
     ap.add_argument("--minimap-control", action="store_true", help="with --processed: write <out>/minimap.y4m with the pitch-control layer (not together with --minimap-voronoi)")
     ap.add_argument("--control-grid", type=int, default=None, choices=[1, 2, 4], metavar="R",
                     help="with --processed: also write <out>/control.npy (uint8 [rows, 68 R, 105 R]) and <out>/control_share.json, team 0's share of the pitch per row")
+    ap.add_argument("--possession", action="store_true",
+                    help="with --processed: also write <out>/possession.json, per kept frame who has the ball, the passes and turnovers, and per id / team what they add up "
+                         "to (most useful with --merge-ids)")
     a = ap.parse_args(argv)
+    if a.possession and not a.processed:
+        ap.error("--possession works on the processed table: it needs --processed")
     if a.minimap and not a.processed:
         ap.error("--minimap draws the processed table: it needs --processed")
     if (a.kinematics or a.minimap_control or a.control_grid) and not a.processed:
@@ -167,6 +173,10 @@ def main(argv=None):
                 np.save(os.path.join(a.out, "control.npy"), grids)
                 with open(os.path.join(a.out, "control_share.json"), "w") as f:
                     json.dump({"cells_per_metre": a.control_grid, "frames": [int(r) for r in table.rows], "team0_share": [float(v) for v in share]}, f)
+        if a.possession:
+            from . import possession as po
+            with open(os.path.join(a.out, "possession.json"), "w") as f:
+                json.dump(po.to_json(po.possession(model.handle, table, a.fps)), f)
         if a.minimap or a.minimap_control:
             from .minimap import minimap
             write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420",

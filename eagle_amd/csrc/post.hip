@@ -639,9 +639,10 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
 void eagle_post_free(EaglePostTable* t)
 {
     if (!t) return;
-    if (t->d_values || t->d_vel) (void)hipSetDevice(t->h->cfg.device);
+    if (t->d_values || t->d_vel || t->d_poss) (void)hipSetDevice(t->h->cfg.device);
     if (t->d_values) (void)hipFree(t->d_values);
     if (t->d_vel) (void)hipFree(t->d_vel);
+    if (t->d_poss) (void)hipFree(t->d_poss);
     delete t;
 }
 

@@ -283,6 +283,9 @@ struct EaglePostTable {
     bool host_vel_ok = false;
     bool has_control = false;            // eagle_minimap_set_control
     EagleControlParams control{};
+    void* d_poss = nullptr;              // possession (eagle_post_possession): dist [rows] f64 | cand [rows] i32 | owner [rows] i32, resident until eagle_post_free
+    bool has_poss = false;
+    std::vector<EaglePossessionEvent> events;
 };
 
 namespace eagle {

@@ -84,11 +84,20 @@ class EagleControlParams(C.Structure):
     _fields_ = [("cells_per_metre", C.c_int32), ("t_react", C.c_float), ("v_max", C.c_float), ("beta", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class EaglePossessionParams(C.Structure):
+    """include/eagle.h EaglePossessionParams: frames per second, rows to confirm a candidate, the largest frame step inside a segment, the radius (m)."""
+    _fields_ = [("fps", C.c_int32), ("min_hold", C.c_int32), ("max_gap", C.c_int32), ("reserved0", C.c_int32), ("radius", C.c_double), ("reserved", C.c_int64)]
+
+
 POST_PLAYER, POST_GOALKEEPER, POST_BALL, POST_BOUNDARY = 0, 1, 2, 3    # include/eagle.h EAGLE_POST_*
 POST_NO_BALL = 1                                                       # ... flag: fewer than two ball sightings
 POSTCOL_DTYPE = np.dtype([("kind", "<i4"), ("id", "<i4"), ("video", "<i4"), ("reserved", "<i4")])      # EaglePostColumn
 POSTMERGE_DTYPE = np.dtype([("kind", "<i4"), ("from_id", "<i4"), ("to_id", "<i4"), ("head_id", "<i4"), ("gap_frames", "<i4"), ("team", "<i4"),
                             ("dist", "<f8")])                                                          # EaglePostMerge
+EVENT_PASS, EVENT_TURNOVER, EVENT_UNKNOWN = 0, 1, 2                    # include/eagle.h EAGLE_EVENT_*
+EVENT_DTYPE = np.dtype([("row", "<i4"), ("from_col", "<i4"), ("to_col", "<i4"), ("release_row", "<i4"), ("receive_row", "<i4"), ("kind", "<i4"),
+                        ("reserved", "<i4", 2), ("x0", "<f8"), ("y0", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("length", "<f8"),
+                        ("duration", "<f8")])                                                          # EaglePossessionEvent (80 bytes)
 E_INVALID = -1
 
 
@@ -225,6 +234,12 @@ def load():
     L.eagle_op_velocities.argtypes = [i32, vp, vp, i32, i32, kp, vp]
     L.eagle_op_control.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, cp, i32, i32, vp, vp]
     L.eagle_op_minimap_control.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, cp, i32, i32, i32, yl, vp]
+    pp = C.POINTER(EaglePossessionParams)
+    L.eagle_post_possession.argtypes = [vp, vp, pp]
+    L.eagle_post_possession_values.argtypes = [vp, vp, vp, vp]
+    L.eagle_post_device_possession.argtypes = [vp, C.POINTER(vp)]
+    L.eagle_post_events.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_op_possession.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, pp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_op_reid_crop.argtypes = [i32, u8p, i32, i32, i32, vp, i32, i32, i32, i32, i32, fp]
     L.eagle_op_reid_conv7.argtypes = [i32, fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
     L.eagle_op_reid_maxpool3s2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -248,7 +263,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_device_values", "eagle_post_merges", "eagle_overlay_from_table", "eagle_minimap_size", "eagle_minimap_device_frames", "eagle_minimap_frames",
            "eagle_op_minimap", "eagle_post_velocities", "eagle_post_velocity_values", "eagle_post_device_velocity_values", "eagle_control_size",
            "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
-           "eagle_op_minimap_control", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_op_minimap_control", "eagle_post_possession", "eagle_post_possession_values", "eagle_post_device_possession", "eagle_post_events",
+           "eagle_op_possession", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -604,6 +620,27 @@ class Handle:
         self._check(self.L.eagle_control_grids(self._h, table._t, int(row0), int(n), C.byref(params), (out if out.size else keep).ctypes.data_as(C.c_void_p),
                                                (share if share.size else keep).ctypes.data_as(C.c_void_p)), "control_grids")
         return out, share
+
+    # --- ball possession and pass events (include/eagle.h, eagle_post_possession / eagle_post_events) ----------------
+    def possession(self, table, params):
+        """Candidate, owner and events of a PostTable of this handle, computed on the GPU and kept with the table (a second call replaces the first)
+        -> (cand int32 [rows], owner int32 [rows]: table columns or -1, dist float64 [rows], events EVENT_DTYPE in row order)."""
+        self._check(self.L.eagle_post_possession(self._h, table._t, C.byref(params)), "post_possession")
+        rows = len(table.rows)
+        cand, owner, dist = np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.float64)
+        keep = np.zeros(4, np.float64)
+        self._check(self.L.eagle_post_possession_values(table._t, _ptr(cand, keep), _ptr(owner, keep), _ptr(dist, keep)), "post_possession_values")
+        n = C.c_int(0)
+        self._check(self.L.eagle_post_events(table._t, None, 0, C.byref(n)), "post_events")
+        ev = np.zeros(n.value, EVENT_DTYPE)
+        self._check(self.L.eagle_post_events(table._t, _ptr(ev, keep), n.value, C.byref(n)), "post_events")
+        return cand, owner, dist, ev
+
+    def possession_device(self, table):
+        """owner int32 [rows] in HBM (None before the first possession call of the table)."""
+        d = C.c_void_p()
+        self._check(self.L.eagle_post_device_possession(table._t, C.byref(d)), "post_device_possession")
+        return d.value
 
     def minimap_set_control(self, table, params):
         """The parameters the minimap's ``control`` layer of this table is computed with (None: forget them)."""
@@ -1210,6 +1247,11 @@ def control_size(params):
     return gw.value, gh.value
 
 
+def possession_params(fps, radius=2.0, min_hold=2, max_gap=None):
+    """EaglePossessionParams; max_gap None: fps frames.  2 m, 2 rows and one second are conventional choices, not fitted to data."""
+    return EaglePossessionParams(int(fps), int(min_hold), int(fps if max_gap is None else max_gap), 0, float(radius), 0)
+
+
 def _table_args(what, values, columns):
     values = np.ascontiguousarray(values, np.float64)
     if not (isinstance(columns, np.ndarray) and columns.dtype == POSTCOL_DTYPE):
@@ -1258,6 +1300,28 @@ def op_control(values, velocities, columns, team_mapping, params, row0=0, n=None
     if rc:
         raise EagleError(f"eagle_op_control failed ({rc}): {L.eagle_last_error(None).decode()}")
     return out, share
+
+
+def op_possession(values, frames, columns, team_mapping, params, cap=None, device=0):
+    """The possession launches on a constructed table (include/eagle.h eagle_op_possession): values float64 [cols][rows][2], frames int32 [rows]
+    strictly ascending, columns POSTCOL_DTYPE (or (kind, id, video) tuples), team_mapping {id: team} or None -> (cand, owner, dist, events, n_events);
+    cap None: every event is fetched, else at most cap of the n_events."""
+    L = load()
+    values, columns = _table_args("op_possession", values, columns)
+    frames = np.ascontiguousarray(frames, np.int32)
+    cols, rows = values.shape[:2]
+    if len(frames) != rows:
+        raise EagleError("op_possession: one frame number per row")
+    ids, vals, nt = _team_arrays(team_mapping)
+    cand, owner, dist = np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.float64)
+    ev = np.zeros(max(rows - 1, 0) if cap is None else int(cap), EVENT_DTYPE)
+    keep = np.zeros(4, np.float64)
+    n = C.c_int(0)
+    rc = L.eagle_op_possession(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(params),
+                               _ptr(cand, keep), _ptr(owner, keep), _ptr(dist, keep), _ptr(ev, keep), len(ev), C.byref(n))
+    if rc:
+        raise EagleError(f"eagle_op_possession failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return cand, owner, dist, ev[: min(n.value, len(ev))].copy(), n.value
 
 
 def op_minimap_control(values, velocities, columns, team_mapping, params, control, row0=0, n=None, fmt="bgr", layout=None, out=None, device=0):

@@ -68,3 +68,8 @@ class Processor:
         """The pitch-control grids of a processed table with velocities (kinematics above) and team 0's area share per row: see eagle_amd/control.py."""
         from . import control as ct
         return ct.control(self.model.handle, table, cells_per_metre, t_react, v_max, beta, rows)
+
+    def possession(self, table, fps, radius=2.0, min_hold=2, max_gap=None):
+        """Who has the ball in each kept frame of a processed table, the passes and turnovers, and what they add up to: see eagle_amd/possession.py."""
+        from . import possession as po
+        return po.possession(self.model.handle, table, fps, radius, min_hold, max_gap)

@@ -395,6 +395,61 @@ int eagle_op_minimap_control(int device, const double* values, const double* vel
                              const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleControlParams* cp, int row0, int n, int out_format,
                              const EagleYuvLayout* out_layout, uint8_t* out);
 
+/* ---- ball possession and pass events: what a processed table says about the ball (own specification: tests/possession_ref.py defines every output bit) ----
+ * float64 without contraction.  The ball is the one Ball pitch column (video == 0), the candidates are the Player and Goalkeeper pitch columns; a cell is
+ * present when x and y are finite (the velocity rule).  Per row r:
+ *   CANDIDATE  ball[r]: the ball cell is present.  Of the present candidate cells the one with the smallest d2 = dx dx + dy dy (a tie: the earlier
+ *              column); cand[r] = its column when the ball is present and d2 <= radius radius (formed once, inclusive), else -1; dist[r] = sqrt(min d2),
+ *              NaN without a ball or without a present candidate.
+ *   RUNS       seg[r] = r == 0 || frames[r] - frames[r - 1] > max_gap || !ball[r];  head[r] = seg[r] || cand[r] < 0 || cand[r] != cand[r - 1];
+ *              headrow[r] = the greatest head row <= r;  run[r] = r - headrow[r] + 1 when cand[r] >= 0, else 0;  conf[r] = cand[r] >= 0 && run[r] >=
+ *              min_hold;  lastconf[r] = the greatest confirmed row <= r or -1;  lastseg[r] = the greatest segment start <= r.
+ *   OWNER      owner[r] = cand[lastconf[r]] when ball[r] && lastconf[r] >= 0 && lastconf[r] >= lastseg[r], else -1: a person owns the ball from the row
+ *              that confirms them (nearest and inside the radius for min_hold consecutive rows), keeps it while it flies or rolls until someone else is
+ *              confirmed; a hole in the frame numbers or a row without a ball forgets the owner.
+ *   EVENT      at r >= 1 when !seg[r], owner[r] >= 0, owner[r - 1] >= 0 and owner[r] != owner[r - 1]; events are reported in ascending row order.
+ * cand, owner, from_col and to_col are COLUMN indices of the table.  A column's team is the first entry of the mapping with its id (an entry below 0 or
+ * none: unknown, -1); without a mapping every event is EAGLE_EVENT_UNKNOWN.  A table without a ball column or flagged EAGLE_POST_NO_BALL gives -1 / NaN
+ * everywhere and no event.  Three launches (possession.hip) on the handle's main stream read the table where eagle_postprocess left it; the handle's
+ * records, staging buffers and graphs are not involved.  radius 2 m, min_hold 2 rows and max_gap = fps are conventional choices, not fitted to data.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, fps, max_gap or min_hold not positive, radius not finite, not positive or above
+ * 1024, more than one Ball pitch column, a column of unknown kind, frames of the operator entry that do not ascend strictly.  rows == 0 is success and
+ * writes nothing. */
+#define EAGLE_EVENT_PASS 0         /* both teams known and equal */
+#define EAGLE_EVENT_TURNOVER 1     /* both teams known and different */
+#define EAGLE_EVENT_UNKNOWN 2      /* a team is unknown */
+typedef struct EaglePossessionParams {
+    int32_t fps;                   /* > 0: frames per second of the frame numbers (event durations) */
+    int32_t min_hold;              /* >= 1: kept rows a candidate must stay nearest and inside the radius to be confirmed */
+    int32_t max_gap;               /* > 0: a step of more frames than this starts a new segment (a usual choice: fps) */
+    int32_t reserved0;
+    double radius;                 /* metres: > 0, finite, at most 1024 */
+    int64_t reserved;
+} EaglePossessionParams;
+typedef struct EaglePossessionEvent {
+    int32_t row;                   /* the row whose owner differs from the row before */
+    int32_t from_col, to_col;      /* owner[row - 1], owner[row] */
+    int32_t release_row;           /* lastconf[row - 1]: the old owner's last confirmed touch */
+    int32_t receive_row;           /* headrow[row]: the first row of the new owner's run (= row - min_hold + 1, > release_row) */
+    int32_t kind;                  /* EAGLE_EVENT_* */
+    int32_t reserved[2];
+    double x0, y0, x1, y1;         /* the ball cell at release_row and at receive_row */
+    double length;                 /* sqrt(dx dx + dy dy) of the two */
+    double duration;               /* (double)(frames[receive_row] - frames[release_row]) / (double)fps, seconds */
+} EaglePossessionEvent;            /* 80 bytes */
+/* The result is kept with the table until eagle_post_free and replaces an earlier one. */
+int eagle_post_possession(EagleHandle* h, EaglePostTable* t, const EaglePossessionParams* p);
+int eagle_post_possession_values(EaglePostTable* t, int32_t* cand, int32_t* owner, double* dist);            /* copies [rows] each to the host; any pointer may be NULL */
+int eagle_post_device_possession(const EaglePostTable* t, const int32_t** d_owner);                          /* owner[rows] in HBM; NULL before eagle_post_possession */
+/* *n = the number of events of the last eagle_post_possession (0 before it); at most cap are written, in row order. */
+int eagle_post_events(const EaglePostTable* t, EaglePossessionEvent* out, int cap, int* n);
+/* Operator entry (host buffers in / out, no handle) for constructed tables: values [cols][rows][2], frames [rows] strictly ascending, columns as
+ * eagle_post_layout gives them, the team mapping as two arrays (team_ids NULL: no mapping).  cand, owner, dist ([rows] each) may be NULL; *n_events = the
+ * number of events, of which at most cap are written. */
+int eagle_op_possession(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                        const int32_t* team_vals, int n_team, const EaglePossessionParams* p, int32_t* cand, int32_t* owner, double* dist,
+                        EaglePossessionEvent* events, int cap, int* n_events);
+
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
  * flags[i] = 0 keep the record, 1 re-project foot points and boundaries with Hs[9*i..], 2 no homography available yet. */
