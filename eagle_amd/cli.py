@@ -18,7 +18,10 @@ interpolated ball, folded goalkeeper ids), as ``main.py:43-81`` does.  ``--merge
 under several tracker ids into one id first and lists the joins as ``merges`` in ``metadata.json``.  ``--minimap`` (with ``--processed``) writes ``minimap.y4m``: the processed table as
 a top-down video of the pitch at the clip's fps (eagle_amd/minimap.py; ``--minimap-voronoi`` tints the areas each team controls, ``--minimap-scale``
 sets the pixels per metre).  ``--possession`` (with ``--processed``) writes ``possession.json``: per kept frame who has the ball, the passes and
-turnovers, and what they add up to per id, per team and per pair of ids (eagle_amd/possession.py).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+turnovers, and what they add up to per id, per team and per pair of ids (eagle_amd/possession.py).  ``--occupancy`` (with ``--processed``) writes
+``occupancy.npy`` and ``occupancy.json``: where every player, every team and the ball spent their time, as seconds per pitch cell
+(eagle_amd/occupancy.py; ``--occupancy-grid`` cells per metre, ``--occupancy-sigma`` metres of Gaussian smoothing, ``--occupancy-pictures`` one PPM per
+team and one for the ball); the maps follow a person only with ``--merge-ids``.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -102,7 +105,19 @@ def main(argv=None):
     ap.add_argument("--possession", action="store_true",
                     help="with --processed: also write <out>/possession.json, per kept frame who has the ball, the passes and turnovers, and per id / team what they add up "
                          "to (most useful with --merge-ids)")
+    ap.add_argument("--occupancy", action="store_true",
+                    help="with --processed: also write <out>/occupancy.npy (float64 seconds [maps, 68 R, 105 R]) and <out>/occupancy.json, where every player, every "
+                         "team and the ball spent their time (the maps follow a person only with --merge-ids)")
+    ap.add_argument("--occupancy-grid", type=int, default=1, choices=[1, 2, 4], metavar="R", help="with --occupancy: cells per metre")
+    ap.add_argument("--occupancy-sigma", type=float, default=2.0, metavar="S", help="with --occupancy: the Gaussian's sigma in metres, 0 .. 10 (0: the raw counts)")
+    ap.add_argument("--occupancy-pictures", action="store_true",
+                    help="with --occupancy: also write one binary PPM per team (<out>/occupancy_team<t>.ppm) and one for the ball (<out>/occupancy_ball.ppm) at "
+                         "--minimap-scale pixels per metre")
     a = ap.parse_args(argv)
+    if a.occupancy and not a.processed:
+        ap.error("--occupancy works on the processed table: it needs --processed")
+    if a.occupancy_pictures and not a.occupancy:
+        ap.error("--occupancy-pictures draws the occupancy maps: it needs --occupancy")
     if a.possession and not a.processed:
         ap.error("--possession works on the processed table: it needs --processed")
     if a.minimap and not a.processed:
@@ -177,6 +192,15 @@ def main(argv=None):
             from . import possession as po
             with open(os.path.join(a.out, "possession.json"), "w") as f:
                 json.dump(po.to_json(po.possession(model.handle, table, a.fps)), f)
+        if a.occupancy:
+            from . import occupancy as oc
+            occ = oc.occupancy(model.handle, table, a.fps, a.occupancy_grid, a.occupancy_sigma)
+            np.save(os.path.join(a.out, "occupancy.npy"), occ["grids"])
+            with open(os.path.join(a.out, "occupancy.json"), "w") as f:
+                json.dump(oc.to_json(occ), f)
+            if a.occupancy_pictures:
+                for name, img in oc.pictures(model.handle, table, occ, a.minimap_scale):
+                    oc.write_ppm(os.path.join(a.out, "occupancy_%s.ppm" % name), img)
         if a.minimap or a.minimap_control:
             from .minimap import minimap
             write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420",

@@ -285,9 +285,7 @@ static void minimap_launch(const MinimapArgs& args, hipStream_t s)
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
-struct MmPlan { int S, M, w, h, r, rb, t; };
-
-static MmPlan minimap_plan(const EagleMinimapParams* p)
+MmPlan minimap_plan(const EagleMinimapParams* p)
 {
     if (!p) fail(EAGLE_E_INVALID, "minimap: params is NULL");
     if (p->scale < 2 || p->scale > 32 || (p->scale & 1)) fail(EAGLE_E_INVALID, "minimap: scale %d must be even and within 2 .. 32 pixels per metre", p->scale);
@@ -305,7 +303,7 @@ static MmPlan minimap_plan(const EagleMinimapParams* p)
 }
 
 // the white pitch markings of a (scale, margin) as a bit mask, rows of (w + 7) / 8 bytes: tests/minimap_ref.py::markings, dimension by dimension
-static std::vector<uint8_t> markings_mask(const MmPlan& pl, int* pitch)
+std::vector<uint8_t> markings_mask(const MmPlan& pl, int* pitch)
 {
     const int S = pl.S, M = pl.M, w = pl.w, h = pl.h, hw = std::max(1, S / 4), mp = (w + 7) / 8;
     std::vector<uint8_t> bits((size_t)mp * h, 0);
@@ -410,6 +408,21 @@ static void grow(void** buf, size_t* cap, size_t need)
     *cap = need;
 }
 
+// the marking mask of this (scale, margin) in the handle, rebuilt when either changed (also the occupancy picture's)
+const uint8_t* minimap_mask(EagleHandle* h, const MmPlan& pl)
+{
+    if (h->mm_mask_scale != pl.S || h->mm_mask_margin != pl.M) {
+        int mp = 0;
+        const std::vector<uint8_t> bits = markings_mask(pl, &mp);
+        grow((void**)&h->mm_mask, &h->mm_mask_cap, bits.size());
+        h->mm_mask_scale = 0;
+        HIP_CHECK(hipMemcpyAsync(h->mm_mask, bits.data(), bits.size(), hipMemcpyHostToDevice, h->s_main));
+        HIP_CHECK(hipStreamSynchronize(h->s_main));        // (a pageable source: it has left the vector before the vector goes)
+        h->mm_mask_scale = pl.S; h->mm_mask_margin = pl.M;
+    }
+    return h->mm_mask;
+}
+
 // bytes a call writes (the pictures) and reads (the pitch cells of its rows)
 static double minimap_bytes(const MinimapArgs& m, const YuvGeom& g) { return (double)m.n * ((double)g.dense_bytes + 16.0 * (m.ncols + 4)); }
 
@@ -423,15 +436,7 @@ static MinimapArgs minimap_prepare(EagleHandle* h, EaglePostTable* t, const MmPl
     m.values = (const double2*)t->d_values; m.rows = t->rows; m.ncols = (int)cols.size(); m.stride = MM_HEAD + m.ncols;
     grow(&h->mm_list, &h->mm_list_cap, (size_t)std::min(max_pass, MM_PASS) * m.stride * sizeof(int4));
     grow(&h->mm_cols, &h->mm_cols_cap, std::max<size_t>(cols.size() * sizeof(MmCol), 16));
-    if (h->mm_mask_scale != pl.S || h->mm_mask_margin != pl.M) {
-        int mp = 0;
-        const std::vector<uint8_t> bits = markings_mask(pl, &mp);
-        grow((void**)&h->mm_mask, &h->mm_mask_cap, bits.size());
-        h->mm_mask_scale = 0;
-        HIP_CHECK(hipMemcpyAsync(h->mm_mask, bits.data(), bits.size(), hipMemcpyHostToDevice, h->s_main));
-        HIP_CHECK(hipStreamSynchronize(h->s_main));        // (a pageable source: it has left the vector before the vector goes)
-        h->mm_mask_scale = pl.S; h->mm_mask_margin = pl.M;
-    }
+    minimap_mask(h, pl);
     if (!cols.empty()) HIP_CHECK(hipMemcpyAsync(h->mm_cols, cols.data(), cols.size() * sizeof(MmCol), hipMemcpyHostToDevice, h->s_main));
     HIP_CHECK(hipStreamSynchronize(h->s_main));            // (pageable sources: they have left the vectors)
     m.lists = (int4*)h->mm_list; m.cols = (const MmCol*)h->mm_cols; m.mask = h->mm_mask;

@@ -626,6 +626,7 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
     if (p->n_team < 0 || (p->n_team > 0 && p->team_ids && !p->team_vals)) fail(EAGLE_E_INVALID, "eagle_postprocess: bad team map (%d entries)", p->n_team);
     if (p->max_bytes < 0) fail(EAGLE_E_INVALID, "eagle_postprocess: max_bytes %lld is negative", (long long)p->max_bytes);
     std::unique_ptr<EaglePostTable> t(new EaglePostTable);
+    t->max_bytes = p->max_bytes;
     try {
         postprocess(h, recs, n, p, t.get());
     } catch (...) {
@@ -639,10 +640,11 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
 void eagle_post_free(EaglePostTable* t)
 {
     if (!t) return;
-    if (t->d_values || t->d_vel || t->d_poss) (void)hipSetDevice(t->h->cfg.device);
+    if (t->d_values || t->d_vel || t->d_poss || t->d_occ) (void)hipSetDevice(t->h->cfg.device);
     if (t->d_values) (void)hipFree(t->d_values);
     if (t->d_vel) (void)hipFree(t->d_vel);
     if (t->d_poss) (void)hipFree(t->d_poss);
+    if (t->d_occ) (void)hipFree(t->d_occ);
     delete t;
 }
 

@@ -286,6 +286,10 @@ struct EaglePostTable {
     void* d_poss = nullptr;              // possession (eagle_post_possession): dist [rows] f64 | cand [rows] i32 | owner [rows] i32, resident until eagle_post_free
     bool has_poss = false;
     std::vector<EaglePossessionEvent> events;
+    int64_t max_bytes = 0;               // eagle_postprocess's memory budget (0: nine tenths of what is free): later results kept with the table answer to it too
+    void* d_occ = nullptr;               // occupancy (eagle_post_occupancy): grids f32 | counts i32 | bytes u8, [occ_nsel][gh][gw] each, then total | outside | max
+    int occ_nsel = 0, occ_R = 0;         // u32 [occ_nsel] each; resident until eagle_post_free
+    bool has_occ = false;
 };
 
 namespace eagle {
@@ -336,6 +340,11 @@ void control_columns(const EaglePostColumn* columns, int ncols, const int32_t* t
 void control_launch(const ControlArgs& a, hipStream_t s);                       // n <= CT_PASS rows: (share memset,) sites, grids
 ControlArgs control_prepare(EagleHandle* h, EaglePostTable* t, const EagleControlParams* p, int max_pass);      // site columns uploaded, list space for max_pass rows
 void control_rows(EagleHandle* h, const ControlArgs& prepared, int row0, int n, uint8_t* d_out, int64_t* d_share);   // enqueued on s_main, not awaited
+// minimap.hip: what the occupancy picture (occupancy.hip) shares with it
+struct MmPlan { int S, M, w, h, r, rb, t; };
+MmPlan minimap_plan(const EagleMinimapParams* p);                               // EAGLE_E_INVALID unless the parameters are in range; canvas size and radii
+std::vector<uint8_t> markings_mask(const MmPlan& pl, int* pitch);               // the white markings of a (scale, margin) as a bit mask, rows of (w + 7) / 8 bytes
+const uint8_t* minimap_mask(EagleHandle* h, const MmPlan& pl);                  // the same in HBM, kept in the handle for the last (scale, margin); synchronises s_main
 }  // namespace eagle
 
 // ---- C ABI: the body of every entry runs between API_BEGIN and API_END ---------------------------------------

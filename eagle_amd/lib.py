@@ -89,6 +89,11 @@ class EaglePossessionParams(C.Structure):
     _fields_ = [("fps", C.c_int32), ("min_hold", C.c_int32), ("max_gap", C.c_int32), ("reserved0", C.c_int32), ("radius", C.c_double), ("reserved", C.c_int64)]
 
 
+class EagleOccupancyParams(C.Structure):
+    """include/eagle.h EagleOccupancyParams: frames per second, the largest frame step a row may stand for, cells per metre, the Gaussian's sigma (m)."""
+    _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("cells_per_metre", C.c_int32), ("reserved0", C.c_int32), ("sigma", C.c_double), ("reserved", C.c_int64)]
+
+
 POST_PLAYER, POST_GOALKEEPER, POST_BALL, POST_BOUNDARY = 0, 1, 2, 3    # include/eagle.h EAGLE_POST_*
 POST_NO_BALL = 1                                                       # ... flag: fewer than two ball sightings
 POSTCOL_DTYPE = np.dtype([("kind", "<i4"), ("id", "<i4"), ("video", "<i4"), ("reserved", "<i4")])      # EaglePostColumn
@@ -240,6 +245,14 @@ def load():
     L.eagle_post_device_possession.argtypes = [vp, C.POINTER(vp)]
     L.eagle_post_events.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_op_possession.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, pp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)]
+    op = C.POINTER(EagleOccupancyParams)
+    L.eagle_occupancy_size.argtypes = [op, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.eagle_post_occupancy.argtypes = [vp, vp, op, vp, vp, i32]
+    L.eagle_post_occupancy_values.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.eagle_post_device_occupancy.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.eagle_occupancy_picture.argtypes = [vp, vp, i32, i32, i32, C.c_uint32, vp]
+    L.eagle_op_occupancy.argtypes = [i32, vp, vp, vp, i32, i32, op, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.eagle_op_occupancy_picture.argtypes = [i32, vp, i32, i32, i32, C.c_uint32, vp]
     L.eagle_op_reid_crop.argtypes = [i32, u8p, i32, i32, i32, vp, i32, i32, i32, i32, i32, fp]
     L.eagle_op_reid_conv7.argtypes = [i32, fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
     L.eagle_op_reid_maxpool3s2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -264,7 +277,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_minimap", "eagle_post_velocities", "eagle_post_velocity_values", "eagle_post_device_velocity_values", "eagle_control_size",
            "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
            "eagle_op_minimap_control", "eagle_post_possession", "eagle_post_possession_values", "eagle_post_device_possession", "eagle_post_events",
-           "eagle_op_possession", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_op_possession", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
+           "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -641,6 +655,36 @@ class Handle:
         d = C.c_void_p()
         self._check(self.L.eagle_post_device_possession(table._t, C.byref(d)), "post_device_possession")
         return d.value
+
+    # --- occupancy heat maps (include/eagle.h, eagle_post_occupancy / eagle_occupancy_picture) -------------------------------
+    def occupancy(self, table, params, sel_off, sel_cols):
+        """The maps of the selections (CSR: sel_off [n_sel + 1], sel_cols table column indices) of a PostTable of this handle, computed on the GPU and
+        kept with the table (a second call replaces the first) -> (grids float32, bytes uint8, counts int32: [n_sel, gh, gw] each; total, outside
+        int64 [n_sel]).  The grids are in frames."""
+        sel_off, sel_cols = np.ascontiguousarray(sel_off, np.int32), np.ascontiguousarray(sel_cols, np.int32)
+        n_sel = len(sel_off) - 1
+        keep = np.zeros(4, np.float64)
+        self._check(self.L.eagle_post_occupancy(self._h, table._t, C.byref(params), _ptr(sel_off, keep), _ptr(sel_cols, keep), n_sel), "post_occupancy")
+        gw, gh = occupancy_size(params)
+        grids, by, counts = np.zeros((n_sel, gh, gw), np.float32), np.zeros((n_sel, gh, gw), np.uint8), np.zeros((n_sel, gh, gw), np.int32)
+        total, outside = np.zeros(n_sel, np.int64), np.zeros(n_sel, np.int64)
+        self._check(self.L.eagle_post_occupancy_values(table._t, _ptr(grids, keep), _ptr(by, keep), _ptr(total, keep), _ptr(outside, keep), _ptr(counts, keep)),
+                    "post_occupancy_values")
+        return grids, by, counts, total, outside
+
+    def occupancy_device(self, table):
+        """(grids float32, bytes uint8) [n_sel, gh, gw] in HBM (None, None before the first occupancy call of the table)."""
+        g, b = C.c_void_p(), C.c_void_p()
+        self._check(self.L.eagle_post_device_occupancy(table._t, C.byref(g), C.byref(b)), "post_device_occupancy")
+        return g.value, b.value
+
+    def occupancy_picture(self, table, sel, scale=8, margin=None, colour=(255, 255, 255)):
+        """Selection ``sel`` of the table's last occupancy result as a still picture of the pitch -> BGR uint8 [h, w, 3]; colour (b, g, r)."""
+        mp = minimap_params(scale, margin)
+        w, h = minimap_size(mp)
+        out = np.zeros((h, w, 3), np.uint8)
+        self._check(self.L.eagle_occupancy_picture(self._h, table._t, int(sel), mp.scale, mp.margin, _bgr(colour), out.ctypes.data_as(C.c_void_p)), "occupancy_picture")
+        return out
 
     def minimap_set_control(self, table, params):
         """The parameters the minimap's ``control`` layer of this table is computed with (None: forget them)."""
@@ -1252,6 +1296,26 @@ def possession_params(fps, radius=2.0, min_hold=2, max_gap=None):
     return EaglePossessionParams(int(fps), int(min_hold), int(fps if max_gap is None else max_gap), 0, float(radius), 0)
 
 
+def occupancy_params(fps, cells_per_metre=1, sigma=2.0, max_gap=None):
+    """EagleOccupancyParams; max_gap None: fps frames.  The 2 m sigma is a conventional choice, not fitted to data."""
+    return EagleOccupancyParams(int(fps), int(fps if max_gap is None else max_gap), int(cells_per_metre), 0, float(sigma), 0)
+
+
+def occupancy_size(params):
+    """(gw, gh) of the maps these parameters give (include/eagle.h eagle_occupancy_size; no GPU involved)."""
+    gw, gh = C.c_int(0), C.c_int(0)
+    L = load()
+    rc = L.eagle_occupancy_size(C.byref(params), C.byref(gw), C.byref(gh))
+    if rc:
+        raise EagleError(f"eagle_occupancy_size failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return gw.value, gh.value
+
+
+def _bgr(colour):
+    b, g, r = (int(v) & 255 for v in colour)
+    return b | g << 8 | r << 16
+
+
 def _table_args(what, values, columns):
     values = np.ascontiguousarray(values, np.float64)
     if not (isinstance(columns, np.ndarray) and columns.dtype == POSTCOL_DTYPE):
@@ -1322,6 +1386,44 @@ def op_possession(values, frames, columns, team_mapping, params, cap=None, devic
     if rc:
         raise EagleError(f"eagle_op_possession failed ({rc}): {L.eagle_last_error(None).decode()}")
     return cand, owner, dist, ev[: min(n.value, len(ev))].copy(), n.value
+
+
+def op_occupancy(values, frames, columns, params, sel_off, sel_cols, device=0):
+    """The occupancy launches on a constructed table (include/eagle.h eagle_op_occupancy): values float64 [cols][rows][2], frames int32 [rows]
+    strictly ascending, columns POSTCOL_DTYPE (or (kind, id, video) tuples), the selections in CSR form -> (grids float32, bytes uint8, counts int32:
+    [n_sel, gh, gw] each; total, outside int64 [n_sel])."""
+    L = load()
+    values, columns = _table_args("op_occupancy", values, columns)
+    frames = np.ascontiguousarray(frames, np.int32)
+    cols, rows = values.shape[:2]
+    if len(frames) != rows:
+        raise EagleError("op_occupancy: one frame number per row")
+    sel_off, sel_cols = np.ascontiguousarray(sel_off, np.int32), np.ascontiguousarray(sel_cols, np.int32)
+    n_sel = len(sel_off) - 1
+    gw, gh = occupancy_size(params)
+    grids, by, counts = np.zeros((n_sel, gh, gw), np.float32), np.zeros((n_sel, gh, gw), np.uint8), np.zeros((n_sel, gh, gw), np.int32)
+    total, outside = np.zeros(n_sel, np.int64), np.zeros(n_sel, np.int64)
+    keep = np.zeros(4, np.float64)
+    rc = L.eagle_op_occupancy(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, C.byref(params), _ptr(sel_off, keep), _ptr(sel_cols, keep),
+                              n_sel, _ptr(grids, keep), _ptr(by, keep), _ptr(total, keep), _ptr(outside, keep), _ptr(counts, keep))
+    if rc:
+        raise EagleError(f"eagle_op_occupancy failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return grids, by, counts, total, outside
+
+
+def op_occupancy_picture(byte_grid, cells_per_metre, scale=8, margin=None, colour=(255, 255, 255), device=0):
+    """One selection's bytes uint8 [gh, gw] -> its picture, BGR uint8 [h, w, 3] (include/eagle.h eagle_op_occupancy_picture); colour (b, g, r)."""
+    L = load()
+    byte_grid = np.ascontiguousarray(byte_grid, np.uint8)
+    if byte_grid.shape != (68 * int(cells_per_metre), 105 * int(cells_per_metre)):
+        raise EagleError("op_occupancy_picture: the bytes must be [68 R, 105 R]")
+    mp = minimap_params(scale, margin)
+    w, h = minimap_size(mp)
+    out = np.zeros((h, w, 3), np.uint8)
+    rc = L.eagle_op_occupancy_picture(device, byte_grid.ctypes.data_as(C.c_void_p), int(cells_per_metre), mp.scale, mp.margin, _bgr(colour), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_occupancy_picture failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
 
 
 def op_minimap_control(values, velocities, columns, team_mapping, params, control, row0=0, n=None, fmt="bgr", layout=None, out=None, device=0):

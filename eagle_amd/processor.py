@@ -73,3 +73,8 @@ class Processor:
         """Who has the ball in each kept frame of a processed table, the passes and turnovers, and what they add up to: see eagle_amd/possession.py."""
         from . import possession as po
         return po.possession(self.model.handle, table, fps, radius, min_hold, max_gap)
+
+    def occupancy(self, table, fps, cells_per_metre=1, sigma=2.0, max_gap=None):
+        """Where every player, every team and the ball of a processed table spent their time, as smoothed seconds per pitch cell: see eagle_amd/occupancy.py."""
+        from . import occupancy as oc
+        return oc.occupancy(self.model.handle, table, fps, cells_per_metre, sigma, max_gap)

@@ -450,6 +450,53 @@ int eagle_op_possession(int device, const double* values, const int32_t* frames,
                         const int32_t* team_vals, int n_team, const EaglePossessionParams* p, int32_t* cand, int32_t* owner, double* dist,
                         EaglePossessionEvent* events, int cap, int* n_events);
 
+/* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
+ * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
+ * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
+ * empty selection gives zeros.
+ *   WEIGHT   w[r] = frames[r + 1] - frames[r] when r + 1 < rows and that step is <= max_gap, else 1 (the last row, the row in front of a hole).
+ *   COUNTS   cells_per_metre R in {1, 2, 4}, gw = 105 R, gh = 68 R, grid row 0 is pitch y = 0 (eagle_control_size's geometry).  A cell of the table is
+ *            present when x and y are finite.  A present cell with 0 <= x < 105 and 0 <= y < 68 (float64) adds w[r] to count[s][(int) floor(y R)][(int)
+ *            floor(x R)], any other present cell adds it to outside[s], an absent cell adds nothing; total[s] = what went inside.  -0.0 is inside, 105.0
+ *            and 68.0 are outside.  Integers: no accumulation order matters.  The library accumulates in 32 bits and refuses a call in which
+ *            rows x max_gap x (the largest selection) reaches 2^31.
+ *   GRIDS    float32 without contraction: s = (float) sigma * (float) R, rad = (int) ceilf(3.0f * s), inv = 1.0f / (2.0f * s * s), t[0] = 1.0f,
+ *            t[k] = d_expf(-((float) (k * k)) * inv) (csrc/dmath.h); sigma == 0: rad = 0.  hz[j][i] = the sum over k = -rad .. rad, ascending, from
+ *            0.0f, of t[|k|] * (float) count[j][i + k], terms outside the grid skipped, multiply and add rounded separately; v[j][i] = the same sum
+ *            over hz[j + k][i].  Truncated at 3 sigma, zero outside the grid, not renormalised at the borders.  The unit is frames; seconds = v / fps.
+ *   BYTES    m = the largest v of the selection; byte = m > 0 ? (int) floorf(v / m * 255.0f + 0.5f) : 0.
+ *   PICTURE  a BGR canvas of eagle_minimap_size's size for (scale, margin), black; a pixel (X, Y) of the pitch rectangle reads the byte c of cell
+ *            i = ((X - margin) R) / scale, j = gh - 1 - ((Y - margin) R) / scale and takes per channel (colour * a + 128) >> 8 with a = c + (c >> 7);
+ *            the minimap's pitch markings on top in white; no players, no ball, no footprint.  bgr_colour = B | G << 8 | R << 16.
+ * Five launches (occupancy.hip) on the handle's main stream read the table where eagle_postprocess left it; the handle's records, staging buffers and
+ * graphs are not involved.  sigma 2 m is a conventional choice, not fitted to data.  The maps follow a person only when the ids do (merge_ids).
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, fps or max_gap not positive, cells_per_metre outside {1, 2, 4}, sigma not finite or
+ * outside [0, 10], n_sel < 0, offsets that do not ascend from 0, a member that is out of range, a video column, a boundary column or listed twice in its
+ * selection, the 2^31 bound, frames of the operator entry that do not ascend strictly, a result beyond the table's memory budget
+ * (EaglePostParams::max_bytes; the operator entry: nine tenths of what is free), a bad scale or margin of the picture (the minimap's rules), a sel
+ * outside the last result.  rows == 0 gives zeros; n_sel == 0 writes nothing. */
+typedef struct EagleOccupancyParams {
+    int32_t fps;                   /* > 0: frames per second of the frame numbers (the host divides by it; the kernels count frames) */
+    int32_t max_gap;               /* > 0: a row in front of a step of more frames than this counts one frame (a usual choice: fps) */
+    int32_t cells_per_metre;       /* 1, 2 or 4 */
+    int32_t reserved0;
+    double sigma;                  /* metres: 0 .. 10; 0 = no smoothing */
+    int64_t reserved;
+} EagleOccupancyParams;
+int eagle_occupancy_size(const EagleOccupancyParams* p, int* gw, int* gh);                                   /* = eagle_control_size's */
+/* The result is kept with the table until eagle_post_free and replaces an earlier one. */
+int eagle_post_occupancy(EagleHandle* h, EaglePostTable* t, const EagleOccupancyParams* p, const int32_t* sel_off, const int32_t* sel_cols, int n_sel);
+/* copies to the host: grids, bytes and counts [n_sel][gh][gw], total and outside [n_sel]; any pointer may be NULL */
+int eagle_post_occupancy_values(EaglePostTable* t, float* grids, uint8_t* bytes, int64_t* total, int64_t* outside, int32_t* counts);
+int eagle_post_device_occupancy(const EaglePostTable* t, const float** d_grids, const uint8_t** d_bytes);    /* in HBM; both NULL before eagle_post_occupancy */
+/* selection sel of the last result as a picture; out: host memory, [h][w][3] */
+int eagle_occupancy_picture(EagleHandle* h, EaglePostTable* t, int sel, int scale, int margin, uint32_t bgr_colour, uint8_t* out);
+/* Operator entries (host buffers in / out, no handle) for constructed tables: values [cols][rows][2], frames [rows] strictly ascending, columns as
+ * eagle_post_layout gives them; every output may be NULL.  The picture entry takes one selection's bytes [gh][gw]. */
+int eagle_op_occupancy(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const EagleOccupancyParams* p,
+                       const int32_t* sel_off, const int32_t* sel_cols, int n_sel, float* grids, uint8_t* bytes, int64_t* total, int64_t* outside, int32_t* counts);
+int eagle_op_occupancy_picture(int device, const uint8_t* bytes_grid, int cells_per_metre, int scale, int margin, uint32_t bgr_colour, uint8_t* out);
+
 /* Reference cadence with homography_interval > 1 (main.py:27 at --fps 5; cm.py:333-415): the caller decides, frame by frame in
  * clip order, which frame's homography each frame uses (scheduled / retry / carried) and hands the records back:
  * flags[i] = 0 keep the record, 1 re-project foot points and boundaries with Hs[9*i..], 2 no homography available yet. */
