@@ -102,6 +102,14 @@ def main(argv=None):
     ap.add_argument("--minimap-control", action="store_true", help="with --processed: write <out>/minimap.y4m with the pitch-control layer (not together with --minimap-voronoi)")
     ap.add_argument("--control-grid", type=int, default=None, choices=[1, 2, 4], metavar="R",
                     help="with --processed: also write <out>/control.npy (uint8 [rows, 68 R, 105 R]) and <out>/control_share.json, team 0's share of the pitch per row")
+    ap.add_argument("--minimap-trails", nargs="?", const="fps", default=None, metavar="W",
+                    help="with --minimap: draw the paths of every person and the ball over the last W kept rows (default: --fps rows)")
+    ap.add_argument("--minimap-passes", action="store_true",
+                    help="with --minimap: draw an arrow per pass or turnover and a ring round the ball's owner (runs the possession step with its defaults)")
+    ap.add_argument("--trajectory", default=None, metavar="IDS",
+                    help="with --processed: also write <out>/trajectory.ppm, the paths of the comma-separated ids (or `ball`) over the clip, at --minimap-scale")
+    ap.add_argument("--pass-pictures", action="store_true",
+                    help="with --processed: also write <out>/pass_<k>.ppm, one still per pass event at its release row (runs the possession step with its defaults)")
     ap.add_argument("--possession", action="store_true",
                     help="with --processed: also write <out>/possession.json, per kept frame who has the ball, the passes and turnovers, and per id / team what they add up "
                          "to (most useful with --merge-ids)")
@@ -118,6 +126,22 @@ def main(argv=None):
         ap.error("--occupancy works on the processed table: it needs --processed")
     if a.occupancy_pictures and not a.occupancy:
         ap.error("--occupancy-pictures draws the occupancy maps: it needs --occupancy")
+    if (a.minimap_trails is not None or a.minimap_passes) and not (a.minimap or a.minimap_control):
+        ap.error("--minimap-trails and --minimap-passes draw into the minimap: they need --minimap")
+    if a.minimap_trails is not None:
+        try:
+            a.minimap_trails = a.fps if a.minimap_trails == "fps" else int(a.minimap_trails)
+        except ValueError:
+            a.minimap_trails = 0
+        if a.minimap_trails < 1:
+            ap.error("--minimap-trails takes a number of rows of at least 1")
+    if (a.trajectory is not None or a.pass_pictures) and not a.processed:
+        ap.error("--trajectory and --pass-pictures work on the processed table: they need --processed")
+    if a.trajectory is not None:
+        try:
+            a.trajectory = [tok if tok == "ball" else int(tok) for tok in a.trajectory.split(",")]
+        except ValueError:
+            ap.error("--trajectory takes a comma list of ids or `ball`")
     if a.possession and not a.processed:
         ap.error("--possession works on the processed table: it needs --processed")
     if a.minimap and not a.processed:
@@ -201,10 +225,26 @@ def main(argv=None):
             if a.occupancy_pictures:
                 for name, img in oc.pictures(model.handle, table, occ, a.minimap_scale):
                     oc.write_ppm(os.path.join(a.out, "occupancy_%s.ppm" % name), img)
+        if (a.minimap_passes or a.pass_pictures) and not a.possession:
+            model.handle.possession(table, lib.possession_params(a.fps))
+        entities = [c for c, k in enumerate(table.columns) if not k["video"] and int(k["kind"]) in (lib.POST_PLAYER, lib.POST_GOALKEEPER, lib.POST_BALL)]
+        if a.trajectory is not None:
+            from . import minimap as mm
+            want = a.trajectory
+            cols = [c for c in entities if (("ball" in want) if int(table.columns[c]["kind"]) == lib.POST_BALL else int(table.columns[c]["id"]) in want)]
+            mm.trajectory_picture(model.handle, table, cols, None, a.minimap_scale, max_gap=a.fps, path=os.path.join(a.out, "trajectory.ppm"))
+        if a.pass_pictures:
+            from . import minimap as mm
+            for k, e in enumerate(model.handle.events(table)):
+                if int(e["kind"]) == lib.EVENT_PASS:
+                    mm.pass_picture(model.handle, table, k, a.minimap_scale, path=os.path.join(a.out, "pass_%d.ppm" % k))
         if a.minimap or a.minimap_control:
             from .minimap import minimap
+            tp = lib.trail_params(window=a.minimap_trails or a.fps, max_gap=a.fps, pass_hold=a.fps)      # (None: no trails, the window is not used)
             write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420",
-                                                                   control=lib.control_params(min(4, a.minimap_scale)) if a.minimap_control else None), a.fps)
+                                                                   control=lib.control_params(min(4, a.minimap_scale)) if a.minimap_control else None,
+                                                                   trails=entities if a.minimap_trails is not None else None, passes=a.minimap_passes,
+                                                                   owner=a.minimap_passes, trail_params=tp), a.fps)
         table.close()
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
         if a.merge_ids:

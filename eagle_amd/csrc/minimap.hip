@@ -17,19 +17,14 @@
 // Voronoi without 64-bit multiplies per pixel: (16X - qx)^2 + (16Y - qy)^2 = 256 (X^2 + Y^2) + [qx^2 + qy^2 - 32 X qx - 32 Y qy]; the first term is the
 // same for every site, so the sites are compared by the bracket: its constant is formed once per staged entry, the Y term once per strip row, and along a
 // row it changes by the 32-bit amount 32 qx per pixel.  Exact: |q| < 2^20 and 32 X < 2^17 keep everything below 2^42.
-#include "runtime.h"
+#include "trails.h"
 #include "pix_out.h"
 
 namespace eagle {
 
 static constexpr int MM_CHUNK = AN_THREADS;            // list entries staged per trip: one per thread
-static constexpr int MM_HEAD = 3;                      // header slots of a row's list: {count, footprint ok}, {BL, TL}, {TR, BR}
-static constexpr int MM_KIND_SHIFT = 24, MM_SITE_BIT = 1 << 28;
-static constexpr int MM_TINT_A = 51, MM_FOOT_A = 77;
-static constexpr double MM_DOMAIN = 1024.0, MM_CIRCLE_R = 9.15;
-static constexpr uint32_t MM_WHITE = 0xffffffu, MM_NONE = 0xffffffffu;
-
-struct MmCol { int32_t col; uint32_t kc; };            // a drawable table column: B | G << 8 | R << 16 | kind << 24 | site << 28
+static constexpr int MM_TINT_A = 51, MM_FOOT_A = 77, MM_DIM_A = 64;
+static constexpr double MM_CIRCLE_R = 9.15;
 
 struct MinimapArgs {
     AnnotArgs out;               // (src, prims, offs unused)
@@ -45,15 +40,9 @@ struct MinimapArgs {
     int ctl_R, ctl_gw, ctl_gh;   // cells per metre and the grid's size
 };
 
-__device__ __forceinline__ bool mm_quantise(double2 v, double K, int ox, int oy, int& qx, int& qy)
-{
-    if (!(fabs(v.x) <= MM_DOMAIN) || !(fabs(v.y) <= MM_DOMAIN)) return false;          // NaN, +-inf and the far field
-    qx = ox + (int)floor(v.x * K + 0.5);
-    qy = oy - (int)floor(v.y * K + 0.5);
-    return true;
-}
-
-__global__ __launch_bounds__(256) void minimap_sites_kernel(MinimapArgs m)
+// LAYERS: the instantiation the K25 layers run (la: owner and dim bits of the entries); the plain one is the code it was before them
+template <bool LAYERS>
+__device__ __forceinline__ void mm_sites(const MinimapArgs& m, const MmLayerArgs* la)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m.n) return;
@@ -66,7 +55,13 @@ __global__ __launch_bounds__(256) void minimap_sites_kernel(MinimapArgs m)
         const MmCol d = m.cols[c];
         int qx, qy;
         if (!mm_quantise(m.values[(size_t)d.col * m.rows + row], K, ox, oy, qx, qy)) continue;
-        L[MM_HEAD + cnt++] = make_int4(qx, qy, (int)d.kc, 0);
+        uint32_t kc = d.kc;
+        if constexpr (LAYERS) {
+            const bool person = (kc >> MM_KIND_SHIFT & 15) != EAGLE_POST_BALL;
+            if (person && la->owner && la->owner[row] == d.col) kc |= MM_OWNER_BIT;
+            if (person && la->dim && d.col != la->pass_from && d.col != la->pass_to) kc |= MM_DIM_BIT;
+        }
+        L[MM_HEAD + cnt++] = make_int4(qx, qy, (int)kc, 0);
     }
     int q[8];
     bool ok = true;
@@ -79,6 +74,9 @@ __global__ __launch_bounds__(256) void minimap_sites_kernel(MinimapArgs m)
     L[1] = make_int4(q[0], q[1], q[2], q[3]);
     L[2] = make_int4(q[4], q[5], q[6], q[7]);
 }
+
+__global__ __launch_bounds__(256) void minimap_sites_kernel(MinimapArgs m) { mm_sites<false>(m, nullptr); }
+__global__ __launch_bounds__(256) void minimap_sites_layers_kernel(MinimapArgs m, MmLayerArgs la) { mm_sites<true>(m, &la); }
 
 __device__ __forceinline__ uint32_t mm_blend(uint32_t bg, uint32_t c, int a)
 {
@@ -119,10 +117,63 @@ __device__ __forceinline__ uint32_t mm_tri_strip(int ax, int ay, int bx, int by,
     return bits;
 }
 
-__global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m)
+// the pixels of the strip at (x0, y0) a capsule covers (tests/trails_ref.py, CAPSULE): squared distance to the segment A B <= hw^2, exactly.  t = (P - A).d and
+// cross = (P - A) x d are affine in the pixel: evaluated once in 64 bits at the strip's origin and stepped by additions (|q| < 2^20: both stay below 2^42).
+// Between the end points a pixel is first rejected in 64 bits by |cross| > hw (|dx| + |dy|) (sufficient: |d| <= |dx| + |dy|), and only then cross^2 is
+// formed as a 128-bit product (high and low half) and compared with hw^2 L2 < 2^57.  (After that reject |cross| < 2^29, so the high half is 0 here; the
+// full form is kept so that the comparison stays exact if the reject is ever loosened.)  The end caps are discs: 32-bit once |P - end| <= hw per axis
+__device__ __forceinline__ uint32_t mm_capsule_strip(int ax, int ay, int bx, int by, int hw, int x0, int y0)
+{
+    const int X = 16 * x0, Y = 16 * y0;
+    if (X + 16 * (AN_STRIP - 1) < min(ax, bx) - hw || X > max(ax, bx) + hw || Y + 16 < min(ay, by) - hw || Y > max(ay, by) + hw) return 0;
+    const int dxi = bx - ax, dyi = by - ay, hw2 = hw * hw;
+    const long long dx = dxi, dy = dyi, L2 = dx * dx + dy * dy;
+    const long long lim = (long long)hw * (llabs(dx) + llabs(dy));
+    const unsigned long long rhs = (unsigned long long)hw2 * (unsigned long long)L2;
+    long long t_row = (long long)(X - ax) * dx + (long long)(Y - ay) * dy, c_row = (long long)(X - ax) * dy - (long long)(Y - ay) * dx;
+    uint32_t bits = 0;
+    #pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        long long t = t_row, c = c_row;
+        const int py = Y + 16 * r - ay;
+        #pragma unroll
+        for (int k = 0; k < AN_STRIP; ++k) {
+            const int px = X + 16 * k - ax;
+            bool cov;
+            if (t <= 0) cov = abs(px) <= hw && abs(py) <= hw && px * px + py * py <= hw2;
+            else if (t >= L2) {
+                const int qx = px - dxi, qy = py - dyi;
+                cov = abs(qx) <= hw && abs(qy) <= hw && qx * qx + qy * qy <= hw2;
+            } else {
+                const unsigned long long ac = (unsigned long long)llabs(c);
+                cov = (long long)ac <= lim && __umul64hi(ac, ac) == 0 && ac * ac <= rhs;
+            }
+            if (cov) bits |= 1u << (r * AN_STRIP + k);
+            t += 16 * dx; c += 16 * dy;
+        }
+        t_row += 16 * dy; c_row -= 16 * dx;
+    }
+    return bits;
+}
+
+__device__ __forceinline__ void mm_paint(uint32_t (&px)[2][AN_STRIP], uint32_t bits, uint32_t color)
+{
+    if (!bits) return;
+    #pragma unroll
+    for (int r = 0; r < 2; ++r)
+        #pragma unroll
+        for (int k = 0; k < AN_STRIP; ++k)
+            if (bits >> (r * AN_STRIP + k) & 1) px[r][k] = color;
+}
+
+// LAYERS: the instantiation with the K25 sections (trails, pass arrows, owner ring, dimmed discs) compiled in, launched only when one of them is on; the
+// plain instantiation is the kernel as it was before them
+template <bool LAYERS>
+__device__ __forceinline__ void mm_draw(const MinimapArgs& m, const MmLayerArgs* la)
 {
     __shared__ int4 s_e[MM_CHUNK];
     __shared__ long long s_n[MM_CHUNK];
+    __shared__ int4 s_f[LAYERS ? MM_CHUNK : 1], s_g[LAYERS ? MM_CHUNK : 1];
     const AnnotArgs& a = m.out;
     const int tiles_x = (a.w + AN_TW - 1) / AN_TW;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x, f = blockIdx.y;
@@ -227,15 +278,85 @@ __global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m)
         }
     }
 
+    if constexpr (LAYERS) {
+        const int row = m.row0 + f, hw = la->hw16;
+        // ---- 4a. trails: entry e of the picture is segment (j - 1, j) of selected column e / per, j = jlo + e % per, the oldest first ----
+        if (la->nsel) {                                // (uniform)
+            const int jlo = la->jlo >= 0 ? la->jlo : max(1, row - la->window + 1), per = max(0, row - jlo + 1), total = la->nsel * per;
+            for (int base = 0; base < total; base += MM_CHUNK) {
+                const int nc = min(MM_CHUNK, total - base);
+                __syncthreads();
+                if (tid < nc) {
+                    const int e = base + tid, ci = e / per, j = jlo + (e - ci * per);
+                    const int2* P = la->pts + (size_t)ci * la->prows + (j - la->prow0);
+                    const int2 A = P[-1], B = P[0];
+                    const bool vis = A.x != MM_ABSENT && B.x != MM_ABSENT && la->link[j - la->prow0] && min(A.x, B.x) - hw <= 16 * tx1 && max(A.x, B.x) + hw >= 16 * tx0 &&
+                                     min(A.y, B.y) - hw <= 16 * ty1 && max(A.y, B.y) + hw >= 16 * ty0;
+                    const uint32_t c = la->sel[ci].kc, fd = 256u - (uint32_t)(((long long)(row - j) * (256 - la->dim_floor)) / la->window);
+                    const uint32_t color = ((c & 255u) * fd >> 8) | ((c >> 8 & 255u) * fd >> 8) << 8 | ((c >> 16 & 255u) * fd >> 8) << 16;
+                    s_e[tid] = make_int4(A.x, A.y, B.x, B.y);
+                    s_f[tid] = make_int4((int)color, vis, 0, 0);
+                }
+                __syncthreads();
+                if (!live) continue;
+                for (int j = 0; j < nc; ++j) {
+                    const int4 g = s_f[j];
+                    if (!g.y) continue;                // (uniform)
+                    const int4 e = s_e[j];
+                    mm_paint(px, mm_capsule_strip(e.x, e.y, e.z, e.w, hw, x0, y0), (uint32_t)g.x);
+                }
+            }
+        }
+        // ---- 4b. pass arrows: the events [first, last) that can show on this picture, in event order; the shaft, then the head ----
+        if (la->ev) {                                  // (uniform)
+            const int2 rg = la->ev_range[row - la->range_row0];
+            for (int base = rg.x; base < rg.y; base += MM_CHUNK) {
+                const int nc = min(MM_CHUNK, rg.y - base);
+                __syncthreads();
+                if (tid < nc) {
+                    const int4* E = la->ev + 3 * (size_t)(base + tid);
+                    const int4 sh = E[0], hd = E[1], k = E[2];
+                    bool vis = (k.x & MM_EV_OK) && (la->only || (k.y <= row && (long long)row < (long long)k.z + la->pass_hold));
+                    int lx = min(sh.x, sh.z) - hw, hx = max(sh.x, sh.z) + hw, ly = min(sh.y, sh.w) - hw, hy = max(sh.y, sh.w) + hw;
+                    if (k.x & MM_EV_HEAD) {
+                        lx = min(lx, min(hd.x, hd.z)); hx = max(hx, max(hd.x, hd.z)); ly = min(ly, min(hd.y, hd.w)); hy = max(hy, max(hd.y, hd.w));
+                    }
+                    vis = vis && lx <= 16 * tx1 && hx >= 16 * tx0 && ly <= 16 * ty1 && hy >= 16 * ty0;
+                    s_e[tid] = sh; s_f[tid] = hd;
+                    s_g[tid] = make_int4(k.x & (int)MM_WHITE, vis, k.x & MM_EV_HEAD, 0);
+                }
+                __syncthreads();
+                if (!live) continue;
+                for (int j = 0; j < nc; ++j) {
+                    const int4 g = s_g[j];
+                    if (!g.y) continue;                // (uniform)
+                    const int4 e = s_e[j];
+                    uint32_t bits = mm_capsule_strip(e.x, e.y, e.z, e.w, hw, x0, y0);
+                    if (g.z) {
+                        const int4 hd = s_f[j];
+                        bits |= mm_tri_strip(e.z, e.w, hd.x, hd.y, hd.z, hd.w, x0, y0);
+                    }
+                    mm_paint(px, bits, (uint32_t)g.x);
+                }
+            }
+        }
+    }
+
     // ---- 5. + 6. discs and ball rings in list order, culled against the tile ----
     for (int base = 0; base < count; base += MM_CHUNK) {
         const int nc = min(MM_CHUNK, count - base);
         __syncthreads();
         if (tid < nc) {
             int4 e = L[MM_HEAD + base + tid];
-            const int rr = ((uint32_t)e.z >> MM_KIND_SHIFT & 15) == EAGLE_POST_BALL ? m.rb16 : m.r16;
+            int rr = ((uint32_t)e.z >> MM_KIND_SHIFT & 15) == EAGLE_POST_BALL ? m.rb16 : m.r16;
+            if constexpr (LAYERS) {
+                if (e.z & MM_OWNER_BIT) rr = la->r16o;
+            }
             // pixels with |16 X - qx| <= rr: ceil((qx - rr) / 16) .. floor((qx + rr) / 16)
             e.w = ((e.x - rr + 15) >> 4) <= tx1 && ((e.x + rr) >> 4) >= tx0 && ((e.y - rr + 15) >> 4) <= ty1 && ((e.y + rr) >> 4) >= ty0;
+            if constexpr (LAYERS) {
+                if (((uint32_t)e.z >> MM_KIND_SHIFT & 15) == MM_KIND_SKIP) e.w = 0;
+            }
             s_e[tid] = e;
         }
         __syncthreads();
@@ -246,6 +367,23 @@ __global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m)
             const bool ball = ((uint32_t)e.z >> MM_KIND_SHIFT & 15) == EAGLE_POST_BALL;
             const int rr = ball ? m.rb16 : m.r16;
             const int dx0 = 16 * x0 - e.x, dy0 = 16 * y0 - e.y;
+            if constexpr (LAYERS) {                    // the owner's ring after its disc; a dimmed disc; a still's ring in its column's colour
+                const int ro = (e.z & MM_OWNER_BIT) ? la->r16o : rr;
+                if (dx0 > ro || dx0 + 16 * (AN_STRIP - 1) < -ro || dy0 > ro || dy0 + 16 < -ro) continue;
+                const int hi = rr * rr, lo = ball ? m.rbi16 * m.rbi16 : -1, ho = ro * ro;
+                const uint32_t color = (uint32_t)e.z & MM_WHITE;
+                #pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int dy = dy0 + 16 * r;
+                    #pragma unroll
+                    for (int k = 0; k < AN_STRIP; ++k) {
+                        const int dx = dx0 + 16 * k, d2 = dx * dx + dy * dy;      // (|dx|, |dy| <= ro + 112 <= 2832 here: 32 bits hold it)
+                        if (d2 <= hi && d2 > lo) px[r][k] = (e.z & MM_DIM_BIT) ? mm_blend(px[r][k], color, MM_DIM_A) : color;
+                        else if (d2 > hi && d2 <= ho) px[r][k] = MM_WHITE;
+                    }
+                }
+                continue;
+            }
             if (dx0 > rr || dx0 + 16 * (AN_STRIP - 1) < -rr || dy0 > rr || dy0 + 16 < -rr) continue;
             const int hi = rr * rr, lo = ball ? m.rbi16 * m.rbi16 : -1;
             const uint32_t color = ball ? MM_WHITE : (uint32_t)e.z & MM_WHITE;
@@ -264,11 +402,15 @@ __global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m)
     if (live) write_strip(a, f, x0, y0, cnt, rows, px);
 }
 
+__global__ __launch_bounds__(AN_THREADS) void minimap_kernel(MinimapArgs m) { mm_draw<false>(m, nullptr); }
+__global__ __launch_bounds__(AN_THREADS) void minimap_layers_kernel(MinimapArgs m, MmLayerArgs la) { mm_draw<true>(m, &la); }
+
 // rows row0 .. row0 + n - 1 -> n pictures; the lists buffer holds min(n, MM_PASS) rows and is reused pass by pass (same stream: ordered)
 static constexpr int MM_PASS = 65535;                  // gridDim.y limit
 static constexpr int64_t MM_STAGING = (int64_t)32 << 20;      // eagle_minimap_frames: device + pinned staging per pass (21 BGR pictures at 8 px per metre; a pass
                                                               // of that size moves for a millisecond or more, against which its two launches and one wait vanish)
-static void minimap_launch(const MinimapArgs& args, hipStream_t s)
+// la: the K25 layers (nullptr: the plain pair of launches); still: the trajectory still, whose one list trail_marks_kernel writes
+static void minimap_launch(const MinimapArgs& args, hipStream_t s, const MmLayerArgs* la = nullptr, bool still = false)
 {
     MinimapArgs m = args;
     const int tiles = (m.out.w + AN_TW - 1) / AN_TW * ((m.out.h + AN_TH - 1) / AN_TH);
@@ -277,6 +419,14 @@ static void minimap_launch(const MinimapArgs& args, hipStream_t s)
         m.row0 = args.row0 + f0;
         m.out.dst = args.out.dst + (int64_t)f0 * args.out.frame_stride;
         if (args.grid) m.grid = args.grid + (size_t)f0 * args.ctl_gw * args.ctl_gh;
+        if (la) {
+            if (still) trail_marks_launch(la->pts, la->sel, la->nsel, la->prows, m.lists, s);
+            else hipLaunchKernelGGL(minimap_sites_layers_kernel, dim3((m.n + 255) / 256), dim3(256), 0, s, m, *la);
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(minimap_layers_kernel, dim3(tiles, m.n), dim3(AN_THREADS), 0, s, m, *la);
+            HIP_CHECK(hipGetLastError());
+            continue;
+        }
         hipLaunchKernelGGL(minimap_sites_kernel, dim3((m.n + 255) / 256), dim3(256), 0, s, m);
         HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(minimap_kernel, dim3(tiles, m.n), dim3(AN_THREADS), 0, s, m);
@@ -293,6 +443,7 @@ MmPlan minimap_plan(const EagleMinimapParams* p)
     if (p->player_radius < 0 || p->player_radius > 4 * p->scale || p->ball_radius < 0 || p->ball_radius > 4 * p->scale)
         fail(EAGLE_E_INVALID, "minimap: radii %d / %d must lie within 0 .. 4 x scale = %d (0: the default)", p->player_radius, p->ball_radius, 4 * p->scale);
     if (p->control && p->voronoi) fail(EAGLE_E_INVALID, "minimap: control and voronoi draw in the same slot: choose one");
+    if (p->layers & ~(EAGLE_MM_TRAILS | EAGLE_MM_PASSES | EAGLE_MM_OWNER)) fail(EAGLE_E_INVALID, "minimap: layers 0x%x has unknown bits", (unsigned)p->layers);
     MmPlan pl;
     pl.S = p->scale; pl.M = p->margin;
     pl.w = 105 * pl.S + 2 * pl.M; pl.h = 68 * pl.S + 2 * pl.M;
@@ -444,13 +595,14 @@ static MinimapArgs minimap_prepare(EagleHandle* h, EaglePostTable* t, const MmPl
 }
 
 // rows row0 .. row0 + n - 1 -> n pictures at d_out (layout g) on s_main; returns when they are complete
-static void minimap_pass(EagleHandle* h, const MinimapArgs& prepared, int row0, int n, const YuvGeom& g, uint8_t* d_out, const ControlArgs* ctl = nullptr)
+static void minimap_pass(EagleHandle* h, const MinimapArgs& prepared, int row0, int n, const YuvGeom& g, uint8_t* d_out, const ControlArgs* ctl = nullptr,
+                         const MmLayerArgs* la = nullptr, bool still = false)
 {
     MinimapArgs m = prepared;
     m.out = annot_args(g, nullptr, d_out, nullptr, nullptr);
     m.row0 = row0; m.n = n;
     if (ctl) control_rows(h, *ctl, row0, n, (uint8_t*)h->ct_grid, nullptr);      // the grids of these rows, on the same stream in front of the draw
-    timed_launch(h, "minimap", minimap_bytes(m, g), h->s_main, [&] { minimap_launch(m, h->s_main); });
+    timed_launch(h, la ? "minimap_layers" : "minimap", minimap_bytes(m, g), h->s_main, [&] { minimap_launch(m, h->s_main, la, still); });
     HIP_CHECK(hipStreamSynchronize(h->s_main));
     if (h->prof) collect_spans(h);
 }
@@ -466,9 +618,186 @@ static MmPlan minimap_begin(EagleHandle* h, EaglePostTable* t, int row0, int n, 
         if (!t->d_vel) fail(EAGLE_E_INVALID, "minimap: control needs the table's velocities (eagle_post_velocities comes first)");
         if (!t->has_control) fail(EAGLE_E_INVALID, "minimap: control needs its parameters (eagle_minimap_set_control comes first)");
     }
+    if (p->layers) {
+        if (!t->has_trails) fail(EAGLE_E_INVALID, "minimap: layers need their parameters (eagle_minimap_set_trails comes first)");
+        if ((p->layers & (EAGLE_MM_PASSES | EAGLE_MM_OWNER)) && !t->has_poss)
+            fail(EAGLE_E_INVALID, "minimap: the pass and owner layers need a possession result (eagle_post_possession comes first)");
+        if ((p->layers & EAGLE_MM_TRAILS) && t->trail_cols.empty()) fail(EAGLE_E_INVALID, "minimap: the trail layer needs a selection (eagle_minimap_set_trails was given none)");
+    }
     minimap_window(t->rows, row0, n);
     HIP_CHECK(hipSetDevice(h->cfg.device));
     return pl;
+}
+
+// ---- the K25 layers: host side ---------------------------------------------------------------------------------------------------------
+void trail_check(const char* who, const EagleTrailParams* p)
+{
+    if (!p) fail(EAGLE_E_INVALID, "%s: the trail parameters are NULL", who);
+    if (p->window < 1) fail(EAGLE_E_INVALID, "%s: window %d must be at least 1 row", who, p->window);
+    if (p->max_gap < 1) fail(EAGLE_E_INVALID, "%s: max_gap %d must be at least 1 frame", who, p->max_gap);
+    if (p->half_width < 1 || p->half_width > 8) fail(EAGLE_E_INVALID, "%s: half_width %d must lie within 1 .. 8 pixels", who, p->half_width);
+    if (p->pass_hold < 1) fail(EAGLE_E_INVALID, "%s: pass_hold %d must be at least 1 row", who, p->pass_hold);
+    if (p->dim_floor < 0 || p->dim_floor > 256) fail(EAGLE_E_INVALID, "%s: dim_floor %d must lie within 0 .. 256", who, p->dim_floor);
+}
+
+void trail_selection_check(const char* who, const EaglePostColumn* columns, int ncols, const int32_t* sel, int nsel)
+{
+    if (nsel < 0 || (nsel > 0 && !sel)) fail(EAGLE_E_INVALID, "%s: bad selection (%p, %d members)", who, (const void*)sel, nsel);
+    if (nsel > 65535) fail(EAGLE_E_INVALID, "%s: a selection of %d columns is beyond 65535", who, nsel);
+    std::vector<uint8_t> seen((size_t)std::max(ncols, 1), 0);
+    for (int k = 0; k < nsel; ++k) {
+        const int c = sel[k];
+        if (c < 0 || c >= ncols) fail(EAGLE_E_INVALID, "%s: selection member %d (column %d) lies outside the table's %d columns", who, k, c, ncols);
+        if (columns[c].video || (columns[c].kind != EAGLE_POST_PLAYER && columns[c].kind != EAGLE_POST_GOALKEEPER && columns[c].kind != EAGLE_POST_BALL))
+            fail(EAGLE_E_INVALID, "%s: selection member %d (column %d) is not a Player, Goalkeeper or Ball pitch column", who, k, c);
+        if (seen[c]) fail(EAGLE_E_INVALID, "%s: column %d is selected twice", who, c);
+        seen[c] = 1;
+    }
+}
+
+// the selected columns that have a colour (their disc's), in selection order
+static std::vector<MmCol> trail_selection(const EaglePostColumn* columns, int ncols, bool has_team, const int32_t* team_ids, const int32_t* team_vals, size_t n_team,
+                                          const int32_t* sel, int nsel)
+{
+    std::vector<MmCol> drawn, out;
+    int corner[4];
+    minimap_columns(columns, ncols, has_team, team_ids, team_vals, n_team, drawn, corner);
+    for (int k = 0; k < nsel; ++k)
+        for (const MmCol& d : drawn)
+            if (d.col == sel[k]) { out.push_back(d); break; }
+    return out;
+}
+
+// device memory of the layers of one call.  With a handle the buffers are the handle's (mm_tr, grown on demand like the draw lists: no allocation and
+// no device-wide synchronisation per call); an operator entry owns them for the call and frees them when it ends (after the device has been synchronised)
+enum { TR_SEL, TR_FRAMES, TR_PTS, TR_LINK, TR_EVSRC, TR_EV, TR_RANGE, TR_OUT };
+struct DevTmp {
+    EagleHandle* h = nullptr;
+    int slot = 0;                                          // the next slot of h->mm_tr (layers_setup asks in a fixed order)
+    std::vector<void*> own;
+    explicit DevTmp(EagleHandle* hh = nullptr) : h(hh) {}
+    ~DevTmp() { for (void* q : own) (void)hipFree(q); }
+    void* get(size_t b, int k)
+    {
+        if (h) { grow(&h->mm_tr[k], &h->mm_tr_cap[k], std::max<size_t>(b, 16)); return h->mm_tr[k]; }
+        void* q = nullptr; HIP_CHECK(hipMalloc(&q, std::max<size_t>(b, 16))); own.push_back(q); return q;
+    }
+    void* upload(const void* src, size_t b, hipStream_t s, int k)
+    {
+        void* q = get(b, k);
+        if (b) HIP_CHECK(hipMemcpyAsync(q, src, b, hipMemcpyHostToDevice, s));
+        return q;
+    }
+};
+
+struct LayerJob {
+    int layers = 0;
+    EagleTrailParams tp{};
+    std::vector<MmCol> sel;              // (trails or the trajectory still)
+    const int32_t* d_owner = nullptr;    // [rows] in HBM
+    const EaglePossessionEvent* events = nullptr;
+    int nev = 0;
+    int only_event = -1;                 // >= 0: the pass still
+    bool trajectory = false;             // the trajectory still of rows row0 .. row0 + n - 1
+};
+
+// everything the layered launches of rows row0 .. row0 + n - 1 read, prepared on stream s (which is synchronised before the host vectors go)
+static MmLayerArgs layers_setup(DevTmp& tmp, hipStream_t s, const double2* d_values, int rows, const int32_t* frames, const MmPlan& pl, const LayerJob& job, int row0, int n)
+{
+    MmLayerArgs la{};
+    const EagleTrailParams& tp = job.tp;
+    la.window = tp.window; la.dim_floor = tp.dim_floor; la.hw16 = 16 * tp.half_width; la.pass_hold = tp.pass_hold;
+    la.jlo = -1; la.range_row0 = row0; la.pass_from = la.pass_to = -1;
+    la.r16o = 16 * (pl.r + std::max(1, pl.r / 3));
+    std::vector<int2> range;
+    if (((job.layers & EAGLE_MM_TRAILS) || job.trajectory) && !job.sel.empty()) {
+        la.nsel = (int)job.sel.size();
+        la.prow0 = job.trajectory || tp.window > row0 ? (job.trajectory ? row0 : 0) : row0 - tp.window;
+        la.prows = row0 + n - la.prow0;
+        if ((int64_t)la.nsel * la.prows > 0x7fffffff) fail(EAGLE_E_INVALID, "minimap: %d selected columns x %d rows of trail is beyond 2^31 segments", la.nsel, la.prows);
+        if (job.trajectory) { la.jlo = row0 + 1; la.dim_floor = 256; la.window = std::max(1, n - 1); }
+        la.sel = (const MmCol*)tmp.upload(job.sel.data(), job.sel.size() * sizeof(MmCol), s, TR_SEL);
+        const int32_t* d_frames = (const int32_t*)tmp.upload(frames + la.prow0, (size_t)la.prows * 4, s, TR_FRAMES);
+        int2* pts = (int2*)tmp.get((size_t)la.nsel * la.prows * sizeof(int2), TR_PTS);
+        uint8_t* link = (uint8_t*)tmp.get((size_t)la.prows, TR_LINK);
+        trail_points_launch(d_values, rows, la.sel, la.nsel, d_frames, la.prow0, la.prows, tp.max_gap, pl.S, pl.M, pts, link, s);
+        la.pts = pts; la.link = link;
+    }
+    if (((job.layers & EAGLE_MM_PASSES) || job.only_event >= 0) && job.nev > 0) {
+        const EaglePossessionEvent* d_ev = (const EaglePossessionEvent*)tmp.upload(job.events, (size_t)job.nev * sizeof(EaglePossessionEvent), s, TR_EVSRC);
+        int4* out = (int4*)tmp.get((size_t)job.nev * 3 * sizeof(int4), TR_EV);
+        trail_events_launch(d_ev, job.nev, pl.S, pl.M, tp.half_width, out, s);
+        la.ev = out;
+        range.resize((size_t)n);
+        if (job.only_event >= 0) {
+            la.only = 1;
+            range[0] = make_int2(job.only_event, job.only_event + 1);
+        } else {
+            // release_row and receive_row ascend with the events: those with release_row <= r are a prefix, those with r < receive_row + hold a suffix
+            int lo = 0, hi = 0;
+            for (int i = 0; i < n; ++i) {
+                const int r = row0 + i;
+                while (hi < job.nev && job.events[hi].release_row <= r) ++hi;
+                while (lo < job.nev && (int64_t)job.events[lo].receive_row + tp.pass_hold <= r) ++lo;
+                range[i] = make_int2(std::min(lo, hi), hi);
+            }
+        }
+        la.ev_range = (const int2*)tmp.upload(range.data(), range.size() * sizeof(int2), s, TR_RANGE);
+    }
+    if (job.only_event >= 0 && job.nev > 0) {
+        la.dim = 1; la.pass_from = job.events[job.only_event].from_col; la.pass_to = job.events[job.only_event].to_col;
+    }
+    if (job.layers & EAGLE_MM_OWNER) la.owner = job.d_owner;
+    HIP_CHECK(hipStreamSynchronize(s));                    // (pageable sources: they have left the vectors)
+    return la;
+}
+
+static LayerJob table_job(EaglePostTable* t, int layers)
+{
+    LayerJob job;
+    job.layers = layers; job.tp = t->trails;
+    if (layers & EAGLE_MM_TRAILS)
+        job.sel = trail_selection(t->columns.data(), t->cols, t->has_team, t->team_ids.data(), t->team_vals.data(), t->team_ids.size(), t->trail_cols.data(), (int)t->trail_cols.size());
+    if (t->has_poss) {
+        job.d_owner = t->rows ? (const int32_t*)((const double*)t->d_poss + t->rows) + t->rows : nullptr;
+        job.events = t->events.data(); job.nev = (int)t->events.size();
+    }
+    if (!job.d_owner) job.layers &= ~EAGLE_MM_OWNER;
+    return job;
+}
+
+static void events_check(const char* who, const EaglePossessionEvent* ev, int nev, int rows)
+{
+    if (nev < 0 || (nev > 0 && !ev)) fail(EAGLE_E_INVALID, "%s: bad events (%p, %d)", who, (const void*)ev, nev);
+    for (int k = 0; k < nev; ++k) {
+        if (ev[k].release_row < 0 || ev[k].release_row >= rows || ev[k].receive_row < 0 || ev[k].receive_row >= rows || ev[k].kind < 0 || ev[k].kind > EAGLE_EVENT_UNKNOWN)
+            fail(EAGLE_E_INVALID, "%s: event %d has rows %d, %d outside the table's %d rows or kind %d", who, k, ev[k].release_row, ev[k].receive_row, rows, ev[k].kind);
+        if (k && (ev[k].release_row < ev[k - 1].release_row || ev[k].receive_row < ev[k - 1].receive_row))
+            fail(EAGLE_E_INVALID, "%s: the rows of event %d do not ascend", who, k);
+    }
+}
+
+// a still of a handle's table: one picture of row `row0` (pass) or of the window (trajectory) -> host memory, BGR
+static void handle_still(EagleHandle* h, EaglePostTable* t, const MmPlan& pl, const EagleMinimapParams* p, const LayerJob& job, int row0, int n, uint8_t* out)
+{
+    HIP_CHECK(hipSetDevice(h->cfg.device));
+    const YuvGeom g = yuv_geometry(EAGLE_PIX_BGR, pl.h, pl.w, nullptr, true);
+    DevTmp tmp(h);
+    try {
+        MinimapArgs m = minimap_prepare(h, t, pl, p, 1);
+        if (job.trajectory) {                              // its list has two entries per selected column, written by trail_marks_kernel
+            m.ncols = 2 * (int)job.sel.size(); m.stride = MM_HEAD + m.ncols;
+            grow(&h->mm_list, &h->mm_list_cap, (size_t)m.stride * sizeof(int4));
+            m.lists = (int4*)h->mm_list;
+        }
+        const MmLayerArgs la = layers_setup(tmp, h->s_main, (const double2*)t->d_values, t->rows, t->frames.data(), pl, job, row0, n);
+        uint8_t* d_out = (uint8_t*)tmp.get((size_t)g.dense_bytes, TR_OUT);
+        minimap_pass(h, m, job.trajectory ? row0 + n - 1 : row0, 1, g, d_out, nullptr, &la, job.trajectory);
+        HIP_CHECK(hipMemcpy(out, d_out, (size_t)g.dense_bytes, hipMemcpyDeviceToHost));
+    } catch (...) {
+        (void)hipStreamSynchronize(h->s_main);
+        throw;
+    }
 }
 
 // the control layer of a handle call: grid space for passes of up to max_pass rows in the handle, the prepared site columns; m learns where the grids are
@@ -500,8 +829,15 @@ int eagle_minimap_device_frames(EagleHandle* h, EaglePostTable* t, int row0, int
     const MmPlan pl = minimap_begin(h, t, row0, n, p, d_out);
     const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
     if (n == 0) return EAGLE_OK;
+    DevTmp tmp(h);
+    MmLayerArgs la{};
+    const MmLayerArgs* lap = nullptr;
+    if (p->layers) {
+        la = layers_setup(tmp, h->s_main, (const double2*)t->d_values, t->rows, t->frames.data(), pl, table_job(t, p->layers), row0, n);
+        lap = &la;
+    }
     if (!p->control) {
-        minimap_pass(h, minimap_prepare(h, t, pl, p, n), row0, n, g, (uint8_t*)d_out);
+        minimap_pass(h, minimap_prepare(h, t, pl, p, n), row0, n, g, (uint8_t*)d_out, nullptr, lap);
         return EAGLE_OK;
     }
     // with the control layer the rows go in passes of what MM_STAGING bytes of grids hold (grids, then their draw), so the handle keeps one pass of grids
@@ -510,7 +846,7 @@ int eagle_minimap_device_frames(EagleHandle* h, EaglePostTable* t, int row0, int
     MinimapArgs m = minimap_prepare(h, t, pl, p, batch);
     const ControlArgs ctl = minimap_control(h, t, m, batch);
     for (int i = 0; i < n; i += batch)
-        minimap_pass(h, m, row0 + i, std::min(batch, n - i), g, (uint8_t*)d_out + (int64_t)i * g.frame_stride, &ctl);
+        minimap_pass(h, m, row0 + i, std::min(batch, n - i), g, (uint8_t*)d_out + (int64_t)i * g.frame_stride, &ctl, lap);
     API_END(h)
 }
 
@@ -525,14 +861,30 @@ int eagle_minimap_frames(EagleHandle* h, EaglePostTable* t, int row0, int n, con
     MinimapArgs m = minimap_prepare(h, t, pl, p, batch);
     ControlArgs ctl{};
     if (p->control) ctl = minimap_control(h, t, m, batch);
+    DevTmp tmp(h);
+    MmLayerArgs la{};
+    const MmLayerArgs* lap = nullptr;
+    if (p->layers) {
+        la = layers_setup(tmp, h->s_main, (const double2*)t->d_values, t->rows, t->frames.data(), pl, table_job(t, p->layers), row0, n);
+        lap = &la;
+    }
     frames_to_host(h, n, pl.h, pl.w, batch, out_format, out_layout, out,
-                   [&](int i, int na, const YuvGeom& dg, uint8_t* d_dst) { minimap_pass(h, m, row0 + i, na, dg, d_dst, p->control ? &ctl : nullptr); });
+                   [&](int i, int na, const YuvGeom& dg, uint8_t* d_dst) { minimap_pass(h, m, row0 + i, na, dg, d_dst, p->control ? &ctl : nullptr, lap); });
     API_END(h)
 }
 
+struct OpLayers {                                          // what eagle_op_minimap_trails and the still entries add to op_minimap
+    const int32_t* frames = nullptr;
+    const int32_t* owner = nullptr;                        // host, [rows]
+    const int32_t* sel = nullptr;
+    int nsel = 0;
+    LayerJob job;
+    bool on = false;
+};
+
 static void op_minimap(const char* who, int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
                        const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleControlParams* cp, int row0, int n, int out_format,
-                       const EagleYuvLayout* out_layout, uint8_t* out)
+                       const EagleYuvLayout* out_layout, uint8_t* out, OpLayers* ol = nullptr)
 {
     if (!values || !columns || !out || rows < 0 || cols < 0 || n_team < 0 || (team_ids && n_team > 0 && !team_vals))
         fail(EAGLE_E_INVALID, "%s: bad argument (values %p, columns %p, out %p, %d rows, %d columns, %d teams)", who, (const void*)values, (const void*)columns,
@@ -544,16 +896,35 @@ static void op_minimap(const char* who, int device, const double* values, const 
         if (!velocities) fail(EAGLE_E_INVALID, "minimap: control needs velocities (eagle_op_minimap_control takes them)");
         control_check(cp);
     }
+    if (p->layers && !(ol && ol->on)) fail(EAGLE_E_INVALID, "%s: layers need their parameters (eagle_op_minimap_trails takes them)", who);
     minimap_window(rows, row0, n);
+    const bool trajectory = ol && ol->job.trajectory;
+    if (trajectory && n < 1) fail(EAGLE_E_INVALID, "%s: a window of %d rows", who, n);
+    const int pics = trajectory ? 1 : n;
     const YuvGeom g = yuv_geometry(out_format, pl.h, pl.w, out_layout, true);
     std::vector<MmCol> dc;
     MinimapArgs m = minimap_args(pl, p);
     minimap_columns(columns, cols, team_ids != nullptr, team_ids, team_vals, (size_t)n_team, dc, m.corner);
     m.ncols = (int)dc.size();
+    if (ol && ol->on) {
+        LayerJob& job = ol->job;
+        if ((job.layers & EAGLE_MM_TRAILS) || trajectory) {
+            if (!ol->frames) fail(EAGLE_E_INVALID, "%s: trails need the frame numbers", who);
+            for (int r = 1; r < rows; ++r)
+                if (ol->frames[r] <= ol->frames[r - 1]) fail(EAGLE_E_INVALID, "%s: frame numbers must ascend (row %d: %d after %d)", who, r, ol->frames[r], ol->frames[r - 1]);
+            trail_selection_check(who, columns, cols, ol->sel, ol->nsel);
+            if ((job.layers & EAGLE_MM_TRAILS) && ol->nsel == 0) fail(EAGLE_E_INVALID, "%s: the trail layer needs a selection", who);
+            job.sel = trail_selection(columns, cols, team_ids != nullptr, team_ids, team_vals, (size_t)n_team, ol->sel, ol->nsel);
+        }
+        if ((job.layers & EAGLE_MM_OWNER) && !ol->owner) fail(EAGLE_E_INVALID, "%s: the owner layer needs owner[rows] (a possession result)", who);
+        if ((job.layers & EAGLE_MM_PASSES) && !job.events) fail(EAGLE_E_INVALID, "%s: the pass layer needs events (a possession result)", who);
+        if ((job.layers & EAGLE_MM_PASSES) || job.only_event >= 0) events_check(who, job.events, job.nev, rows);
+        if (trajectory) { m.ncols = 2 * (int)job.sel.size(); }
+    }
     if (n == 0) return;
     HIP_CHECK(hipSetDevice(device));
     Net net;
-    const size_t span = (size_t)((n - 1) * g.frame_stride + g.extent);
+    const size_t span = (size_t)((pics - 1) * g.frame_stride + g.extent);
     int mp = 0;
     const std::vector<uint8_t> bits = markings_mask(pl, &mp);
     uint8_t* d_out = (uint8_t*)net.upload(out, span);                        // bytes the layout does not cover come back as they were
@@ -562,8 +933,8 @@ static void op_minimap(const char* who, int device, const double* values, const 
     dc.resize(std::max<size_t>(dc.size(), 2), MmCol{0, 0});                  // (a table without a drawable column still uploads 16 bytes; ncols says how many count)
     m.cols = (const MmCol*)net.upload(dc.data(), dc.size() * sizeof(MmCol));
     m.mask = (const uint8_t*)net.upload(bits.data(), bits.size());
-    m.rows = rows; m.row0 = row0; m.n = n; m.stride = MM_HEAD + m.ncols;
-    m.lists = (int4*)net.get((size_t)std::min(n, MM_PASS) * m.stride * sizeof(int4));
+    m.rows = rows; m.row0 = trajectory ? row0 + n - 1 : row0; m.n = pics; m.stride = MM_HEAD + m.ncols;
+    m.lists = (int4*)net.get((size_t)std::min(pics, MM_PASS) * m.stride * sizeof(int4));
     if (p->control) {                                                        // the grids of the window, in front of the draw on the same (null) stream
         std::vector<CtCol> sc;
         control_columns(columns, cols, team_ids, team_vals, (size_t)n_team, sc);
@@ -582,6 +953,16 @@ static void op_minimap(const char* who, int device, const double* values, const 
             control_launch(b, nullptr);
         }
         m.grid = d_g; m.ctl_R = c.R; m.ctl_gw = c.gw; m.ctl_gh = c.gh;
+    }
+    if (ol && ol->on) {
+        HIP_CHECK(hipDeviceSynchronize());                 // (Net::get clears its buffers on the null stream)
+        DevTmp tmp;
+        if (ol->job.layers & EAGLE_MM_OWNER) ol->job.d_owner = (const int32_t*)tmp.upload(ol->owner, (size_t)rows * 4, nullptr, TR_OUT);
+        const MmLayerArgs la = layers_setup(tmp, nullptr, m.values, rows, ol->frames, pl, ol->job, row0, n);
+        minimap_launch(m, nullptr, &la, trajectory);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, d_out, span, hipMemcpyDeviceToHost));
+        return;
     }
     minimap_launch(m, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
@@ -604,6 +985,119 @@ int eagle_op_minimap_control(int device, const double* values, const double* vel
     EagleHandle* hh = nullptr;
     API_BEGIN
     op_minimap("eagle_op_minimap_control", device, values, velocities, columns, rows, cols, team_ids, team_vals, n_team, p, cp, row0, n, out_format, out_layout, out);
+    API_END(hh)
+}
+
+int eagle_minimap_set_trails(EaglePostTable* t, const EagleTrailParams* p, const int32_t* cols, int ncols)
+{
+    if (!t) return EAGLE_E_INVALID;
+    EagleHandle* h = t->h;
+    API_BEGIN
+    if (p) {
+        trail_check("eagle_minimap_set_trails", p);
+        trail_selection_check("eagle_minimap_set_trails", t->columns.data(), t->cols, cols, ncols);
+        t->trails = *p;
+        t->trail_cols.assign(cols, cols + ncols);
+    } else t->trail_cols.clear();
+    t->has_trails = p != nullptr;
+    API_END(h)
+}
+
+int eagle_trajectory_picture(EagleHandle* h, EaglePostTable* t, const int32_t* cols, int ncols, int row0, int n, int scale, int margin, int half_width, int max_gap,
+                             uint8_t* out)
+{
+    API_BEGIN_H(h)
+    if (!t || !out) fail(EAGLE_E_INVALID, "eagle_trajectory_picture: bad argument (table %p, out %p)", (const void*)t, (const void*)out);
+    if (t->h != h) fail(EAGLE_E_INVALID, "eagle_trajectory_picture: the table belongs to another handle");
+    EagleMinimapParams p{};
+    p.scale = scale; p.margin = margin;
+    const MmPlan pl = minimap_plan(&p);
+    LayerJob job;
+    job.tp.window = 1; job.tp.max_gap = max_gap; job.tp.half_width = half_width; job.tp.pass_hold = 1; job.tp.dim_floor = 256;
+    trail_check("eagle_trajectory_picture", &job.tp);
+    trail_selection_check("eagle_trajectory_picture", t->columns.data(), t->cols, cols, ncols);
+    minimap_window(t->rows, row0, n);
+    if (n < 1) fail(EAGLE_E_INVALID, "eagle_trajectory_picture: a window of %d rows", n);
+    job.trajectory = true;
+    job.sel = trail_selection(t->columns.data(), t->cols, t->has_team, t->team_ids.data(), t->team_vals.data(), t->team_ids.size(), cols, ncols);
+    handle_still(h, t, pl, &p, job, row0, n, out);
+    API_END(h)
+}
+
+int eagle_pass_picture(EagleHandle* h, EaglePostTable* t, int event, int scale, int margin, int half_width, uint8_t* out)
+{
+    API_BEGIN_H(h)
+    if (!t || !out) fail(EAGLE_E_INVALID, "eagle_pass_picture: bad argument (table %p, out %p)", (const void*)t, (const void*)out);
+    if (t->h != h) fail(EAGLE_E_INVALID, "eagle_pass_picture: the table belongs to another handle");
+    EagleMinimapParams p{};
+    p.scale = scale; p.margin = margin;
+    const MmPlan pl = minimap_plan(&p);
+    LayerJob job;
+    job.tp.window = 1; job.tp.max_gap = 1; job.tp.half_width = half_width; job.tp.pass_hold = 1; job.tp.dim_floor = 256;
+    trail_check("eagle_pass_picture", &job.tp);
+    if (!t->has_poss) fail(EAGLE_E_INVALID, "eagle_pass_picture: the table has no possession result (eagle_post_possession comes first)");
+    if (event < 0 || event >= (int)t->events.size()) fail(EAGLE_E_INVALID, "eagle_pass_picture: event %d lies outside the table's %d events", event, (int)t->events.size());
+    job.events = t->events.data(); job.nev = (int)t->events.size(); job.only_event = event;
+    handle_still(h, t, pl, &p, job, t->events[event].release_row, 1, out);
+    API_END(h)
+}
+
+int eagle_op_minimap_trails(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                            const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleTrailParams* tp, const int32_t* sel, int nsel,
+                            const int32_t* owner, const EaglePossessionEvent* events, int n_events, int row0, int n, int out_format, const EagleYuvLayout* out_layout,
+                            uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    const char* who = "eagle_op_minimap_trails";
+    if (!p) fail(EAGLE_E_INVALID, "minimap: params is NULL");
+    if (p->control) fail(EAGLE_E_INVALID, "%s: the control layer is not available here (it needs velocities)", who);
+    OpLayers ol;
+    if (p->layers) {
+        if (!tp) fail(EAGLE_E_INVALID, "%s: a layer without trail parameters", who);
+        trail_check(who, tp);
+        ol.on = true; ol.frames = frames; ol.owner = owner; ol.sel = sel; ol.nsel = nsel;
+        ol.job.layers = p->layers; ol.job.tp = *tp; ol.job.events = events; ol.job.nev = n_events;
+    }
+    op_minimap(who, device, values, nullptr, columns, rows, cols, team_ids, team_vals, n_team, p, nullptr, row0, n, out_format, out_layout, out, &ol);
+    API_END(hh)
+}
+
+int eagle_op_trajectory_picture(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                                const int32_t* team_vals, int n_team, const int32_t* sel, int nsel, int row0, int n, int scale, int margin, int half_width, int max_gap,
+                                uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    const char* who = "eagle_op_trajectory_picture";
+    EagleMinimapParams p{};
+    p.scale = scale; p.margin = margin;
+    OpLayers ol;
+    ol.on = true; ol.frames = frames; ol.sel = sel; ol.nsel = nsel;
+    ol.job.trajectory = true;
+    ol.job.tp.window = 1; ol.job.tp.max_gap = max_gap; ol.job.tp.half_width = half_width; ol.job.tp.pass_hold = 1; ol.job.tp.dim_floor = 256;
+    trail_check(who, &ol.job.tp);
+    op_minimap(who, device, values, nullptr, columns, rows, cols, team_ids, team_vals, n_team, &p, nullptr, row0, n, EAGLE_PIX_BGR, nullptr, out, &ol);
+    API_END(hh)
+}
+
+int eagle_op_pass_picture(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
+                          int n_team, const EaglePossessionEvent* events, int n_events, int event, int scale, int margin, int half_width, uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    const char* who = "eagle_op_pass_picture";
+    EagleMinimapParams p{};
+    p.scale = scale; p.margin = margin;
+    OpLayers ol;
+    ol.on = true;
+    ol.job.tp.window = 1; ol.job.tp.max_gap = 1; ol.job.tp.half_width = half_width; ol.job.tp.pass_hold = 1; ol.job.tp.dim_floor = 256;
+    trail_check(who, &ol.job.tp);
+    if (!events || n_events < 0) fail(EAGLE_E_INVALID, "%s: bad events (%p, %d)", who, (const void*)events, n_events);
+    if (event < 0 || event >= n_events) fail(EAGLE_E_INVALID, "%s: event %d lies outside the %d events", who, event, n_events);
+    events_check(who, events, n_events, rows);
+    ol.job.events = events; ol.job.nev = n_events; ol.job.only_event = event;
+    op_minimap(who, device, values, nullptr, columns, rows, cols, team_ids, team_vals, n_team, &p, nullptr, events[event].release_row, 1, EAGLE_PIX_BGR, nullptr, out, &ol);
     API_END(hh)
 }
 

@@ -258,6 +258,8 @@ struct EagleHandle {
     // minimap (minimap.hip): the draw lists of the call being run, the drawable columns and the marking mask of the last (scale, margin); grown on demand
     void* mm_list = nullptr; size_t mm_list_cap = 0;
     void* mm_cols = nullptr; size_t mm_cols_cap = 0;
+    // the K25 layers of the call being run (minimap.hip layers_setup): selection, frame numbers, points, links, events, prepared events, event ranges, still picture
+    void* mm_tr[8] = {}; size_t mm_tr_cap[8] = {};
     uint8_t* mm_mask = nullptr; size_t mm_mask_cap = 0; int mm_mask_scale = 0, mm_mask_margin = -1;
     // pitch control (control.hip): the site lists and site columns of the call being run, and the grids the minimap's control layer reads; grown on demand
     void* ct_list = nullptr; size_t ct_list_cap = 0;
@@ -290,6 +292,9 @@ struct EaglePostTable {
     void* d_occ = nullptr;               // occupancy (eagle_post_occupancy): grids f32 | counts i32 | bytes u8, [occ_nsel][gh][gw] each, then total | outside | max
     int occ_nsel = 0, occ_R = 0;         // u32 [occ_nsel] each; resident until eagle_post_free
     bool has_occ = false;
+    bool has_trails = false;             // eagle_minimap_set_trails
+    EagleTrailParams trails{};
+    std::vector<int32_t> trail_cols;
 };
 
 namespace eagle {

@@ -164,6 +164,7 @@ void eagle_destroy(EagleHandle* h)
     if (h->annot_ring) (void)hipHostFree(h->annot_ring);
     if (h->mm_list) (void)hipFree(h->mm_list);
     if (h->mm_cols) (void)hipFree(h->mm_cols);
+    for (void* q : h->mm_tr) if (q) (void)hipFree(q);
     if (h->mm_mask) (void)hipFree(h->mm_mask);
     if (h->ct_list) (void)hipFree(h->ct_list);
     if (h->ct_cols) (void)hipFree(h->ct_cols);

@@ -71,7 +71,16 @@ class EaglePostParams(C.Structure):
 class EagleMinimapParams(C.Structure):
     """include/eagle.h EagleMinimapParams: pixels per metre, margin, the two optional layers, radii in pixels (0 = the default)."""
     _fields_ = [("scale", C.c_int32), ("margin", C.c_int32), ("voronoi", C.c_int32), ("footprint", C.c_int32), ("player_radius", C.c_int32),
-                ("ball_radius", C.c_int32), ("control", C.c_int32), ("reserved", C.c_int32)]
+                ("ball_radius", C.c_int32), ("control", C.c_int32), ("layers", C.c_int32)]
+
+
+class EagleTrailParams(C.Structure):
+    """include/eagle.h EagleTrailParams: rows a trail looks back, the largest frame step inside a trail, half the line width (px), rows an arrow stays
+    after the receive row, the brightness (of 256) the oldest segment fades towards."""
+    _fields_ = [("window", C.c_int32), ("max_gap", C.c_int32), ("half_width", C.c_int32), ("pass_hold", C.c_int32), ("dim_floor", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+MM_TRAILS, MM_PASSES, MM_OWNER = 1, 2, 4                                # include/eagle.h EAGLE_MM_*
 
 
 class EagleKinematicsParams(C.Structure):
@@ -253,6 +262,13 @@ def load():
     L.eagle_occupancy_picture.argtypes = [vp, vp, i32, i32, i32, C.c_uint32, vp]
     L.eagle_op_occupancy.argtypes = [i32, vp, vp, vp, i32, i32, op, vp, vp, i32, vp, vp, vp, vp, vp]
     L.eagle_op_occupancy_picture.argtypes = [i32, vp, i32, i32, i32, C.c_uint32, vp]
+    tp = C.POINTER(EagleTrailParams)
+    L.eagle_minimap_set_trails.argtypes = [vp, tp, vp, i32]
+    L.eagle_trajectory_picture.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.eagle_pass_picture.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    L.eagle_op_minimap_trails.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, tp, vp, i32, vp, vp, i32, i32, i32, i32, yl, vp]
+    L.eagle_op_trajectory_picture.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.eagle_op_pass_picture.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.eagle_op_reid_crop.argtypes = [i32, u8p, i32, i32, i32, vp, i32, i32, i32, i32, i32, fp]
     L.eagle_op_reid_conv7.argtypes = [i32, fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
     L.eagle_op_reid_maxpool3s2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -278,7 +294,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
            "eagle_op_minimap_control", "eagle_post_possession", "eagle_post_possession_values", "eagle_post_device_possession", "eagle_post_events",
            "eagle_op_possession", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
-           "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_minimap_set_trails", "eagle_trajectory_picture",
+           "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -650,6 +667,14 @@ class Handle:
         self._check(self.L.eagle_post_events(table._t, _ptr(ev, keep), n.value, C.byref(n)), "post_events")
         return cand, owner, dist, ev
 
+    def events(self, table):
+        """The events of the table's last possession result (EVENT_DTYPE, row order; empty before it)."""
+        n = C.c_int(0)
+        self._check(self.L.eagle_post_events(table._t, None, 0, C.byref(n)), "post_events")
+        ev = np.zeros(n.value, EVENT_DTYPE)
+        self._check(self.L.eagle_post_events(table._t, _ptr(ev, np.zeros(4, np.float64)), n.value, C.byref(n)), "post_events")
+        return ev
+
     def possession_device(self, table):
         """owner int32 [rows] in HBM (None before the first possession call of the table)."""
         d = C.c_void_p()
@@ -684,6 +709,33 @@ class Handle:
         w, h = minimap_size(mp)
         out = np.zeros((h, w, 3), np.uint8)
         self._check(self.L.eagle_occupancy_picture(self._h, table._t, int(sel), mp.scale, mp.margin, _bgr(colour), out.ctypes.data_as(C.c_void_p)), "occupancy_picture")
+        return out
+
+    def minimap_set_trails(self, table, params, cols=()):
+        """The parameters (trail_params) and the selected table columns the minimap's trail, pass and owner layers of this table are drawn with (params
+        None: forget them; no columns: passes and owner only)."""
+        cols = np.ascontiguousarray(cols, np.int32)
+        keep = np.zeros(4, np.int32)
+        self._check(self.L.eagle_minimap_set_trails(table._t, None if params is None else C.byref(params), _ptr(cols, keep), len(cols)), "minimap_set_trails")
+
+    def trajectory_picture(self, table, cols, row0=0, n=None, scale=8, margin=None, half_width=1, max_gap=25):
+        """The paths of the selected table columns over rows row0 .. row0 + n - 1 as a still picture of the pitch -> BGR uint8 [h, w, 3]."""
+        mp = minimap_params(scale, margin)
+        w, h = minimap_size(mp)
+        cols = np.ascontiguousarray(cols, np.int32)
+        keep = np.zeros(4, np.int32)
+        n = len(table.rows) - row0 if n is None else n
+        out = np.zeros((h, w, 3), np.uint8)
+        self._check(self.L.eagle_trajectory_picture(self._h, table._t, _ptr(cols, keep), len(cols), int(row0), int(n), mp.scale, mp.margin, int(half_width), int(max_gap),
+                                                    out.ctypes.data_as(C.c_void_p)), "trajectory_picture")
+        return out
+
+    def pass_picture(self, table, event, scale=8, margin=None, half_width=1):
+        """Event ``event`` of the table's last possession result at its release row as a still picture -> BGR uint8 [h, w, 3]."""
+        mp = minimap_params(scale, margin)
+        w, h = minimap_size(mp)
+        out = np.zeros((h, w, 3), np.uint8)
+        self._check(self.L.eagle_pass_picture(self._h, table._t, int(event), mp.scale, mp.margin, int(half_width), out.ctypes.data_as(C.c_void_p)), "pass_picture")
         return out
 
     def minimap_set_control(self, table, params):
@@ -1220,12 +1272,12 @@ def op_annotate(frames, prims, offsets, fmt="bgr", layout=None, out=None, device
 
 
 # --- the minimap ------------------------------------------------------------------------------------------------
-def minimap_params(scale=8, margin=None, voronoi=False, footprint=True, player_radius=0, ball_radius=0, control=False):
+def minimap_params(scale=8, margin=None, voronoi=False, footprint=True, player_radius=0, ball_radius=0, control=False, layers=0):
     """EagleMinimapParams; margin None: two metres' worth of pixels, at most 64.  control: the pitch-control layer (Handle.minimap_set_control /
-    op_minimap_control say with which parameters)."""
+    op_minimap_control say with which parameters).  layers: MM_TRAILS | MM_PASSES | MM_OWNER (Handle.minimap_set_trails / op_minimap_trails)."""
     if margin is None:
         margin = min(64, 2 * int(scale))
-    return EagleMinimapParams(int(scale), int(margin), int(bool(voronoi)), int(bool(footprint)), int(player_radius), int(ball_radius), int(bool(control)))
+    return EagleMinimapParams(int(scale), int(margin), int(bool(voronoi)), int(bool(footprint)), int(player_radius), int(ball_radius), int(bool(control)), int(layers))
 
 
 def minimap_size(params):
@@ -1546,3 +1598,82 @@ def op_reid_head(x, w, b, x_cs=None, x_off=0, device=0):
     feats = np.empty((n, dim), np.float32)
     _reid_check(L, L.eagle_op_reid_head(device, _fp(x), n, h, wd, c, x_cs, x_off, _fp(w), _fp(b), dim, _fp(feats)), "eagle_op_reid_head")
     return feats
+
+
+# --- trails, pass arrows and the owner ring; the trajectory and the pass still -------------------------------------------------
+def trail_params(window=25, max_gap=25, half_width=1, pass_hold=5, dim_floor=64):
+    """EagleTrailParams.  One second of rows at 25 fps, a thin line, five rows of hold and a fade to a quarter are conventional choices."""
+    return EagleTrailParams(int(window), int(max_gap), int(half_width), int(pass_hold), int(dim_floor))
+
+
+def op_minimap_trails(values, frames, columns, team_mapping, params, trail, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None, device=0):
+    """op_minimap with the trail, pass-arrow and owner layers (include/eagle.h eagle_op_minimap_trails): frames int32 [rows], params minimap_params(...,
+    layers=...), trail trail_params(...) (None with layers == 0), sel the selected table columns, owner int32 [rows] or None, events EVENT_DTYPE or None."""
+    L = load()
+    values, columns = _table_args("op_minimap_trails", values, columns)
+    cols, rows = values.shape[:2]
+    frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
+    sel = np.ascontiguousarray(sel, np.int32)
+    owner = None if owner is None else np.ascontiguousarray(owner, np.int32)
+    events = None if events is None else np.ascontiguousarray(events, EVENT_DTYPE)
+    if (frames is not None and len(frames) != rows) or (owner is not None and len(owner) != rows):
+        raise EagleError("op_minimap_trails: one frame number and one owner per row")
+    ids, vals, nt = _team_arrays(team_mapping)
+    n = rows - row0 if n is None else n
+    w, h = minimap_size(params)
+    lay = _yuv_layout(layout)
+    need = out_span(fmt, h, w, lay, n)
+    if out is None:
+        out = np.zeros(need, np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+        raise EagleError(f"op_minimap_trails: out must be a contiguous uint8 array of at least {need} bytes")
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_minimap_trails(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(params),
+                                   None if trail is None else C.byref(trail), _ptr(sel, keep), len(sel), _ptr(owner, keep), _ptr(events, keep),
+                                   0 if events is None else len(events), int(row0), int(n), _out_pix(fmt), None if lay is None else C.byref(lay),
+                                   out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_minimap_trails failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if lay is None:
+        return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+    return out
+
+
+def op_trajectory_picture(values, frames, columns, team_mapping, sel, row0=0, n=None, scale=8, margin=None, half_width=1, max_gap=25, device=0):
+    """The trajectory still of a constructed table (include/eagle.h eagle_op_trajectory_picture) -> BGR uint8 [h, w, 3]."""
+    L = load()
+    values, columns = _table_args("op_trajectory_picture", values, columns)
+    cols, rows = values.shape[:2]
+    frames = np.ascontiguousarray(frames, np.int32)
+    if len(frames) != rows:
+        raise EagleError("op_trajectory_picture: one frame number per row")
+    sel = np.ascontiguousarray(sel, np.int32)
+    ids, vals, nt = _team_arrays(team_mapping)
+    n = rows - row0 if n is None else n
+    mp = minimap_params(scale, margin)
+    w, h = minimap_size(mp)
+    out = np.zeros((h, w, 3), np.uint8)
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_trajectory_picture(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, _ptr(sel, keep),
+                                       len(sel), int(row0), int(n), mp.scale, mp.margin, int(half_width), int(max_gap), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_trajectory_picture failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
+
+
+def op_pass_picture(values, columns, team_mapping, events, event, scale=8, margin=None, half_width=1, device=0):
+    """The pass still of a constructed table (include/eagle.h eagle_op_pass_picture): events EVENT_DTYPE -> BGR uint8 [h, w, 3]."""
+    L = load()
+    values, columns = _table_args("op_pass_picture", values, columns)
+    cols, rows = values.shape[:2]
+    events = np.ascontiguousarray(events, EVENT_DTYPE)
+    ids, vals, nt = _team_arrays(team_mapping)
+    mp = minimap_params(scale, margin)
+    w, h = minimap_size(mp)
+    out = np.zeros((h, w, 3), np.uint8)
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_pass_picture(device, _ptr(values, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, _ptr(events, keep), len(events), int(event),
+                                 mp.scale, mp.margin, int(half_width), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_pass_picture failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out

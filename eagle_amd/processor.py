@@ -54,10 +54,25 @@ class Processor:
         ``table``: draw the processed table (process_data above) instead of the raw records."""
         return self.model.annotate(frames, coords_or_records, team_mapping, pixel_format, out_format, table=table)
 
-    def minimap(self, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, control=None):
-        """The minimap pictures of a processed table (process_data above), drawn on the GPU: see eagle_amd/minimap.py."""
+    def minimap(self, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, control=None, trails=None, passes=False, owner=False,
+                trail_params=None):
+        """The minimap pictures of a processed table (process_data above), drawn on the GPU: see eagle_amd/minimap.py.  trails (table columns), passes and
+        owner add the paths, the pass arrows and the owner's ring (the last two after possession below)."""
         from . import minimap as mm
-        return mm.minimap(self.model.handle, table, scale, margin, voronoi, footprint, pixel_format, rows, control=control)
+        return mm.minimap(self.model.handle, table, scale, margin, voronoi, footprint, pixel_format, rows, control=control, trails=trails, passes=passes, owner=owner,
+                          trail_params=trail_params)
+
+    def trajectory(self, table, cols, rows=None, scale=8, margin=None, half_width=1, max_gap=25):
+        """The paths of table columns over a row window as one still picture of the pitch (BGR): see eagle_amd/minimap.py trajectory_picture."""
+        from . import minimap as mm
+        return mm.trajectory_picture(self.model.handle, table, cols, rows, scale, margin, half_width, max_gap)
+
+    def pass_pictures(self, table, scale=8, margin=None, half_width=1, kinds=(0,)):
+        """One still picture (BGR) per possession event of the given kinds (default: passes) at its release row, after possession below
+        -> [(event index, picture)]."""
+        from . import minimap as mm
+        events = self.model.handle.events(table)
+        return [(k, mm.pass_picture(self.model.handle, table, k, scale, margin, half_width)) for k, e in enumerate(events) if int(e["kind"]) in kinds]
 
     def kinematics(self, table, fps, max_gap=None, speed_cap=12.0):
         """Velocities of a processed table (computed on the GPU, kept with the table) plus per id distance covered and top speed: see eagle_amd/control.py."""

@@ -334,7 +334,7 @@ typedef struct EagleMinimapParams {
     int32_t player_radius;         /* pixels, 0 .. 4 scale; 0 = max(2, scale) */
     int32_t ball_radius;           /* outer radius of the ring, pixels, 0 .. 4 scale; 0 = max(3, scale / 2 + 1); the ring is max(1, radius / 3) thick */
     int32_t control;               /* != 0: draw the pitch-control layer in Voronoi's slot (below: eagle_minimap_set_control); refused together with voronoi */
-    int32_t reserved;
+    int32_t layers;                /* bit mask of EAGLE_MM_* (below: eagle_minimap_set_trails); 0: none of them, the minimap as it is without them */
 } EagleMinimapParams;
 int eagle_minimap_size(const EagleMinimapParams* p, int* w, int* h);
 /* rows row0 .. row0 + n - 1 -> n pictures in HBM (a buffer of the caller: eagle_device_alloc, or an encoder's input surface with its layout); returns when
@@ -449,6 +449,56 @@ int eagle_post_events(const EaglePostTable* t, EaglePossessionEvent* out, int ca
 int eagle_op_possession(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
                         const int32_t* team_vals, int n_team, const EaglePossessionParams* p, int32_t* cand, int32_t* owner, double* dist,
                         EaglePossessionEvent* events, int cap, int* n_events);
+
+/* ---- trails, pass arrows and the ball owner in the minimap; the trajectory and the pass still (the reference's examples/trajectory.py and pass.py) ----
+ * Own specification: tests/trails_ref.py defines every output byte.  Three more layers of the minimap video, chosen by EagleMinimapParams::layers, drawn
+ * between the markings and the discs:
+ *   TRAILS  of the selected columns over the last `window` kept rows: on the picture of row r column c draws the segments (j - 1, j), max(1, r - window + 1)
+ *           <= j <= r, whose two cells are present (the minimap's rule) and whose frame step is at most max_gap; selection order, the oldest segment first;
+ *           a segment of age a = r - j is opaque in (colour * f) >> 8, f = 256 - (a (256 - dim_floor)) / window; the colour is the column's disc colour (a
+ *           player without a mapping entry has no trail).  A segment covers the pixels whose squared distance to it is at most (16 half_width)^2 in 1/16
+ *           pixel, decided exactly in integers.
+ *   PASSES  an arrow per event of eagle_post_possession on the rows release_row <= r < receive_row + pass_hold: white (pass), yellow (turnover) or grey
+ *           (unknown), a shaft of the trails' width between the two quantised ball cells and a head 4 half_width long and 2 x 2 half_width wide; either cell
+ *           absent: no arrow.
+ *   OWNER   a white ring max(1, radius / 3) pixels thick round the disc of eagle_post_possession's owner of the row.
+ * The layers need eagle_minimap_set_trails, PASSES and OWNER also eagle_post_possession.  With layers == 0 the output and the two launches are what they
+ * are without this section; otherwise the draw is a second instantiation of the kernel behind up to two preparing launches (trails.hip).
+ * STILLS, BGR [h][w][3] on the minimap's canvas: the trajectory of a selection over rows row0 .. row0 + n - 1 (markings, the segments undimmed, per column
+ * a ring at its first and a disc at its last present cell), and one event at its release row (markings, the arrow, the discs with everyone but passer and
+ * receiver blended at a quarter, the ball).
+ * EAGLE_E_INVALID with a message, before any launch: a layer bit without eagle_minimap_set_trails, PASSES or OWNER without a possession result, TRAILS with
+ * an empty selection, window < 1, half_width outside 1 .. 8, dim_floor outside 0 .. 256, pass_hold < 1, max_gap < 1, a selection member that is out of
+ * range, a video or boundary column or repeated, an event outside the event count, a row window outside the table (a still: n < 1), unknown bits in layers,
+ * and what the minimap refuses. */
+#define EAGLE_MM_TRAILS 1
+#define EAGLE_MM_PASSES 2
+#define EAGLE_MM_OWNER 4
+typedef struct EagleTrailParams {
+    int32_t window;                /* >= 1: kept rows a trail looks back */
+    int32_t max_gap;               /* >= 1: a step of more frames than this breaks a trail (a usual choice: fps) */
+    int32_t half_width;            /* 1 .. 8 pixels: of trails and arrow shafts */
+    int32_t pass_hold;             /* >= 1: rows an arrow stays after the receive row */
+    int32_t dim_floor;             /* 0 .. 256: the brightness (of 256) the oldest segment fades towards */
+    int32_t reserved[3];
+} EagleTrailParams;
+/* The parameters and the selection are kept with the table (p NULL: forget them); ncols == 0 with p set: passes and owner only. */
+int eagle_minimap_set_trails(EaglePostTable* t, const EagleTrailParams* p, const int32_t* cols, int ncols);
+int eagle_trajectory_picture(EagleHandle* h, EaglePostTable* t, const int32_t* cols, int ncols, int row0, int n, int scale, int margin, int half_width, int max_gap,
+                             uint8_t* out);
+int eagle_pass_picture(EagleHandle* h, EaglePostTable* t, int event, int scale, int margin, int half_width, uint8_t* out);
+/* Operator entries (host buffers in / out, no handle) for constructed tables, as eagle_op_minimap: frames [rows] strictly ascending, sel [nsel] the selection,
+ * owner [rows] or NULL, events [n_events] (ascending release_row and receive_row) or NULL; tp may be NULL when p->layers == 0.  The control layer is not
+ * available here. */
+int eagle_op_minimap_trails(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                            const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleTrailParams* tp, const int32_t* sel, int nsel,
+                            const int32_t* owner, const EaglePossessionEvent* events, int n_events, int row0, int n, int out_format, const EagleYuvLayout* out_layout,
+                            uint8_t* out);
+int eagle_op_trajectory_picture(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                                const int32_t* team_vals, int n_team, const int32_t* sel, int nsel, int row0, int n, int scale, int margin, int half_width, int max_gap,
+                                uint8_t* out);
+int eagle_op_pass_picture(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
+                          int n_team, const EaglePossessionEvent* events, int n_events, int event, int scale, int margin, int half_width, uint8_t* out);
 
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
