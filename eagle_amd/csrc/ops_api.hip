@@ -507,4 +507,139 @@ int eagle_op_reid_head(int device, const float* x, int n, int h, int w, int c, i
     API_END(hh)
 }
 
+// ---- the detector's concat-by-slice path one launch at a time (tests/test_gpu_slices.py) -----------------------------------------------------
+// The caller's whole buffers go through to_dev / from_dev (all three storage formats) and the launches get TView::slice views of them, as
+// build_yolo / YoloBuilder::c2f make them: what lies outside a slice is the caller's (the tests' NaN) and comes back with the output buffer.
+static void slice_check(const char* what, int prec, int n, int h, int w, int c, int cs, int off, int gran = 0)
+{
+    const int vn = prec == EAGLE_PREC_F32 ? 4 : 8;
+    if (gran == 0) gran = vn;
+    if (n < 1 || h < 1 || w < 1 || c < gran || c % gran || cs % vn || off % vn || off < 0 || cs < off + c)
+        fail(EAGLE_E_INVALID, "%s: [%d, %d, %d, %d] at channel %d of %d: sizes >= 1; c a multiple of %d; cs, off multiples of %d; off + c <= cs", what, n, h, w, c, off, cs, gran, vn);
+}
+static void slice_disjoint(const char* what, int off_a, int c_a, int off_b, int c_b)
+{
+    if (off_a < off_b + c_b && off_b < off_a + c_a) fail(EAGLE_E_INVALID, "%s: channels %d..%d and %d..%d of one buffer overlap", what, off_a, off_a + c_a, off_b, off_b + c_b);
+}
+static TView whole_to_dev(Net& net, int prec, const float* src, int n, int h, int w, int cs)
+{
+    TView v;
+    to_dev(net, prec, src, n, h, w, cs, cs, v);
+    return v;
+}
+static void whole_from_dev(TView v, float* dst) { v.off = 0; v.c = v.cs; from_dev(v, v.cs, dst); }
+
+int eagle_op_conv2d_sliced(int device, int precision, const float* x, int n, int h, int w, int cin, int x_cs, int x_off, const float* w_hwio, const float* bias,
+                           int cout, int ks, int stride, int pre_act, const float* r1, int r1_cs, int r1_off, int r1_where,
+                           const float* r2, int r2_cs, int r2_off, int r2_where, int post_act, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!x || !w_hwio || !bias || !y || (ks != 1 && ks != 3) || stride < 1 || stride > 2 || precision < EAGLE_PREC_F16 || precision > EAGLE_PREC_F32S)
+        fail(EAGLE_E_INVALID, "eagle_op_conv2d_sliced: bad argument (ks 1 or 3, stride 1 or 2)");
+    const int ho = (h + 2 * (ks / 2) - ks) / stride + 1, wo = (w + 2 * (ks / 2) - ks) / stride + 1;
+    slice_check("eagle_op_conv2d_sliced: x", precision, n, h, w, cin, x_cs, x_off, 16);
+    slice_check("eagle_op_conv2d_sliced: y", precision, n, ho, wo, cout, y_cs, y_off, 16);
+    const float* rp[2] = {r1, r2};
+    int rcs[2] = {r1_cs, r2_cs};
+    const int roff[2] = {r1_off, r2_off}, rwhere[2] = {r1_where, r2_where};
+    bool has[2];
+    for (int k = 0; k < 2; ++k) {
+        has[k] = rp[k] || rwhere[k] != EAGLE_OP_RES_OWN;
+        if (!has[k]) continue;
+        if (rwhere[k] == EAGLE_OP_RES_IN_Y) rcs[k] = y_cs;
+        else if (rwhere[k] == EAGLE_OP_RES_IN_X) {
+            if (ho != h || wo != w) fail(EAGLE_E_INVALID, "eagle_op_conv2d_sliced: a residual inside the input buffer needs an output of the input's size");
+            rcs[k] = x_cs;
+        } else if (rwhere[k] != EAGLE_OP_RES_OWN) fail(EAGLE_E_INVALID, "eagle_op_conv2d_sliced: residual placement %d", rwhere[k]);
+        slice_check("eagle_op_conv2d_sliced: residual", precision, n, ho, wo, cout, rcs[k], roff[k], 16);
+        if (rwhere[k] == EAGLE_OP_RES_IN_Y) slice_disjoint("eagle_op_conv2d_sliced: residual and output", roff[k], cout, y_off, cout);
+    }
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    ConvLaunch L;
+    const TView xb = whole_to_dev(net, precision, x, n, h, w, x_cs);
+    const TView yb = whole_to_dev(net, precision, y, n, ho, wo, y_cs);
+    L.x = xb.slice(x_off, cin);
+    L.y = yb.slice(y_off, cout);
+    TView* rv[2] = {&L.r1, &L.r2};
+    for (int k = 0; k < 2; ++k) {
+        if (!has[k]) continue;
+        const TView base = rwhere[k] == EAGLE_OP_RES_IN_Y ? yb : rwhere[k] == EAGLE_OP_RES_IN_X ? xb : whole_to_dev(net, precision, rp[k], n, ho, wo, rcs[k]);
+        *rv[k] = base.slice(roff[k], cout);
+    }
+    L.cfg = conv_choose(precision, ks, stride, cin, cout, wo, pre_act == ACT_NONE && post_act <= ACT_RELU, has[0] && has[1]);      // as Builder::conv: the slice's channel counts
+    if (!conv_supported(precision, L.cfg)) fail(EAGLE_E_NOKERNEL, "no kernel instance ks=%d s=%d kc=%d nt=%d", ks, stride, L.cfg.kc, L.cfg.nt);
+    std::vector<char> tiled(conv_weight_elems(precision, L.cfg) * (precision == EAGLE_PREC_F32 ? 4 : 2));
+    conv_tile_weights(precision, L.cfg, w_hwio, cin, cout, tiled.data(), &L.descale);
+    L.w = net.upload(tiled.data(), tiled.size());
+    L.bias = (const float*)net.upload(bias, (size_t)cout * 4);
+    L.pre_act = pre_act; L.post_act = post_act;
+    conv_launch(precision, L, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    whole_from_dev(yb, y);
+    API_END(hh)
+}
+
+// x -> y of one element-wise launch: y is the caller's in/out buffer, or (same_buffer) the input buffer itself
+static void slice_pair(Net& net, const char* what, int prec_x, int prec_y, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int same_buffer,
+                       int yh, int yw, int y_cs, int y_off, const float* y, TView& xv, TView& yv)
+{
+    if (!x || !y) fail(EAGLE_E_INVALID, "%s: null argument", what);
+    if (same_buffer && (y_cs != x_cs || yh != h || yw != w || prec_x != prec_y)) fail(EAGLE_E_INVALID, "%s: slices of one buffer share its size, stride and format", what);
+    slice_check(what, prec_x, n, h, w, c, x_cs, x_off);
+    slice_check(what, prec_y, n, yh, yw, c, y_cs, y_off, prec_x == EAGLE_PREC_F32 ? 4 : 8);
+    if (same_buffer) slice_disjoint(what, x_off, c, y_off, c);
+    const TView xb = whole_to_dev(net, prec_x, x, n, h, w, x_cs);
+    const TView yb = same_buffer ? xb : whole_to_dev(net, prec_y, y, n, yh, yw, y_cs);
+    xv = xb.slice(x_off, c); yv = yb.slice(y_off, c);
+}
+
+int eagle_op_maxpool5(int device, int precision, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int same_buffer, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (precision < EAGLE_PREC_F16 || precision > EAGLE_PREC_F32S) fail(EAGLE_E_INVALID, "eagle_op_maxpool5: precision %d", precision);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    TView xv, yv;
+    slice_pair(net, "eagle_op_maxpool5", precision, precision, x, n, h, w, c, x_cs, x_off, same_buffer, h, w, y_cs, y_off, y, xv, yv);
+    maxpool5_launch(xv, yv, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    whole_from_dev(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_upsample2(int device, int precision, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int same_buffer, int yh, int yw, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (precision < EAGLE_PREC_F16 || precision > EAGLE_PREC_F32S) fail(EAGLE_E_INVALID, "eagle_op_upsample2: precision %d", precision);
+    if (h < 1 || w < 1 || (yh != 2 * h - 1 && yh != 2 * h) || (yw != 2 * w - 1 && yw != 2 * w))
+        fail(EAGLE_E_INVALID, "eagle_op_upsample2: a %d x %d map goes to {%d, %d} x {%d, %d}, not %d x %d", h, w, 2 * h - 1, 2 * h, 2 * w - 1, 2 * w, yh, yw);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    TView xv, yv;
+    slice_pair(net, "eagle_op_upsample2", precision, precision, x, n, h, w, c, x_cs, x_off, same_buffer, yh, yw, y_cs, y_off, y, xv, yv);
+    yv.h = yh; yv.w = yw;
+    upsample2_launch(xv, yv, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    whole_from_dev(yv, y);
+    API_END(hh)
+}
+
+int eagle_op_split_to_f32(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    TView xv, yv;
+    slice_pair(net, "eagle_op_split_to_f32", EAGLE_PREC_F32S, EAGLE_PREC_F32, x, n, h, w, c, x_cs, x_off, 0, h, w, y_cs, y_off, y, xv, yv);
+    split_to_f32_launch(xv, yv, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    whole_from_dev(yv, y);
+    API_END(hh)
+}
+
 }  // extern "C"

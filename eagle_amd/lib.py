@@ -276,6 +276,10 @@ def load():
     L.eagle_op_reid_dw3.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
     L.eagle_op_reid_gate.argtypes = [i32, C.POINTER(fp), i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, i32, i32, i32, fp, fp]
     L.eagle_op_reid_head.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, fp, fp, i32, fp]
+    L.eagle_op_conv2d_sliced.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, i32, fp, i32, i32, i32, fp, i32, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_maxpool5.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_upsample2.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_split_to_f32.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
     _lib = L
     return L
 
@@ -296,7 +300,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_possession", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
            "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_minimap_set_trails", "eagle_trajectory_picture",
            "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
-           "eagle_op_reid_gate", "eagle_op_reid_head"]
+           "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -1598,6 +1602,71 @@ def op_reid_head(x, w, b, x_cs=None, x_off=0, device=0):
     feats = np.empty((n, dim), np.float32)
     _reid_check(L, L.eagle_op_reid_head(device, _fp(x), n, h, wd, c, x_cs, x_off, _fp(w), _fp(b), dim, _fp(feats)), "eagle_op_reid_head")
     return feats
+
+
+# --- the detector's concat-by-slice path one launch at a time (include/eagle.h eagle_op_conv2d_sliced ...; csrc/nets.hip build_yolo) ---------------
+# Unlike the op_reid_* wrappers these take WHOLE buffers ([n, h, w, cs] float32; the caller owns what lies outside the slices) and return the whole
+# output buffer; the library converts them to and from the family's storage format, where a NaN stays a NaN but loses its payload outside fp32.
+RES_OWN, RES_IN_Y, RES_IN_X = 0, 1, 2
+
+
+def _whole(a):
+    a = np.ascontiguousarray(a, np.float32)
+    assert a.ndim == 4
+    return a
+
+
+def op_conv2d_sliced(x, x_off, w_hwio, bias, y, y_off, stride=1, pre=0, r1=None, r2=None, post=0, precision=PREC_F32, device=0):
+    """conv_launch on slice views: channels x_off .. x_off + cin of the buffer x [n, h, w, x_cs] -> channels y_off .. y_off + cout of a copy of the buffer
+    y [n, ho, wo, y_cs], which is returned whole.  r1 / r2: None, or (where, buffer, off) with where RES_OWN (cout channels at off of its own buffer
+    [n, ho, wo, cs]), RES_IN_Y or RES_IN_X (at off of the output / input buffer; buffer is None)."""
+    L = load()
+    x = _whole(x); y = _whole(y).copy(); w = np.ascontiguousarray(w_hwio, np.float32); b = np.ascontiguousarray(bias, np.float32)
+    n, h, wd, x_cs = x.shape
+    ks, _, cin, cout = w.shape
+    ho, wo = (h + 2 * (ks // 2) - ks) // stride + 1, (wd + 2 * (ks // 2) - ks) // stride + 1
+    assert y.shape[:3] == (n, ho, wo) and b.shape == (cout,)
+    res = []
+    for r in (r1, r2):
+        where, buf, off = (RES_OWN, None, 0) if r is None else r
+        buf = None if buf is None else _whole(buf)
+        assert buf is None or (where == RES_OWN and buf.shape[:3] == (n, ho, wo))
+        res += [buf, _fp(buf), 0 if buf is None else buf.shape[3], off, where]
+    _reid_check(L, L.eagle_op_conv2d_sliced(device, precision, _fp(x), n, h, wd, cin, x_cs, x_off, _fp(w), _fp(b), cout, ks, stride, pre, *res[1:5], *res[6:10], post,
+                                            y.shape[3], y_off, _fp(y)), "eagle_op_conv2d_sliced")
+    return y
+
+
+def _op_slice_pair(name, precision, x, c, x_off, y, y_off, extra, device):
+    L = load()
+    x = _whole(x)
+    same = y is None
+    y = np.empty((x.shape[0],) + tuple(extra or x.shape[1:3]) + (x.shape[3],), np.float32) if same else _whole(y).copy()
+    n, h, w, x_cs = x.shape
+    assert y.shape[0] == n and (extra is None or y.shape[1:3] == tuple(extra))
+    prec = [] if precision is None else [precision]
+    mid = [] if precision is None else [int(same)]
+    _reid_check(L, getattr(L, name)(device, *prec, _fp(x), n, h, w, c, x_cs, x_off, *mid, *(extra or ()), y.shape[3], y_off, _fp(y)), name)
+    return y
+
+
+def op_maxpool5(x, c, x_off, y, y_off, precision=PREC_F32, device=0):
+    """maxpool5_kernel (MaxPool2d(5, 1, 2)): channels x_off .. x_off + c of the buffer x [n, h, w, x_cs] -> channels y_off .. of a copy of the buffer y
+    [n, h, w, y_cs], returned whole.  y = None: input and output are slices of ONE buffer (SPPF); feed the result back as x for the next pool of the chain."""
+    return _op_slice_pair("eagle_op_maxpool5", precision, x, c, x_off, y, y_off, None, device)
+
+
+def op_upsample2(x, c, x_off, y, y_off, out_hw, precision=PREC_F32, device=0):
+    """upsample2_kernel (nearest x2, cropped): channels x_off .. of x [n, h, w, x_cs] -> channels y_off .. of a copy of y [n, yh, yw, y_cs], returned whole;
+    out_hw = (yh, yw) with yh in {2h - 1, 2h}, yw in {2w - 1, 2w}, anything else is an EagleError.  y = None: one buffer (only a 1 x 1 map keeps its size)."""
+    return _op_slice_pair("eagle_op_upsample2", precision, x, c, x_off, y, y_off, tuple(out_hw), device)
+
+
+def op_split_to_f32(x, c, x_off, y, y_off, device=0):
+    """split_to_f32_kernel: channels x_off .. of x [n, h, w, x_cs], stored as split pairs, -> channels y_off .. of a copy of the fp32 buffer y [n, h, w, y_cs],
+    returned whole with every bit outside the slice as it was."""
+    assert y is not None, "the two storage formats differ: input and output cannot share a buffer"
+    return _op_slice_pair("eagle_op_split_to_f32", None, x, c, x_off, y, y_off, None, device)
 
 
 # --- trails, pass arrows and the owner ring; the trajectory and the pass still -------------------------------------------------

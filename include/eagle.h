@@ -724,6 +724,29 @@ int eagle_op_reid_gate(int device, const float* const* streams, int n, int h, in
 /* global average -> Linear(c, dim) + bias -> ReLU; wt [dim][c] (BatchNorm1d folded), feats [n][dim] */
 int eagle_op_reid_head(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, const float* wt, const float* b, int dim, float* feats);
 
+/* ---- the detector's concat-by-slice path one launch at a time (nets.hip build_yolo / YoloBuilder::c2f; tests/test_gpu_slices.py).  Test surface only: each
+ * entry calls the network's own launch function on TView::slice views.  The caller passes WHOLE buffers as fp32 host arrays [n][h][w][cs] and owns every
+ * value outside the slices (the tests put a NaN there); the entry converts whole buffers to the family's storage format (fp32 / binary16 / split pairs,
+ * precision = EAGLE_PREC_*), launches, and returns the whole output buffer converted back.  In binary16 and split storage a NaN comes back as a NaN, not
+ * with its payload.  c, cs and off are multiples of the family's vector width (4 fp32, 8 otherwise; 16 for a convolution's channel counts) and
+ * off + c <= cs; slices of one buffer that a launch reads and writes must not overlap.  A violation is EAGLE_E_INVALID and nothing is launched. */
+#define EAGLE_OP_RES_OWN 0      /* the residual is a slice of a buffer of its own [n][ho][wo][cs] */
+#define EAGLE_OP_RES_IN_Y 1     /* ... of the OUTPUT buffer (C2f: m.k.cv2 adds slice (1 + k) c of `cat` and writes slice (2 + k) c); the pointer is not read */
+#define EAGLE_OP_RES_IN_X 2     /* ... of the INPUT buffer (stride 1 only: same map size); the pointer is not read */
+/* eagle_op_conv2d on slice views: x [n][h][w][x_cs] of which channels x_off .. x_off + cin are convolved; y [n][ho][wo][y_cs] is IN/OUT (its contents are
+ * uploaded first, channels y_off .. y_off + cout are written); r1 / r2: NULL with where = EAGLE_OP_RES_OWN for none, else cout channels at r_off of the
+ * buffer `where` names.  The configuration is conv_choose's for the slice's channel counts, as the network builder's; EAGLE_CONV_FORCE / EAGLE_F32_FORCE apply. */
+int eagle_op_conv2d_sliced(int device, int precision, const float* x, int n, int h, int w, int cin, int x_cs, int x_off, const float* w_hwio, const float* bias,
+                           int cout, int ks, int stride, int pre_act, const float* r1, int r1_cs, int r1_off, int r1_where,
+                           const float* r2, int r2_cs, int r2_off, int r2_where, int post_act, int y_cs, int y_off, float* y);
+/* MaxPool2d(5, 1, 2) (SPPF) of c channels.  same_buffer = 0: y [n][h][w][y_cs] is in/out.  same_buffer != 0: input and output are slices of ONE buffer (y_cs
+ * = x_cs): x is uploaded, slice y_off is written into it and the whole buffer comes back in y, so that SPPF's chain is three calls feeding y back as x. */
+int eagle_op_maxpool5(int device, int precision, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int same_buffer, int y_cs, int y_off, float* y);
+/* nearest x2 of c channels into y [n][yh][yw][y_cs] (in/out), yh in {2h - 1, 2h}, yw in {2w - 1, 2w}: y[i][j] = x[i / 2][j / 2].  same_buffer as above (yh = h, yw = w: 1 x 1 maps) */
+int eagle_op_upsample2(int device, int precision, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int same_buffer, int yh, int yw, int y_cs, int y_off, float* y);
+/* the mixed detector's seam: a split-format slice to an fp32 slice, exactly (hi + lo) / 16.  x is stored as split pairs, y [n][h][w][y_cs] (in/out) as fp32, bit for bit */
+int eagle_op_split_to_f32(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y);
+
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
  * Keys: "lk_threads" (64 | 256), "lk_dbg" (1 trace, 2 LDS guard words, 4 end-of-level verification, 8 L1-bypassing loads), "lk_excl_lds" (bytes), "lk_trace", "lk_counters". */
