@@ -21,7 +21,9 @@ sets the pixels per metre).  ``--possession`` (with ``--processed``) writes ``po
 turnovers, and what they add up to per id, per team and per pair of ids (eagle_amd/possession.py).  ``--occupancy`` (with ``--processed``) writes
 ``occupancy.npy`` and ``occupancy.json``: where every player, every team and the ball spent their time, as seconds per pitch cell
 (eagle_amd/occupancy.py; ``--occupancy-grid`` cells per metre, ``--occupancy-sigma`` metres of Gaussian smoothing, ``--occupancy-pictures`` one PPM per
-team and one for the ball); the maps follow a person only with ``--merge-ids``.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+team and one for the ball); the maps follow a person only with ``--merge-ids``.  ``--shape`` (with ``--processed``) writes ``shape.json``: per kept
+frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
+draws the two hulls into the minimap.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -121,7 +123,24 @@ def main(argv=None):
     ap.add_argument("--occupancy-pictures", action="store_true",
                     help="with --occupancy: also write one binary PPM per team (<out>/occupancy_team<t>.ppm) and one for the ball (<out>/occupancy_ball.ppm) at "
                          "--minimap-scale pixels per metre")
+    ap.add_argument("--shape", action="store_true",
+                    help="with --processed: also write <out>/shape.json, per kept frame each team's centroid, length, width, hull area, stretch index, lines and "
+                         "convex hull, and their means over the clip")
+    ap.add_argument("--minimap-hulls", nargs="?", const="1", default=None, metavar="W",
+                    help="with --minimap: draw the convex hull of each team, W pixels either side of the line (1 .. 8, default 1); computes the team shape if "
+                         "--shape did not")
     a = ap.parse_args(argv)
+    if a.shape and not a.processed:
+        ap.error("--shape works on the processed table: it needs --processed")
+    if a.minimap_hulls is not None:
+        if not (a.minimap or a.minimap_control):
+            ap.error("--minimap-hulls draws into the minimap: it needs --minimap")
+        try:
+            a.minimap_hulls = int(a.minimap_hulls)
+        except ValueError:
+            a.minimap_hulls = 0
+        if not 1 <= a.minimap_hulls <= 8:
+            ap.error("--minimap-hulls takes a half width of 1 .. 8 pixels")
     if a.occupancy and not a.processed:
         ap.error("--occupancy works on the processed table: it needs --processed")
     if a.occupancy_pictures and not a.occupancy:
@@ -225,6 +244,12 @@ def main(argv=None):
             if a.occupancy_pictures:
                 for name, img in oc.pictures(model.handle, table, occ, a.minimap_scale):
                     oc.write_ppm(os.path.join(a.out, "occupancy_%s.ppm" % name), img)
+        if a.shape:
+            from . import shape as sh
+            with open(os.path.join(a.out, "shape.json"), "w") as f:
+                json.dump(sh.to_json(sh.shape(model.handle, table)), f)
+        elif a.minimap_hulls is not None:
+            model.handle.team_shape(table)
         if (a.minimap_passes or a.pass_pictures) and not a.possession:
             model.handle.possession(table, lib.possession_params(a.fps))
         entities = [c for c, k in enumerate(table.columns) if not k["video"] and int(k["kind"]) in (lib.POST_PLAYER, lib.POST_GOALKEEPER, lib.POST_BALL)]
@@ -244,7 +269,7 @@ def main(argv=None):
             write_y4m(os.path.join(a.out, "minimap.y4m"), minimap(model.handle, table, a.minimap_scale, voronoi=a.minimap_voronoi, pixel_format="i420",
                                                                    control=lib.control_params(min(4, a.minimap_scale)) if a.minimap_control else None,
                                                                    trails=entities if a.minimap_trails is not None else None, passes=a.minimap_passes,
-                                                                   owner=a.minimap_passes, trail_params=tp), a.fps)
+                                                                   owner=a.minimap_passes, trail_params=tp, hulls=a.minimap_hulls), a.fps)
         table.close()
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
         if a.merge_ids:

@@ -280,6 +280,28 @@ __device__ __forceinline__ void mm_draw(const MinimapArgs& m, const MmLayerArgs*
 
     if constexpr (LAYERS) {
         const int row = m.row0 + f, hw = la->hw16;
+        // ---- 4.0 hulls (K26): the 2 x 32 edge slots of the picture in one staging trip, group 0 first; the trails' capsule in the layer's own width ----
+        if (la->hull_edges) {                          // (uniform)
+            static_assert(2 * EAGLE_SHAPE_HULL_CAP <= MM_CHUNK, "a picture's hull edges are staged in one trip");
+            const int hh = la->hull_hw16;
+            __syncthreads();
+            if (tid < 2 * EAGLE_SHAPE_HULL_CAP) {
+                const int4 e = la->hull_edges[(size_t)(row - la->range_row0) * (2 * EAGLE_SHAPE_HULL_CAP) + tid];
+                const bool vis = e.x != MM_ABSENT && min(e.x, e.z) - hh <= 16 * tx1 && max(e.x, e.z) + hh >= 16 * tx0 && min(e.y, e.w) - hh <= 16 * ty1 &&
+                                 max(e.y, e.w) + hh >= 16 * ty0;
+                s_e[tid] = e;
+                s_f[tid] = make_int4(tid < EAGLE_SHAPE_HULL_CAP ? 0x9f0000 : 0x00009f, vis, 0, 0);       // (255 * 160) >> 8 = 159 of red | blue
+            }
+            __syncthreads();
+            if (live) {
+                for (int j = 0; j < 2 * EAGLE_SHAPE_HULL_CAP; ++j) {
+                    const int4 g = s_f[j];
+                    if (!g.y) continue;                // (uniform)
+                    const int4 e = s_e[j];
+                    mm_paint(px, mm_capsule_strip(e.x, e.y, e.z, e.w, hh, x0, y0), (uint32_t)g.x);
+                }
+            }
+        }
         // ---- 4a. trails: entry e of the picture is segment (j - 1, j) of selected column e / per, j = jlo + e % per, the oldest first ----
         if (la->nsel) {                                // (uniform)
             const int jlo = la->jlo >= 0 ? la->jlo : max(1, row - la->window + 1), per = max(0, row - jlo + 1), total = la->nsel * per;
@@ -443,7 +465,7 @@ MmPlan minimap_plan(const EagleMinimapParams* p)
     if (p->player_radius < 0 || p->player_radius > 4 * p->scale || p->ball_radius < 0 || p->ball_radius > 4 * p->scale)
         fail(EAGLE_E_INVALID, "minimap: radii %d / %d must lie within 0 .. 4 x scale = %d (0: the default)", p->player_radius, p->ball_radius, 4 * p->scale);
     if (p->control && p->voronoi) fail(EAGLE_E_INVALID, "minimap: control and voronoi draw in the same slot: choose one");
-    if (p->layers & ~(EAGLE_MM_TRAILS | EAGLE_MM_PASSES | EAGLE_MM_OWNER)) fail(EAGLE_E_INVALID, "minimap: layers 0x%x has unknown bits", (unsigned)p->layers);
+    if (p->layers & ~(EAGLE_MM_TRAILS | EAGLE_MM_PASSES | EAGLE_MM_OWNER | EAGLE_MM_HULLS)) fail(EAGLE_E_INVALID, "minimap: layers 0x%x has unknown bits", (unsigned)p->layers);
     MmPlan pl;
     pl.S = p->scale; pl.M = p->margin;
     pl.w = 105 * pl.S + 2 * pl.M; pl.h = 68 * pl.S + 2 * pl.M;
@@ -618,7 +640,11 @@ static MmPlan minimap_begin(EagleHandle* h, EaglePostTable* t, int row0, int n, 
         if (!t->d_vel) fail(EAGLE_E_INVALID, "minimap: control needs the table's velocities (eagle_post_velocities comes first)");
         if (!t->has_control) fail(EAGLE_E_INVALID, "minimap: control needs its parameters (eagle_minimap_set_control comes first)");
     }
-    if (p->layers) {
+    if (p->layers & EAGLE_MM_HULLS) {
+        if (!t->has_shape) fail(EAGLE_E_INVALID, "minimap: the hull layer needs a team-shape result (eagle_post_team_shape comes first)");
+        if (!t->has_hulls) fail(EAGLE_E_INVALID, "minimap: the hull layer needs its parameters (eagle_minimap_set_hulls comes first)");
+    }
+    if (p->layers & (EAGLE_MM_TRAILS | EAGLE_MM_PASSES | EAGLE_MM_OWNER)) {
         if (!t->has_trails) fail(EAGLE_E_INVALID, "minimap: layers need their parameters (eagle_minimap_set_trails comes first)");
         if ((p->layers & (EAGLE_MM_PASSES | EAGLE_MM_OWNER)) && !t->has_poss)
             fail(EAGLE_E_INVALID, "minimap: the pass and owner layers need a possession result (eagle_post_possession comes first)");
@@ -670,7 +696,7 @@ static std::vector<MmCol> trail_selection(const EaglePostColumn* columns, int nc
 
 // device memory of the layers of one call.  With a handle the buffers are the handle's (mm_tr, grown on demand like the draw lists: no allocation and
 // no device-wide synchronisation per call); an operator entry owns them for the call and frees them when it ends (after the device has been synchronised)
-enum { TR_SEL, TR_FRAMES, TR_PTS, TR_LINK, TR_EVSRC, TR_EV, TR_RANGE, TR_OUT };
+enum { TR_SEL, TR_FRAMES, TR_PTS, TR_LINK, TR_EVSRC, TR_EV, TR_RANGE, TR_OUT, TR_HULL };
 struct DevTmp {
     EagleHandle* h = nullptr;
     int slot = 0;                                          // the next slot of h->mm_tr (layers_setup asks in a fixed order)
@@ -699,6 +725,9 @@ struct LayerJob {
     int nev = 0;
     int only_event = -1;                 // >= 0: the pass still
     bool trajectory = false;             // the trajectory still of rows row0 .. row0 + n - 1
+    const EagleTeamShape* d_shapes = nullptr;      // K26 hulls: the shape result in HBM ([rows][2]; [rows][2][32]) and the layer's half width
+    const int32_t* d_hull = nullptr;
+    int hull_hw = 0;
 };
 
 // everything the layered launches of rows row0 .. row0 + n - 1 read, prepared on stream s (which is synchronised before the host vectors go)
@@ -748,6 +777,11 @@ static MmLayerArgs layers_setup(DevTmp& tmp, hipStream_t s, const double2* d_val
         la.dim = 1; la.pass_from = job.events[job.only_event].from_col; la.pass_to = job.events[job.only_event].to_col;
     }
     if (job.layers & EAGLE_MM_OWNER) la.owner = job.d_owner;
+    if ((job.layers & EAGLE_MM_HULLS) && job.d_shapes && n > 0) {
+        int4* edges = (int4*)tmp.get((size_t)n * 2 * EAGLE_SHAPE_HULL_CAP * sizeof(int4), TR_HULL);
+        shape_edges_launch(d_values, rows, job.d_shapes, job.d_hull, row0, n, pl.S, pl.M, edges, s);
+        la.hull_edges = edges; la.hull_hw16 = 16 * job.hull_hw;
+    }
     HIP_CHECK(hipStreamSynchronize(s));                    // (pageable sources: they have left the vectors)
     return la;
 }
@@ -763,6 +797,10 @@ static LayerJob table_job(EaglePostTable* t, int layers)
         job.events = t->events.data(); job.nev = (int)t->events.size();
     }
     if (!job.d_owner) job.layers &= ~EAGLE_MM_OWNER;
+    if ((layers & EAGLE_MM_HULLS) && t->has_shape && t->rows) {
+        job.d_shapes = (const EagleTeamShape*)t->d_shape; job.d_hull = (const int32_t*)(job.d_shapes + (size_t)t->rows * 2);
+        job.hull_hw = t->hulls.half_width;
+    }
     return job;
 }
 
@@ -880,6 +918,8 @@ struct OpLayers {                                          // what eagle_op_mini
     int nsel = 0;
     LayerJob job;
     bool on = false;
+    const EagleHullParams* hp = nullptr;                   // eagle_op_minimap_hulls: the entry computes the shape itself
+    bool hulls = false;
 };
 
 static void op_minimap(const char* who, int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
@@ -921,6 +961,11 @@ static void op_minimap(const char* who, int device, const double* values, const 
         if ((job.layers & EAGLE_MM_PASSES) || job.only_event >= 0) events_check(who, job.events, job.nev, rows);
         if (trajectory) { m.ncols = 2 * (int)job.sel.size(); }
     }
+    ShapeCols shc;
+    if (ol && ol->hulls) {
+        hull_check(who, ol->hp);
+        shc = shape_columns(who, columns, cols, team_ids, team_vals, (size_t)n_team);
+    }
     if (n == 0) return;
     HIP_CHECK(hipSetDevice(device));
     Net net;
@@ -958,6 +1003,11 @@ static void op_minimap(const char* who, int device, const double* values, const 
         HIP_CHECK(hipDeviceSynchronize());                 // (Net::get clears its buffers on the null stream)
         DevTmp tmp;
         if (ol->job.layers & EAGLE_MM_OWNER) ol->job.d_owner = (const int32_t*)tmp.upload(ol->owner, (size_t)rows * 4, nullptr, TR_OUT);
+        if (ol->hulls) {                                   // the shape of the whole table, as eagle_op_team_shape computes it
+            EagleTeamShape* d_s = (EagleTeamShape*)tmp.get((size_t)rows * 2 * (sizeof(EagleTeamShape) + 4 * EAGLE_SHAPE_HULL_CAP), TR_HULL + 1);
+            shape_run(nullptr, shc, m.values, rows, d_s, (int32_t*)(d_s + (size_t)rows * 2), nullptr);
+            ol->job.d_shapes = d_s; ol->job.d_hull = (const int32_t*)(d_s + (size_t)rows * 2); ol->job.hull_hw = ol->hp->half_width;
+        }
         const MmLayerArgs la = layers_setup(tmp, nullptr, m.values, rows, ol->frames, pl, ol->job, row0, n);
         minimap_launch(m, nullptr, &la, trajectory);
         HIP_CHECK(hipDeviceSynchronize());
@@ -1052,12 +1102,41 @@ int eagle_op_minimap_trails(int device, const double* values, const int32_t* fra
     const char* who = "eagle_op_minimap_trails";
     if (!p) fail(EAGLE_E_INVALID, "minimap: params is NULL");
     if (p->control) fail(EAGLE_E_INVALID, "%s: the control layer is not available here (it needs velocities)", who);
+    if (p->layers & EAGLE_MM_HULLS) fail(EAGLE_E_INVALID, "%s: the hull layer needs a team-shape result, which this entry cannot carry (eagle_op_minimap_hulls computes one)", who);
     OpLayers ol;
     if (p->layers) {
         if (!tp) fail(EAGLE_E_INVALID, "%s: a layer without trail parameters", who);
         trail_check(who, tp);
         ol.on = true; ol.frames = frames; ol.owner = owner; ol.sel = sel; ol.nsel = nsel;
         ol.job.layers = p->layers; ol.job.tp = *tp; ol.job.events = events; ol.job.nev = n_events;
+    }
+    op_minimap(who, device, values, nullptr, columns, rows, cols, team_ids, team_vals, n_team, p, nullptr, row0, n, out_format, out_layout, out, &ol);
+    API_END(hh)
+}
+
+int eagle_op_minimap_hulls(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                           const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleHullParams* hp, const EagleTrailParams* tp, const int32_t* sel,
+                           int nsel, const int32_t* owner, const EaglePossessionEvent* events, int n_events, int row0, int n, int out_format,
+                           const EagleYuvLayout* out_layout, uint8_t* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    const char* who = "eagle_op_minimap_hulls";
+    if (!p) fail(EAGLE_E_INVALID, "minimap: params is NULL");
+    if (p->control) fail(EAGLE_E_INVALID, "%s: the control layer is not available here (it needs velocities)", who);
+    if (frames)
+        for (int r = 1; r < rows; ++r)
+            if (frames[r] <= frames[r - 1]) fail(EAGLE_E_INVALID, "%s: frame numbers must ascend (row %d: %d after %d)", who, r, frames[r], frames[r - 1]);
+    OpLayers ol;
+    if (p->layers) {
+        ol.on = true; ol.frames = frames; ol.owner = owner; ol.sel = sel; ol.nsel = nsel;
+        ol.job.layers = p->layers; ol.job.events = events; ol.job.nev = n_events;
+        if (p->layers & (EAGLE_MM_TRAILS | EAGLE_MM_PASSES | EAGLE_MM_OWNER)) {
+            if (!tp) fail(EAGLE_E_INVALID, "%s: a layer without trail parameters", who);
+            trail_check(who, tp);
+            ol.job.tp = *tp;
+        }
+        if (p->layers & EAGLE_MM_HULLS) { ol.hulls = true; ol.hp = hp; }
     }
     op_minimap(who, device, values, nullptr, columns, rows, cols, team_ids, team_vals, n_team, p, nullptr, row0, n, out_format, out_layout, out, &ol);
     API_END(hh)

@@ -258,8 +258,8 @@ struct EagleHandle {
     // minimap (minimap.hip): the draw lists of the call being run, the drawable columns and the marking mask of the last (scale, margin); grown on demand
     void* mm_list = nullptr; size_t mm_list_cap = 0;
     void* mm_cols = nullptr; size_t mm_cols_cap = 0;
-    // the K25 layers of the call being run (minimap.hip layers_setup): selection, frame numbers, points, links, events, prepared events, event ranges, still picture
-    void* mm_tr[8] = {}; size_t mm_tr_cap[8] = {};
+    // the K25 layers of the call being run (minimap.hip layers_setup): selection, frame numbers, points, links, events, prepared events, event ranges, still picture, hull edges (K26)
+    void* mm_tr[9] = {}; size_t mm_tr_cap[9] = {};
     uint8_t* mm_mask = nullptr; size_t mm_mask_cap = 0; int mm_mask_scale = 0, mm_mask_margin = -1;
     // pitch control (control.hip): the site lists and site columns of the call being run, and the grids the minimap's control layer reads; grown on demand
     void* ct_list = nullptr; size_t ct_list_cap = 0;
@@ -295,6 +295,10 @@ struct EaglePostTable {
     bool has_trails = false;             // eagle_minimap_set_trails
     EagleTrailParams trails{};
     std::vector<int32_t> trail_cols;
+    void* d_shape = nullptr;             // team shape (eagle_post_team_shape): EagleTeamShape [rows][2] | hull i32 [rows][2][32], resident until eagle_post_free
+    bool has_shape = false;
+    bool has_hulls = false;              // eagle_minimap_set_hulls
+    EagleHullParams hulls{};
 };
 
 namespace eagle {
@@ -350,6 +354,15 @@ struct MmPlan { int S, M, w, h, r, rb, t; };
 MmPlan minimap_plan(const EagleMinimapParams* p);                               // EAGLE_E_INVALID unless the parameters are in range; canvas size and radii
 std::vector<uint8_t> markings_mask(const MmPlan& pl, int* pitch);               // the white markings of a (scale, margin) as a bit mask, rows of (w + 7) / 8 bytes
 const uint8_t* minimap_mask(EagleHandle* h, const MmPlan& pl);                  // the same in HBM, kept in the handle for the last (scale, margin); synchronises s_main
+// shape.hip (K26): what the minimap's hull layer and eagle_op_minimap_hulls need from it
+struct ShapeCols { std::vector<int32_t> gcols; int n0 = 0, n1 = 0; };   // the member columns in table order, group 0's and then group 1's
+// EAGLE_E_INVALID without a mapping, for a column of unknown kind and beyond EAGLE_SHAPE_MAX_MEMBERS members
+ShapeCols shape_columns(const char* who, const EaglePostColumn* columns, int ncols, const int32_t* team_ids, const int32_t* team_vals, size_t n_team);
+void hull_check(const char* who, const EagleHullParams* p);
+// the two launches on stream s (h: timed under its profiling mode, or nullptr); returns when the records and vertices are complete
+void shape_run(EagleHandle* h, const ShapeCols& sc, const double2* d_values, int rows, EagleTeamShape* d_shapes, int32_t* d_hull, hipStream_t s);
+// rows row0 .. row0 + n - 1 -> edges [n][2][EAGLE_SHAPE_HULL_CAP] = {A, B} in the minimap's quantisation (x == MM_ABSENT: no edge); no synchronisation
+void shape_edges_launch(const double2* values, int rows, const EagleTeamShape* shapes, const int32_t* hull, int row0, int n, int scale, int margin, int4* edges, hipStream_t s);
 }  // namespace eagle
 
 // ---- C ABI: the body of every entry runs between API_BEGIN and API_END ---------------------------------------

@@ -28,6 +28,8 @@ struct MmLayerArgs {
     int range_row0, only;        // only != 0: the pass still (the one event of the range shows whatever its rows are)
     int dim, pass_from, pass_to; // dim != 0: person discs of other columns than these two are blended at a = 64
     int r16o;                    // 16 x the owner ring's outer radius
+    const int4* hull_edges;      // K26 hulls: [pictures of the call][2][EAGLE_SHAPE_HULL_CAP] = {A, B} (x == MM_ABSENT: no edge); nullptr: layer off (shape.hip)
+    int hull_hw16;               // 16 x the hull layer's half width
 };
 
 __device__ __forceinline__ bool mm_quantise(double2 v, double K, int ox, int oy, int& qx, int& qy)

@@ -80,7 +80,18 @@ class EagleTrailParams(C.Structure):
     _fields_ = [("window", C.c_int32), ("max_gap", C.c_int32), ("half_width", C.c_int32), ("pass_hold", C.c_int32), ("dim_floor", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
-MM_TRAILS, MM_PASSES, MM_OWNER = 1, 2, 4                                # include/eagle.h EAGLE_MM_*
+MM_TRAILS, MM_PASSES, MM_OWNER, MM_HULLS = 1, 2, 4, 8                    # include/eagle.h EAGLE_MM_*
+
+
+class EagleHullParams(C.Structure):
+    """include/eagle.h EagleHullParams: half the line width (px) of the minimap's hull layer."""
+    _fields_ = [("half_width", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+SHAPE_HULL_CAP, SHAPE_MAX_MEMBERS, SHAPE_CUT, SHAPE_Q = 32, 4096, 1, 1024   # include/eagle.h EAGLE_SHAPE_*; positions are quantised to 1 / SHAPE_Q metres
+SHAPE_DTYPE = np.dtype([("sum_x", "<i8"), ("sum_y", "<i8"), ("sum_xx", "<i8"), ("sum_yy", "<i8"), ("area2", "<i8"), ("n", "<i4"), ("hull_n", "<i4"),
+                        ("flags", "<i4"), ("reserved0", "<i4"), ("min_x", "<i4"), ("max_x", "<i4"), ("min_y", "<i4"), ("max_y", "<i4"),
+                        ("col_min_x", "<i4"), ("col_max_x", "<i4"), ("col_min_y", "<i4"), ("col_max_y", "<i4"), ("reserved", "<i4", 2)])      # EagleTeamShape (96 bytes)
 
 
 class EagleKinematicsParams(C.Structure):
@@ -269,6 +280,13 @@ def load():
     L.eagle_op_minimap_trails.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, tp, vp, i32, vp, vp, i32, i32, i32, i32, yl, vp]
     L.eagle_op_trajectory_picture.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.eagle_op_pass_picture.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
+    hp = C.POINTER(EagleHullParams)
+    L.eagle_post_team_shape.argtypes = [vp, vp]
+    L.eagle_post_team_shape_values.argtypes = [vp, vp, vp]
+    L.eagle_post_device_team_shape.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.eagle_minimap_set_hulls.argtypes = [vp, hp]
+    L.eagle_op_team_shape.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, vp, vp]
+    L.eagle_op_minimap_hulls.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, hp, tp, vp, i32, vp, vp, i32, i32, i32, i32, yl, vp]
     L.eagle_op_reid_crop.argtypes = [i32, u8p, i32, i32, i32, vp, i32, i32, i32, i32, i32, fp]
     L.eagle_op_reid_conv7.argtypes = [i32, fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
     L.eagle_op_reid_maxpool3s2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -299,7 +317,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_minimap_control", "eagle_post_possession", "eagle_post_possession_values", "eagle_post_device_possession", "eagle_post_events",
            "eagle_op_possession", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
            "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_minimap_set_trails", "eagle_trajectory_picture",
-           "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_post_team_shape", "eagle_post_team_shape_values",
+           "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -741,6 +760,28 @@ class Handle:
         out = np.zeros((h, w, 3), np.uint8)
         self._check(self.L.eagle_pass_picture(self._h, table._t, int(event), mp.scale, mp.margin, int(half_width), out.ctypes.data_as(C.c_void_p)), "pass_picture")
         return out
+
+    # --- team shape (include/eagle.h, eagle_post_team_shape / eagle_minimap_set_hulls) ---------------------------------------
+    def team_shape(self, table):
+        """The shape records and hulls of a PostTable of this handle (it needs a team mapping), computed on the GPU and kept with the table (a second
+        call replaces the first) -> (SHAPE_DTYPE [rows, 2], int32 [rows, 2, SHAPE_HULL_CAP]: table columns, -1 padded).  eagle_amd.shape derives metres."""
+        self._check(self.L.eagle_post_team_shape(self._h, table._t), "post_team_shape")
+        rows = len(table.rows)
+        rec, hull = np.zeros((rows, 2), SHAPE_DTYPE), np.zeros((rows, 2, SHAPE_HULL_CAP), np.int32)
+        keep = np.zeros(4, np.float64)
+        self._check(self.L.eagle_post_team_shape_values(table._t, _ptr(rec, keep), _ptr(hull, keep)), "post_team_shape_values")
+        return rec, hull
+
+    def team_shape_device(self, table):
+        """(records, hull) in HBM (None, None before the first team_shape call of the table)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._check(self.L.eagle_post_device_team_shape(table._t, C.byref(a), C.byref(b)), "post_device_team_shape")
+        return a.value, b.value
+
+    def set_hulls(self, table, half_width=1):
+        """The half width (pixels, 1 .. 8; or an EagleHullParams) the minimap's hull layer (MM_HULLS) of this table is drawn with; None: forget it."""
+        p = half_width if isinstance(half_width, EagleHullParams) or half_width is None else hull_params(half_width)
+        self._check(self.L.eagle_minimap_set_hulls(table._t, None if p is None else C.byref(p)), "minimap_set_hulls")
 
     def minimap_set_control(self, table, params):
         """The parameters the minimap's ``control`` layer of this table is computed with (None: forget them)."""
@@ -1278,7 +1319,8 @@ def op_annotate(frames, prims, offsets, fmt="bgr", layout=None, out=None, device
 # --- the minimap ------------------------------------------------------------------------------------------------
 def minimap_params(scale=8, margin=None, voronoi=False, footprint=True, player_radius=0, ball_radius=0, control=False, layers=0):
     """EagleMinimapParams; margin None: two metres' worth of pixels, at most 64.  control: the pitch-control layer (Handle.minimap_set_control /
-    op_minimap_control say with which parameters).  layers: MM_TRAILS | MM_PASSES | MM_OWNER (Handle.minimap_set_trails / op_minimap_trails)."""
+    op_minimap_control say with which parameters).  layers: MM_TRAILS | MM_PASSES | MM_OWNER (Handle.minimap_set_trails / op_minimap_trails) | MM_HULLS
+    (Handle.team_shape and Handle.set_hulls / op_minimap_hulls)."""
     if margin is None:
         margin = min(64, 2 * int(scale))
     return EagleMinimapParams(int(scale), int(margin), int(bool(voronoi)), int(bool(footprint)), int(player_radius), int(ball_radius), int(bool(control)), int(layers))
@@ -1678,15 +1720,46 @@ def trail_params(window=25, max_gap=25, half_width=1, pass_hold=5, dim_floor=64)
 def op_minimap_trails(values, frames, columns, team_mapping, params, trail, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None, device=0):
     """op_minimap with the trail, pass-arrow and owner layers (include/eagle.h eagle_op_minimap_trails): frames int32 [rows], params minimap_params(...,
     layers=...), trail trail_params(...) (None with layers == 0), sel the selected table columns, owner int32 [rows] or None, events EVENT_DTYPE or None."""
+    return _op_minimap_layers("op_minimap_trails", values, frames, columns, team_mapping, params, None, trail, sel, owner, events, row0, n, fmt, layout, out, device)
+
+
+def hull_params(half_width=1):
+    """EagleHullParams: a thin line is the conventional choice."""
+    return EagleHullParams(int(half_width))
+
+
+def op_team_shape(values, columns, team_mapping, device=0):
+    """The team-shape launches on a constructed table (include/eagle.h eagle_op_team_shape): values float64 [cols][rows][2], columns [(kind, id, video)]
+    -> (SHAPE_DTYPE [rows, 2], int32 [rows, 2, SHAPE_HULL_CAP])."""
     L = load()
-    values, columns = _table_args("op_minimap_trails", values, columns)
+    values, columns = _table_args("op_team_shape", values, columns)
+    cols, rows = values.shape[:2]
+    ids, vals, nt = _team_arrays(team_mapping)
+    rec, hull = np.zeros((rows, 2), SHAPE_DTYPE), np.full((rows, 2, SHAPE_HULL_CAP), -1, np.int32)
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_team_shape(device, _ptr(values, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, _ptr(rec, keep), _ptr(hull, keep))
+    if rc:
+        raise EagleError(f"eagle_op_team_shape failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return rec, hull
+
+
+def op_minimap_hulls(values, frames, columns, team_mapping, params, hull, trail=None, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None,
+                     device=0):
+    """op_minimap_trails with the hull layer (include/eagle.h eagle_op_minimap_hulls): the entry computes the team shape itself; hull hull_params(...)
+    (None without MM_HULLS in params.layers), trail None without the other three bits."""
+    return _op_minimap_layers("op_minimap_hulls", values, frames, columns, team_mapping, params, hull, trail, sel, owner, events, row0, n, fmt, layout, out, device, True)
+
+
+def _op_minimap_layers(name, values, frames, columns, team_mapping, params, hull, trail, sel, owner, events, row0, n, fmt, layout, out, device, hulls=False):
+    L = load()
+    values, columns = _table_args(name, values, columns)
     cols, rows = values.shape[:2]
     frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
     sel = np.ascontiguousarray(sel, np.int32)
     owner = None if owner is None else np.ascontiguousarray(owner, np.int32)
     events = None if events is None else np.ascontiguousarray(events, EVENT_DTYPE)
     if (frames is not None and len(frames) != rows) or (owner is not None and len(owner) != rows):
-        raise EagleError("op_minimap_trails: one frame number and one owner per row")
+        raise EagleError(f"{name}: one frame number and one owner per row")
     ids, vals, nt = _team_arrays(team_mapping)
     n = rows - row0 if n is None else n
     w, h = minimap_size(params)
@@ -1695,14 +1768,17 @@ def op_minimap_trails(values, frames, columns, team_mapping, params, trail, sel=
     if out is None:
         out = np.zeros(need, np.uint8)
     if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
-        raise EagleError(f"op_minimap_trails: out must be a contiguous uint8 array of at least {need} bytes")
+        raise EagleError(f"{name}: out must be a contiguous uint8 array of at least {need} bytes")
     keep = np.zeros(16, np.float64)
-    rc = L.eagle_op_minimap_trails(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(params),
-                                   None if trail is None else C.byref(trail), _ptr(sel, keep), len(sel), _ptr(owner, keep), _ptr(events, keep),
-                                   0 if events is None else len(events), int(row0), int(n), _out_pix(fmt), None if lay is None else C.byref(lay),
-                                   out.ctypes.data_as(C.c_void_p))
+    head = (device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(params))
+    tail = (None if trail is None else C.byref(trail), _ptr(sel, keep), len(sel), _ptr(owner, keep), _ptr(events, keep), 0 if events is None else len(events), int(row0),
+            int(n), _out_pix(fmt), None if lay is None else C.byref(lay), out.ctypes.data_as(C.c_void_p))
+    if hulls:
+        rc = L.eagle_op_minimap_hulls(*head, None if hull is None else C.byref(hull), *tail)
+    else:
+        rc = L.eagle_op_minimap_trails(*head, *tail)
     if rc:
-        raise EagleError(f"eagle_op_minimap_trails failed ({rc}): {L.eagle_last_error(None).decode()}")
+        raise EagleError(f"eagle_{name} failed ({rc}): {L.eagle_last_error(None).decode()}")
     if lay is None:
         return out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
     return out

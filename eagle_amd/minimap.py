@@ -9,15 +9,18 @@ from . import lib
 
 
 def minimap(handle, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, player_radius=0, ball_radius=0, control=None,
-            trails=None, passes=False, owner=False, trail_params=None):
+            trails=None, passes=False, owner=False, trail_params=None, hulls=None):
     """A lib.PostTable of ``handle`` -> its minimap pictures on the host: uint8 [n, h, w, 3] ("bgr") or [n, 3h/2, w] ("nv12" / "i420"), one per table
     row, with w = 105 scale + 2 margin and h = 68 scale + 2 margin (margin None: two metres' worth of pixels).  ``rows``: (first row, count) to draw
     a window of the table.  voronoi needs a table with a team mapping.  ``control``: a lib.control_params(...) draws the pitch-control layer in
     Voronoi's place (not both); the table needs velocities (Handle.velocities) and a team mapping.  ``trails``: table columns whose paths over the last
     rows are drawn; ``passes`` / ``owner``: an arrow per possession event and a ring round the ball's owner (Handle.possession comes first);
-    ``trail_params``: a lib.trail_params(...) for the three (None: its defaults)."""
+    ``trail_params``: a lib.trail_params(...) for the three (None: its defaults).  ``hulls``: half the line width in pixels (1 .. 8) of the two teams'
+    convex hulls, drawn under the trails (Handle.team_shape comes first; None: no hulls)."""
     layers = (lib.MM_TRAILS if trails is not None and len(trails) else 0) | (lib.MM_PASSES if passes else 0) | (lib.MM_OWNER if owner else 0)
-    params = lib.minimap_params(scale, margin, voronoi, footprint, player_radius, ball_radius, control is not None, layers)
+    params = lib.minimap_params(scale, margin, voronoi, footprint, player_radius, ball_radius, control is not None, layers | (lib.MM_HULLS if hulls is not None else 0))
+    if hulls is not None:
+        handle.set_hulls(table, hulls)
     if layers:
         handle.minimap_set_trails(table, trail_params or lib.trail_params(), () if trails is None else trails)
     if control is not None:

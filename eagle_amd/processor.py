@@ -55,12 +55,13 @@ class Processor:
         return self.model.annotate(frames, coords_or_records, team_mapping, pixel_format, out_format, table=table)
 
     def minimap(self, table, scale=8, margin=None, voronoi=False, footprint=True, pixel_format="bgr", rows=None, control=None, trails=None, passes=False, owner=False,
-                trail_params=None):
+                trail_params=None, hulls=None):
         """The minimap pictures of a processed table (process_data above), drawn on the GPU: see eagle_amd/minimap.py.  trails (table columns), passes and
-        owner add the paths, the pass arrows and the owner's ring (the last two after possession below)."""
+        owner add the paths, the pass arrows and the owner's ring (the last two after possession below); hulls (a half width in pixels) the two teams'
+        convex hulls (after shape below)."""
         from . import minimap as mm
         return mm.minimap(self.model.handle, table, scale, margin, voronoi, footprint, pixel_format, rows, control=control, trails=trails, passes=passes, owner=owner,
-                          trail_params=trail_params)
+                          trail_params=trail_params, hulls=hulls)
 
     def trajectory(self, table, cols, rows=None, scale=8, margin=None, half_width=1, max_gap=25):
         """The paths of table columns over a row window as one still picture of the pitch (BGR): see eagle_amd/minimap.py trajectory_picture."""
@@ -93,3 +94,9 @@ class Processor:
         """Where every player, every team and the ball of a processed table spent their time, as smoothed seconds per pitch cell: see eagle_amd/occupancy.py."""
         from . import occupancy as oc
         return oc.occupancy(self.model.handle, table, fps, cells_per_metre, sigma, max_gap)
+
+    def shape(self, table):
+        """Each team as a body in every kept frame of a processed table (centroid, length, width, hull area, stretch, lines, hull) and what that adds up
+        to over the clip: see eagle_amd/shape.py."""
+        from . import shape as sh
+        return sh.shape(self.model.handle, table)

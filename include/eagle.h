@@ -334,7 +334,7 @@ typedef struct EagleMinimapParams {
     int32_t player_radius;         /* pixels, 0 .. 4 scale; 0 = max(2, scale) */
     int32_t ball_radius;           /* outer radius of the ring, pixels, 0 .. 4 scale; 0 = max(3, scale / 2 + 1); the ring is max(1, radius / 3) thick */
     int32_t control;               /* != 0: draw the pitch-control layer in Voronoi's slot (below: eagle_minimap_set_control); refused together with voronoi */
-    int32_t layers;                /* bit mask of EAGLE_MM_* (below: eagle_minimap_set_trails); 0: none of them, the minimap as it is without them */
+    int32_t layers;                /* bit mask of EAGLE_MM_* (below: eagle_minimap_set_trails, eagle_minimap_set_hulls); 0: none of them, the minimap as it is without them */
 } EagleMinimapParams;
 int eagle_minimap_size(const EagleMinimapParams* p, int* w, int* h);
 /* rows row0 .. row0 + n - 1 -> n pictures in HBM (a buffer of the caller: eagle_device_alloc, or an encoder's input surface with its layout); returns when
@@ -499,6 +499,67 @@ int eagle_op_trajectory_picture(int device, const double* values, const int32_t*
                                 uint8_t* out);
 int eagle_op_pass_picture(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
                           int n_team, const EaglePossessionEvent* events, int n_events, int event, int scale, int margin, int half_width, uint8_t* out);
+
+/* ---- team shape per row: members, sums, extrema and the exact convex hull of each team; the minimap's hull layer (own specification: tests/shape_ref.py
+ * defines every output bit and byte) ----
+ * GROUPS   0 = team value 0, 1 = any other non-negative team value (the minimap's red / blue).  The members of a group are the Player pitch columns
+ *          (video == 0) with a mapping entry of that group; a column's team is the first mapping entry with its id (the possession rule).  Goalkeepers,
+ *          balls, boundary columns and players without an entry (or with a negative one) are no members.  A mapping is required.  A member is PRESENT on a
+ *          row when x and y are finite and |x|, |y| <= 1024 m (the minimap's rule: every hull vertex can be drawn).
+ *   QUANTISE qx = (int) floor(x * 1024.0 + 0.5), qy likewise (float64, no contraction; the multiply is exact).  |q| <= 2^20, every product below stays
+ *            under 2^45 and is exact in int64; all sums are integers, so no order of accumulation matters.
+ *   RECORD   one EagleTeamShape per row and group: n present members, the sums of q and q^2, the extrema and the EARLIEST table column attaining each (0
+ *            and -1 when n == 0), hull_n = the true number of hull vertices, area2 = twice the hull's area in q^2 (over all vertices, >= 0).
+ *   HULL     int32 [rows][2][EAGLE_SHAPE_HULL_CAP] table columns, counter-clockwise with pitch y up, -1 padded; EAGLE_SHAPE_CUT in flags when hull_n
+ *            exceeds the cap.  The start is the present member with the smallest (qy, qx, column).  From the current vertex c the candidates are the
+ *            present members whose q differs from q_c; p beats the best so far b when o = (bx - cx)(py - cy) - (by - cy)(px - cx) < 0, or o == 0 and
+ *            |p - c|^2 > |b - c|^2, or both are equal and p's column is smaller.  The march ends when the winner is the start, without a candidate, and after
+ *            at most n steps.  A point strictly inside an edge is no vertex, coincident points are one (the earliest column); all coincident: hull_n 1;
+ *            all collinear: hull_n 2, area2 0.
+ *   LAYER    EAGLE_MM_HULLS in EagleMinimapParams::layers: per group (0 first) the stored vertices joined by capsules (the trails' exact rule) of
+ *            EagleHullParams::half_width pixels, drawn after the markings and before the trails, opaque, in the group's disc colour scaled (c * 160) >> 8.
+ *            hull_n >= 3: the closed polygon, without its closing edge when the list is cut; hull_n == 2: one segment; below: nothing.  It needs
+ *            eagle_post_team_shape and eagle_minimap_set_hulls.  eagle_op_minimap_trails cannot carry a shape result and refuses the bit.
+ * Two launches (shape.hip) on the handle's main stream read the table where eagle_postprocess left it, a third prepares the layer's edges; the handle's
+ * records, staging buffers and graphs are not involved.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, a table without a mapping, more than EAGLE_SHAPE_MAX_MEMBERS members over both
+ * groups, half_width outside 1 .. 8, the hull bit without a team-shape result or without eagle_minimap_set_hulls, a column of unknown kind, frames of an
+ * operator entry that do not ascend strictly, and what the minimap and its other layers refuse.  rows == 0 is success and writes nothing. */
+#define EAGLE_MM_HULLS 8
+#define EAGLE_SHAPE_HULL_CAP 32
+#define EAGLE_SHAPE_MAX_MEMBERS 4096
+#define EAGLE_SHAPE_CUT 1          /* EagleTeamShape::flags: the hull has more than EAGLE_SHAPE_HULL_CAP vertices, the stored list holds the first of them */
+typedef struct EagleTeamShape {
+    int64_t sum_x, sum_y;          /* over the present members, of q */
+    int64_t sum_xx, sum_yy;        /* ... of q^2 */
+    int64_t area2;                 /* twice the hull's area, q^2 */
+    int32_t n;                     /* present members */
+    int32_t hull_n;                /* hull vertices (all of them) */
+    int32_t flags;                 /* EAGLE_SHAPE_CUT */
+    int32_t reserved0;
+    int32_t min_x, max_x, min_y, max_y;                      /* q; 0 when n == 0 */
+    int32_t col_min_x, col_max_x, col_min_y, col_max_y;      /* the earliest table column attaining each; -1 when n == 0 */
+    int32_t reserved[2];
+} EagleTeamShape;                  /* 96 bytes */
+typedef struct EagleHullParams {
+    int32_t half_width;            /* 1 .. 8 pixels */
+    int32_t reserved[3];
+} EagleHullParams;
+/* The result is kept with the table until eagle_post_free and replaces an earlier one. */
+int eagle_post_team_shape(EagleHandle* h, EaglePostTable* t);
+int eagle_post_team_shape_values(EaglePostTable* t, EagleTeamShape* shapes /* [rows][2] */, int32_t* hull /* [rows][2][EAGLE_SHAPE_HULL_CAP] */);   /* to the host; either may be NULL */
+int eagle_post_device_team_shape(const EaglePostTable* t, const EagleTeamShape** d_shapes, const int32_t** d_hull);      /* in HBM; both NULL before eagle_post_team_shape */
+/* The hull layer's parameters are kept with the table (p NULL: forget them). */
+int eagle_minimap_set_hulls(EaglePostTable* t, const EagleHullParams* p);
+/* Operator entries (host buffers in / out, no handle) for constructed tables, as eagle_op_possession and eagle_op_minimap_trails: shapes and hull may be
+ * NULL.  eagle_op_minimap_hulls computes the shape itself and draws any combination of the four layer bits: hp is needed with EAGLE_MM_HULLS, tp with any
+ * of the other three (sel, owner, events as in eagle_op_minimap_trails), frames with EAGLE_MM_TRAILS. */
+int eagle_op_team_shape(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
+                        int n_team, EagleTeamShape* shapes, int32_t* hull);
+int eagle_op_minimap_hulls(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                           const int32_t* team_vals, int n_team, const EagleMinimapParams* p, const EagleHullParams* hp, const EagleTrailParams* tp, const int32_t* sel,
+                           int nsel, const int32_t* owner, const EaglePossessionEvent* events, int n_events, int row0, int n, int out_format,
+                           const EagleYuvLayout* out_layout, uint8_t* out);
 
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
