@@ -23,7 +23,9 @@ turnovers, and what they add up to per id, per team and per pair of ids (eagle_a
 (eagle_amd/occupancy.py; ``--occupancy-grid`` cells per metre, ``--occupancy-sigma`` metres of Gaussian smoothing, ``--occupancy-pictures`` one PPM per
 team and one for the ball); the maps follow a person only with ``--merge-ids``.  ``--shape`` (with ``--processed``) writes ``shape.json``: per kept
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
-draws the two hulls into the minimap.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
+zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -129,7 +131,28 @@ def main(argv=None):
     ap.add_argument("--minimap-hulls", nargs="?", const="1", default=None, metavar="W",
                     help="with --minimap: draw the convex hull of each team, W pixels either side of the line (1 .. 8, default 1); computes the team shape if "
                          "--shape did not")
+    ap.add_argument("--physical", action="store_true",
+                    help="with --processed: also write <out>/physical.json, per id the distance and the seconds per speed zone, the total distance, the top speed and "
+                         "the high-speed runs, sprints, accelerations and decelerations (computes the velocities with the --kinematics defaults if they are absent; the "
+                         "figures follow a person only with --merge-ids)")
+    ap.add_argument("--physical-rows", action="store_true",
+                    help="with --physical: also write the speed (m/s), its derivative (m/s^2) and the zone per id and kept frame into physical.json")
+    ap.add_argument("--physical-edges", default=None, metavar="a,b,c,d",
+                    help="with --physical: the four zone edges in m/s, strictly ascending (default 2,4,5.5,7: conventional choices, not fitted to data)")
     a = ap.parse_args(argv)
+    if a.physical and not a.processed:
+        ap.error("--physical works on the processed table: it needs --processed")
+    if a.physical_rows and not a.physical:
+        ap.error("--physical-rows adds to the physical report: it needs --physical")
+    if a.physical_edges is not None:
+        if not a.physical:
+            ap.error("--physical-edges sets the zones of the physical report: it needs --physical")
+        try:
+            a.physical_edges = [float(tok) for tok in a.physical_edges.split(",")]
+        except ValueError:
+            a.physical_edges = []
+        if len(a.physical_edges) != 4 or not all(0.0 < x < float("inf") for x in a.physical_edges) or any(x >= y for x, y in zip(a.physical_edges, a.physical_edges[1:])):
+            ap.error("--physical-edges takes four positive speeds in m/s, strictly ascending")
     if a.shape and not a.processed:
         ap.error("--shape works on the processed table: it needs --processed")
     if a.minimap_hulls is not None:
@@ -231,6 +254,13 @@ def main(argv=None):
                 np.save(os.path.join(a.out, "control.npy"), grids)
                 with open(os.path.join(a.out, "control_share.json"), "w") as f:
                     json.dump({"cells_per_metre": a.control_grid, "frames": [int(r) for r in table.rows], "team0_share": [float(v) for v in share]}, f)
+        if a.physical:
+            from . import physical as ph
+            if not (a.kinematics or a.minimap_control or a.control_grid):
+                model.handle.velocities(table, a.fps)
+            d = ph.physical(model.handle, table, a.fps, **({} if a.physical_edges is None else {"zone_edges": a.physical_edges}))
+            with open(os.path.join(a.out, "physical.json"), "w") as f:
+                json.dump(ph.to_json(d, rows=a.physical_rows), f)
         if a.possession:
             from . import possession as po
             with open(os.path.join(a.out, "possession.json"), "w") as f:

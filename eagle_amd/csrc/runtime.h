@@ -299,6 +299,11 @@ struct EaglePostTable {
     bool has_shape = false;
     bool has_hulls = false;              // eagle_minimap_set_hulls
     EagleHullParams hulls{};
+    void* d_phys = nullptr;              // physical report (eagle_post_physical): speed f64 | accel f64 | zone u8, [phys_persons][rows] each, resident until eagle_post_free
+    int phys_persons = 0;
+    bool has_phys = false;
+    std::vector<EagleLoadTotals> phys_totals;
+    std::vector<EagleLoadEffort> phys_efforts;
 };
 
 namespace eagle {

@@ -109,6 +109,21 @@ class EaglePossessionParams(C.Structure):
     _fields_ = [("fps", C.c_int32), ("min_hold", C.c_int32), ("max_gap", C.c_int32), ("reserved0", C.c_int32), ("radius", C.c_double), ("reserved", C.c_int64)]
 
 
+class EagleLoadParams(C.Structure):
+    """include/eagle.h EagleLoadParams: frames per second, the largest frame step that links two rows, the shortest effort in frames (speed kinds,
+    acceleration kinds), the four zone edges (m/s), the speeds a high-speed run and a sprint start at (m/s), the acceleration threshold (m/s^2)."""
+    _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("min_frames", C.c_int32 * 2), ("zone_edges", C.c_double * 4), ("effort_speed", C.c_double * 2),
+                ("accel", C.c_double), ("reserved", C.c_int64 * 2)]
+
+
+LOAD_HSR, LOAD_SPRINT, LOAD_ACCEL, LOAD_DECEL, LOAD_ABSENT, LOAD_Q = 0, 1, 2, 3, 255, 1 << 20    # include/eagle.h EAGLE_LOAD_*; distances are in 1 / LOAD_Q metres
+LOAD_TOTALS_DTYPE = np.dtype([("zone_frames", "<i8", 5), ("zone_dist_q", "<i8", 5), ("top_speed", "<f8"), ("col", "<i4"), ("rows_present", "<i4"),
+                              ("efforts", "<i4", 4), ("reserved", "<i4", 4)])                                      # EagleLoadTotals (128 bytes)
+LOAD_EFFORT_DTYPE = np.dtype([("col", "<i4"), ("kind", "<i4"), ("first_row", "<i4"), ("last_row", "<i4"), ("frames", "<i4"), ("reserved0", "<i4"),
+                              ("distance_q", "<i8"), ("peak_speed", "<f8"), ("peak_accel", "<f8")])                # EagleLoadEffort (48 bytes)
+assert C.sizeof(EagleLoadParams) == 88 and LOAD_TOTALS_DTYPE.itemsize == 128 and LOAD_EFFORT_DTYPE.itemsize == 48  # the sizes physical.hip asserts of the C structs
+
+
 class EagleOccupancyParams(C.Structure):
     """include/eagle.h EagleOccupancyParams: frames per second, the largest frame step a row may stand for, cells per metre, the Gaussian's sigma (m)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("cells_per_metre", C.c_int32), ("reserved0", C.c_int32), ("sigma", C.c_double), ("reserved", C.c_int64)]
@@ -287,6 +302,13 @@ def load():
     L.eagle_minimap_set_hulls.argtypes = [vp, hp]
     L.eagle_op_team_shape.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, vp, vp]
     L.eagle_op_minimap_hulls.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, hp, tp, vp, i32, vp, vp, i32, i32, i32, i32, yl, vp]
+    lp = C.POINTER(EagleLoadParams)
+    L.eagle_post_physical.argtypes = [vp, vp, lp]
+    L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
+    L.eagle_post_physical_totals.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_post_physical_efforts.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_post_device_physical.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.eagle_op_physical.argtypes = [i32, vp, vp, vp, i32, i32, lp, vp, vp, vp, vp, i32, C.POINTER(C.c_int), vp, i32, C.POINTER(C.c_int)]
     L.eagle_op_reid_crop.argtypes = [i32, u8p, i32, i32, i32, vp, i32, i32, i32, i32, i32, fp]
     L.eagle_op_reid_conv7.argtypes = [i32, fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, fp]
     L.eagle_op_reid_maxpool3s2.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -318,7 +340,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_possession", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
            "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_minimap_set_trails", "eagle_trajectory_picture",
            "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_post_team_shape", "eagle_post_team_shape_values",
-           "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
+           "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -703,6 +726,33 @@ class Handle:
         d = C.c_void_p()
         self._check(self.L.eagle_post_device_possession(table._t, C.byref(d)), "post_device_possession")
         return d.value
+
+    # --- physical report (include/eagle.h, eagle_post_physical) ------------------------------------------------------------
+    def physical(self, table, params):
+        """Speed, its derivative and the speed zone per person and row, the totals per person and the efforts of a PostTable of this handle with
+        velocities (Handle.velocities), computed on the GPU and kept with the table (a second call replaces the first) -> (speed float64, accel float64,
+        zone uint8: [persons, rows] each; totals LOAD_TOTALS_DTYPE [persons]; efforts LOAD_EFFORT_DTYPE in (person, kind, first_row) order).  The persons
+        are the Player and Goalkeeper pitch columns in table order (totals["col"]); without rows or persons everything is empty."""
+        self._check(self.L.eagle_post_physical(self._h, table._t, C.byref(params)), "post_physical")
+        keep = np.zeros(4, np.float64)
+        n = C.c_int(0)
+        self._check(self.L.eagle_post_physical_totals(table._t, None, 0, C.byref(n)), "post_physical_totals")
+        totals = np.zeros(n.value, LOAD_TOTALS_DTYPE)
+        self._check(self.L.eagle_post_physical_totals(table._t, _ptr(totals, keep), n.value, C.byref(n)), "post_physical_totals")
+        persons, rows = len(totals), len(table.rows)
+        speed, accel, zone = np.zeros((persons, rows), np.float64), np.zeros((persons, rows), np.float64), np.zeros((persons, rows), np.uint8)
+        if persons and rows:
+            self._check(self.L.eagle_post_physical_values(table._t, _ptr(speed, keep), _ptr(accel, keep), _ptr(zone, keep)), "post_physical_values")
+        self._check(self.L.eagle_post_physical_efforts(table._t, None, 0, C.byref(n)), "post_physical_efforts")
+        ev = np.zeros(n.value, LOAD_EFFORT_DTYPE)
+        self._check(self.L.eagle_post_physical_efforts(table._t, _ptr(ev, keep), n.value, C.byref(n)), "post_physical_efforts")
+        return speed, accel, zone, totals, ev
+
+    def physical_device(self, table):
+        """(speed float64, zone uint8) [persons, rows] in HBM (None, None before the first physical call of the table)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._check(self.L.eagle_post_device_physical(table._t, C.byref(a), C.byref(b)), "post_device_physical")
+        return a.value, b.value
 
     # --- occupancy heat maps (include/eagle.h, eagle_post_occupancy / eagle_occupancy_picture) -------------------------------
     def occupancy(self, table, params, sel_off, sel_cols):
@@ -1394,6 +1444,18 @@ def possession_params(fps, radius=2.0, min_hold=2, max_gap=None):
     return EaglePossessionParams(int(fps), int(min_hold), int(fps if max_gap is None else max_gap), 0, float(radius), 0)
 
 
+def load_params(fps, max_gap=None, zone_edges=(2.0, 4.0, 5.5, 7.0), effort_speed=(5.5, 7.0), accel=2.0, min_frames=None):
+    """EagleLoadParams; max_gap None: fps frames; min_frames None: max(1, fps // 2) for both durations (one int: both).  The edges (m/s), the speeds a
+    high-speed run and a sprint start at, 2 m/s^2 and half a second are conventional choices, not fitted to data."""
+    if min_frames is None:
+        min_frames = max(1, int(fps) // 2)
+    mf = (int(min_frames),) * 2 if np.isscalar(min_frames) else tuple(int(m) for m in min_frames)
+    if len(mf) != 2 or len(zone_edges) != 4 or len(effort_speed) != 2:
+        raise EagleError("load_params: two min_frames, four zone_edges and two effort_speed values")
+    return EagleLoadParams(int(fps), int(fps if max_gap is None else max_gap), (C.c_int32 * 2)(*mf), (C.c_double * 4)(*[float(x) for x in zone_edges]),
+                           (C.c_double * 2)(*[float(x) for x in effort_speed]), float(accel), (C.c_int64 * 2)(0, 0))
+
+
 def occupancy_params(fps, cells_per_metre=1, sigma=2.0, max_gap=None):
     """EagleOccupancyParams; max_gap None: fps frames.  The 2 m sigma is a conventional choice, not fitted to data."""
     return EagleOccupancyParams(int(fps), int(fps if max_gap is None else max_gap), int(cells_per_metre), 0, float(sigma), 0)
@@ -1484,6 +1546,34 @@ def op_possession(values, frames, columns, team_mapping, params, cap=None, devic
     if rc:
         raise EagleError(f"eagle_op_possession failed ({rc}): {L.eagle_last_error(None).decode()}")
     return cand, owner, dist, ev[: min(n.value, len(ev))].copy(), n.value
+
+
+def op_physical(velocities, frames, columns, params, cap=None, device=0):
+    """The physical-report launches on a constructed table (include/eagle.h eagle_op_physical): velocities float64 [cols][rows][2] (NaN where a cell is
+    absent), frames int32 [rows] strictly ascending, columns POSTCOL_DTYPE (or (kind, id, video) tuples) -> (speed, accel, zone: [persons, rows] each,
+    totals LOAD_TOTALS_DTYPE, efforts LOAD_EFFORT_DTYPE, n_efforts); cap None: every effort is fetched, else at most cap of the n_efforts."""
+    L = load()
+    velocities, columns = _table_args("op_physical", velocities, columns)
+    frames = np.ascontiguousarray(frames, np.int32)
+    cols, rows = velocities.shape[:2]
+    if len(frames) != rows:
+        raise EagleError("op_physical: one frame number per row")
+    persons = int(((columns["video"] == 0) & ((columns["kind"] == POST_PLAYER) | (columns["kind"] == POST_GOALKEEPER))).sum()) if rows else 0
+    speed, accel, zone = np.zeros((persons, rows), np.float64), np.zeros((persons, rows), np.float64), np.zeros((persons, rows), np.uint8)
+    totals = np.zeros(persons, LOAD_TOTALS_DTYPE)
+    keep = np.zeros(4, np.float64)
+    np_, ne = C.c_int(0), C.c_int(0)
+    want = 4096 if cap is None else int(cap)
+    while True:                                                        # cap None: a second call when the first guess was too small
+        ev = np.zeros(want, LOAD_EFFORT_DTYPE)
+        rc = L.eagle_op_physical(device, _ptr(velocities, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, C.byref(params), _ptr(speed, keep),
+                                 _ptr(accel, keep), _ptr(zone, keep), _ptr(totals, keep), len(totals), C.byref(np_), _ptr(ev, keep), len(ev), C.byref(ne))
+        if rc:
+            raise EagleError(f"eagle_op_physical failed ({rc}): {L.eagle_last_error(None).decode()}")
+        if cap is not None or ne.value <= want:
+            break
+        want = ne.value
+    return speed, accel, zone, totals[: np_.value].copy(), ev[: min(ne.value, len(ev))].copy(), ne.value
 
 
 def op_occupancy(values, frames, columns, params, sel_off, sel_cols, device=0):

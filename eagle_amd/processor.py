@@ -95,6 +95,12 @@ class Processor:
         from . import occupancy as oc
         return oc.occupancy(self.model.handle, table, fps, cells_per_metre, sigma, max_gap)
 
+    def physical(self, table, fps, max_gap=None, zone_edges=(2.0, 4.0, 5.5, 7.0), effort_speed=(5.5, 7.0), accel=2.0, min_frames=None):
+        """The physical report of a processed table with velocities (kinematics above): per id the distance and the seconds per speed zone, the top speed,
+        and the high-speed runs, sprints, accelerations and decelerations: see eagle_amd/physical.py."""
+        from . import physical as ph
+        return ph.physical(self.model.handle, table, fps, max_gap, zone_edges, effort_speed, accel, min_frames)
+
     def shape(self, table):
         """Each team as a body in every kept frame of a processed table (centroid, length, width, hull area, stretch, lines, hull) and what that adds up
         to over the clip: see eagle_amd/shape.py."""

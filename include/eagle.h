@@ -561,6 +561,80 @@ int eagle_op_minimap_hulls(int device, const double* values, const int32_t* fram
                            int nsel, const int32_t* owner, const EaglePossessionEvent* events, int n_events, int row0, int n, int out_format,
                            const EagleYuvLayout* out_layout, uint8_t* out);
 
+/* ---- physical report per person: speed zones, efforts (high-speed runs, sprints, accelerations, decelerations) and totals (own specification:
+ * tests/physical_ref.py defines every output bit) ----
+ * float64 without contraction, sqrt and division correctly rounded.  The inputs are the table's velocities (eagle_post_velocities) and frame numbers f.
+ * The PERSONS are the Player and Goalkeeper pitch columns (video == 0) in table order; every other column is ignored.  Per person column c and row r,
+ * with v = vel[c][r]:
+ *   ROW      pres[r]: vx and vy are finite (the velocity rule makes that "the cell is present").  s[r] = sqrt(vx vx + vy vy), NaN when absent.  link[r] =
+ *            r >= 1 && pres[r] && pres[r - 1] && f[r] - f[r - 1] <= max_gap.  a[r] = the speed differenced by the velocity kernel's neighbour rule: row
+ *            r - 1 is usable when link[r], row r + 1 when r + 1 < rows && link[r + 1]; both: (s[r + 1] - s[r - 1]) / ((double)(f[r + 1] - f[r - 1]) /
+ *            (double) fps); one: the one-sided form; none: 0; absent: NaN.  zone[r] = the number of k in 0 .. 3 with s[r] >= zone_edges[k], 255 when absent.
+ *   STEP     at every r with link[r]: df = f[r] - f[r - 1], m = 0.5 (s[r - 1] + s[r]), d = m ((double) df / (double) fps) clamped to at most 2^20,
+ *            q[r] = (int64) floor(d 1048576.0 + 0.5), zs[r] = the number of k with m >= zone_edges[k].
+ *   TOTALS   zone_frames[z] = the sum of df and zone_dist_q[z] = the sum of q over the steps with zs == z; rows_present; top_speed = the greatest s of a
+ *            present row (0.0 with none); efforts[kind] = the number of efforts.  Integers and a maximum: no order of accumulation can show.  Metres are
+ *            q / 2^20, seconds frames / fps.
+ *   EFFORT   kinds: 0 high-speed run (s >= effort_speed[0]), 1 sprint (s >= effort_speed[1]), 2 acceleration (a >= accel), 3 deceleration (a <=
+ *            -accel); hot_k[r] = pres[r] and the kind's condition.  head_k[r] = hot_k[r] && (!link[r] || !hot_k[r - 1]); tail_k[r] = hot_k[r] &&
+ *            (r == rows - 1 || !link[r + 1] || !hot_k[r + 1]); start_k[r] = the greatest head row <= r.  An effort exists at every tail row r with
+ *            f[r] - f[start_k[r]] >= min_frames[kind < 2 ? 0 : 1]: first_row = start_k[r], last_row = r, frames = f[r] - f[first_row], distance_q = the
+ *            sum of q over rows first_row + 1 .. r, peak_speed and peak_accel = the greatest s and |a| of rows first_row .. r (from 0.0, a value counts
+ *            when it is greater than the peak so far).  Efforts are reported in ascending (person order, kind, first_row).
+ * Three launches (physical.hip) on the handle's main stream read the velocities where eagle_post_velocities left them; the handle's records, staging
+ * buffers and graphs are not involved.  The result is kept with the table and answers to its max_bytes budget: the per-row arrays and the call's scratch
+ * are checked before any launch, the effort records (48 bytes each) against what is left once their number is known, in front of the third launch.  Edges at 2 / 4 / 5.5 / 7 m/s, efforts from
+ * 5.5 and 7 m/s, 2 m/s^2 and half a second are conventional choices, not fitted to data.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, fps, max_gap or a min_frames not positive, edges not finite, not positive or not
+ * strictly ascending, effort_speed or accel not finite or not positive, a table without velocities, a table of another handle, a column of unknown kind,
+ * frames of the operator entry that do not ascend strictly, a result beyond the budget.  rows == 0 or no person column is success with nothing written. */
+#define EAGLE_LOAD_HSR 0
+#define EAGLE_LOAD_SPRINT 1
+#define EAGLE_LOAD_ACCEL 2
+#define EAGLE_LOAD_DECEL 3
+#define EAGLE_LOAD_ABSENT 255      /* zone of an absent row */
+typedef struct EagleLoadParams {
+    int32_t fps;                   /* > 0: frames per second of the frame numbers */
+    int32_t max_gap;               /* > 0: a step of more frames than this links nothing (a usual choice: fps) */
+    int32_t min_frames[2];         /* > 0: the shortest effort in frames, [0] for the speed kinds, [1] for accelerations and decelerations */
+    double zone_edges[4];          /* m/s: finite, positive, strictly ascending */
+    double effort_speed[2];        /* m/s: finite, positive: high-speed run, sprint */
+    double accel;                  /* m/s^2: finite, positive */
+    int64_t reserved[2];
+} EagleLoadParams;                 /* 88 bytes */
+typedef struct EagleLoadTotals {
+    int64_t zone_frames[5];        /* frames of the steps whose mean speed lies in the zone */
+    int64_t zone_dist_q[5];        /* their distance in 2^-20 m */
+    double top_speed;              /* m/s; 0.0 without a present row */
+    int32_t col;                   /* the person's table column */
+    int32_t rows_present;
+    int32_t efforts[4];            /* per EAGLE_LOAD_* kind */
+    int32_t reserved[4];
+} EagleLoadTotals;                 /* 128 bytes */
+typedef struct EagleLoadEffort {
+    int32_t col, kind;             /* table column, EAGLE_LOAD_* */
+    int32_t first_row, last_row;
+    int32_t frames;                /* f[last_row] - f[first_row] */
+    int32_t reserved0;
+    int64_t distance_q;            /* 2^-20 m */
+    double peak_speed, peak_accel; /* m/s, m/s^2 (the magnitude) */
+} EagleLoadEffort;                 /* 48 bytes */
+/* The result is kept with the table until eagle_post_free and replaces an earlier one; it needs eagle_post_velocities.  A call that fails after its
+ * argument checks leaves the table without a result (the earlier one's arrays are rewritten in place). */
+int eagle_post_physical(EagleHandle* h, EaglePostTable* t, const EagleLoadParams* p);
+/* copies [persons][rows] each to the host; any pointer may be NULL */
+int eagle_post_physical_values(EaglePostTable* t, double* speed, double* accel, uint8_t* zone);
+/* *n = the number of persons / efforts of the last eagle_post_physical (0 before it); at most cap are written, in the order above. */
+int eagle_post_physical_totals(const EaglePostTable* t, EagleLoadTotals* out, int cap, int* n);
+int eagle_post_physical_efforts(const EaglePostTable* t, EagleLoadEffort* out, int cap, int* n);
+int eagle_post_device_physical(const EaglePostTable* t, const double** d_speed, const uint8_t** d_zone);     /* [persons][rows] in HBM; NULL before eagle_post_physical */
+/* Operator entry (host buffers in / out, no handle) for constructed tables: velocities [cols][rows][2], frames [rows] strictly ascending, columns as
+ * eagle_post_layout gives them.  speed, accel, zone ([persons][rows] each) may be NULL; at most totals_cap totals and efforts_cap efforts are written,
+ * *n_persons and *n_efforts are what there is. */
+int eagle_op_physical(int device, const double* velocities, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const EagleLoadParams* p,
+                      double* speed, double* accel, uint8_t* zone, EagleLoadTotals* totals, int totals_cap, int* n_persons, EagleLoadEffort* efforts,
+                      int efforts_cap, int* n_efforts);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
