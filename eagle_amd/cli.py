@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -139,7 +139,20 @@ def main(argv=None):
                     help="with --physical: also write the speed (m/s), its derivative (m/s^2) and the zone per id and kept frame into physical.json")
     ap.add_argument("--physical-edges", default=None, metavar="a,b,c,d",
                     help="with --physical: the four zone edges in m/s, strictly ascending (default 2,4,5.5,7: conventional choices, not fitted to data)")
+    ap.add_argument("--pass-options", action="store_true",
+                    help="with --processed: also write <out>/pass_options.json, per kept frame where the ball's owner could play (status, owner, best option, the "
+                         "option per teammate id) and per pass event how the pass played ranks among them (computes velocities and possession with their "
+                         "defaults if they are absent; 16 samples, 0.7 s, 5 m/s, 4 / s and a 15 m/s ball are conventional choices, not fitted to data)")
+    ap.add_argument("--pass-options-grid", type=int, default=None, choices=[1, 2, 4], metavar="R",
+                    help="with --pass-options: also write <out>/pass_options.npy (uint8 [rows, 68 R, 105 R]), the option surface per kept frame at R cells per metre")
+    ap.add_argument("--pass-options-pictures", action="store_true",
+                    help="with --pass-options: also write <out>/pass_options_<k>.ppm, the option surface at the release row of pass event k in the owner's team "
+                         "colour, at --minimap-scale pixels per metre")
     a = ap.parse_args(argv)
+    if a.pass_options and not a.processed:
+        ap.error("--pass-options works on the processed table: it needs --processed")
+    if (a.pass_options_grid is not None or a.pass_options_pictures) and not a.pass_options:
+        ap.error("--pass-options-grid and --pass-options-pictures add to the pass options: they need --pass-options")
     if a.physical and not a.processed:
         ap.error("--physical works on the processed table: it needs --processed")
     if a.physical_rows and not a.physical:
@@ -254,10 +267,11 @@ def main(argv=None):
                 np.save(os.path.join(a.out, "control.npy"), grids)
                 with open(os.path.join(a.out, "control_share.json"), "w") as f:
                     json.dump({"cells_per_metre": a.control_grid, "frames": [int(r) for r in table.rows], "team0_share": [float(v) for v in share]}, f)
+        have_vel = bool(a.kinematics or a.minimap_control or a.control_grid)
+        if (a.physical or a.pass_options) and not have_vel:
+            model.handle.velocities(table, a.fps)
         if a.physical:
             from . import physical as ph
-            if not (a.kinematics or a.minimap_control or a.control_grid):
-                model.handle.velocities(table, a.fps)
             d = ph.physical(model.handle, table, a.fps, **({} if a.physical_edges is None else {"zone_edges": a.physical_edges}))
             with open(os.path.join(a.out, "physical.json"), "w") as f:
                 json.dump(ph.to_json(d, rows=a.physical_rows), f)
@@ -280,8 +294,19 @@ def main(argv=None):
                 json.dump(sh.to_json(sh.shape(model.handle, table)), f)
         elif a.minimap_hulls is not None:
             model.handle.team_shape(table)
-        if (a.minimap_passes or a.pass_pictures) and not a.possession:
+        if (a.minimap_passes or a.pass_pictures or a.pass_options) and not a.possession:
             model.handle.possession(table, lib.possession_params(a.fps))
+        if a.pass_options:
+            from . import occupancy as oc, options as op
+            want_grid = a.pass_options_grid is not None or a.pass_options_pictures
+            res = op.pass_options(model.handle, table, a.pass_options_grid or 1, grids=want_grid)
+            with open(os.path.join(a.out, "pass_options.json"), "w") as f:
+                json.dump(op.to_json(res, table), f)
+            if a.pass_options_grid is not None:
+                np.save(os.path.join(a.out, "pass_options.npy"), res["grids"])
+            if a.pass_options_pictures:
+                for k, img in op.pictures(model.handle, table, res, a.minimap_scale):
+                    oc.write_ppm(os.path.join(a.out, "pass_options_%d.ppm" % k), img)
         entities = [c for c, k in enumerate(table.columns) if not k["video"] and int(k["kind"]) in (lib.POST_PLAYER, lib.POST_GOALKEEPER, lib.POST_BALL)]
         if a.trajectory is not None:
             from . import minimap as mm

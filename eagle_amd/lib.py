@@ -124,6 +124,21 @@ LOAD_EFFORT_DTYPE = np.dtype([("col", "<i4"), ("kind", "<i4"), ("first_row", "<i
 assert C.sizeof(EagleLoadParams) == 88 and LOAD_TOTALS_DTYPE.itemsize == 128 and LOAD_EFFORT_DTYPE.itemsize == 48  # the sizes physical.hip asserts of the C structs
 
 
+class EaglePassOptionParams(C.Structure):
+    """include/eagle.h EaglePassOptionParams: cells per metre (1, 2, 4), lane samples K (1 .. 64), reaction time (s), top speed (m/s), sharpness (1/s),
+    ball speed (m/s)."""
+    _fields_ = [("cells_per_metre", C.c_int32), ("samples", C.c_int32), ("t_react", C.c_float), ("v_max", C.c_float), ("beta", C.c_float), ("v_ball", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+PASS_ACTIVE, PASS_NO_OWNER, PASS_IN_FLIGHT, PASS_NO_TEAM, PASS_OFF_DOMAIN = 0, 1, 2, 3, 4    # include/eagle.h EAGLE_PASS_*
+PASS_STATUS_NAMES = ("active", "no_owner", "in_flight", "no_team", "off_domain")
+PASS_MAX_SITES = 1024
+PASS_ROW_DTYPE = np.dtype([("status", "<i4"), ("owner_col", "<i4"), ("group", "<i4"), ("n_mates", "<i4"), ("n_defenders", "<i4"), ("best_col", "<i4"),
+                           ("best_byte", "<i4"), ("reserved", "<i4"), ("sum", "<i8")])                             # EaglePassOptionRow (40 bytes)
+assert C.sizeof(EaglePassOptionParams) == 32 and PASS_ROW_DTYPE.itemsize == 40      # the sizes options.hip asserts of the C structs
+
+
 class EagleOccupancyParams(C.Structure):
     """include/eagle.h EagleOccupancyParams: frames per second, the largest frame step a row may stand for, cells per metre, the Gaussian's sigma (m)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("cells_per_metre", C.c_int32), ("reserved0", C.c_int32), ("sigma", C.c_double), ("reserved", C.c_int64)]
@@ -280,6 +295,12 @@ def load():
     L.eagle_post_device_possession.argtypes = [vp, C.POINTER(vp)]
     L.eagle_post_events.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_op_possession.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, pp, vp, vp, vp, vp, i32, C.POINTER(C.c_int)]
+    po = C.POINTER(EaglePassOptionParams)
+    L.eagle_pass_options_size.argtypes = [po, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.eagle_pass_options_layout.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_pass_options_device.argtypes = [vp, vp, i32, i32, po, vp, vp, vp]
+    L.eagle_pass_options.argtypes = [vp, vp, i32, i32, po, vp, vp, vp]
+    L.eagle_op_pass_options.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, po, i32, i32, vp, vp, vp]
     op = C.POINTER(EagleOccupancyParams)
     L.eagle_occupancy_size.argtypes = [op, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.eagle_post_occupancy.argtypes = [vp, vp, op, vp, vp, i32]
@@ -337,7 +358,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_minimap", "eagle_post_velocities", "eagle_post_velocity_values", "eagle_post_device_velocity_values", "eagle_control_size",
            "eagle_control_device_grids", "eagle_control_grids", "eagle_minimap_set_control", "eagle_op_velocities", "eagle_op_control",
            "eagle_op_minimap_control", "eagle_post_possession", "eagle_post_possession_values", "eagle_post_device_possession", "eagle_post_events",
-           "eagle_op_possession", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
+           "eagle_op_possession", "eagle_pass_options_size", "eagle_pass_options_layout", "eagle_pass_options_device", "eagle_pass_options",
+           "eagle_op_pass_options", "eagle_occupancy_size", "eagle_post_occupancy", "eagle_post_occupancy_values", "eagle_post_device_occupancy",
            "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_minimap_set_trails", "eagle_trajectory_picture",
            "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_post_team_shape", "eagle_post_team_shape_values",
            "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
@@ -726,6 +748,35 @@ class Handle:
         d = C.c_void_p()
         self._check(self.L.eagle_post_device_possession(table._t, C.byref(d)), "post_device_possession")
         return d.value
+
+    # --- pass options (include/eagle.h, eagle_pass_options_*) ---------------------------------------------------------------
+    def pass_options_layout(self, table):
+        """The table columns of the site columns (mapped Player pitch columns with a team >= 0), in table order: the second axis of the options."""
+        n = C.c_int(0)
+        self._check(self.L.eagle_pass_options_layout(table._t, None, 0, C.byref(n)), "pass_options_layout")
+        cols = np.zeros(n.value, np.int32)
+        self._check(self.L.eagle_pass_options_layout(table._t, _ptr(cols, np.zeros(4, np.float64)), n.value, C.byref(n)), "pass_options_layout")
+        return cols
+
+    def pass_options_device(self, table, params, d_rows, row0=0, n=None, d_grid=None, d_options=None):
+        """Rows row0 .. row0 + n - 1 -> n records at ``d_rows`` and, where given, n grids [n][gh][gw] at ``d_grid`` and options [n][n_sites] at
+        ``d_options`` (device memory)."""
+        n = len(table.rows) - row0 if n is None else n
+        self._check(self.L.eagle_pass_options_device(self._h, table._t, int(row0), int(n), C.byref(params), d_grid, d_rows, d_options), "pass_options_device")
+
+    def pass_options(self, table, params, row0=0, n=None, grids=True, options=True):
+        """Where the ball owner of each row can play, for a PostTable of this handle with velocities (Handle.velocities) and possession
+        (Handle.possession) -> (grids uint8 [n, gh, gw] or None, records PASS_ROW_DTYPE [n], options int16 [n, n_sites] or None).  Without grids the
+        grid kernel is not launched and the records' sums are 0."""
+        n = len(table.rows) - row0 if n is None else n
+        gw, gh = pass_options_size(params)
+        ns = len(self.pass_options_layout(table)) if options else 0
+        g = np.zeros((max(n, 0), gh, gw), np.uint8) if grids else None
+        recs = np.zeros(max(n, 0), PASS_ROW_DTYPE)
+        opt = np.zeros((max(n, 0), ns), np.int16) if options else None
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_pass_options(self._h, table._t, int(row0), int(n), C.byref(params), _ptr(g, keep), _ptr(recs, keep), _ptr(opt, keep)), "pass_options")
+        return g, recs, opt
 
     # --- physical report (include/eagle.h, eagle_post_physical) ------------------------------------------------------------
     def physical(self, table, params):
@@ -1444,6 +1495,21 @@ def possession_params(fps, radius=2.0, min_hold=2, max_gap=None):
     return EaglePossessionParams(int(fps), int(min_hold), int(fps if max_gap is None else max_gap), 0, float(radius), 0)
 
 
+def pass_option_params(cells_per_metre=1, samples=16, t_react=0.7, v_max=5.0, beta=4.0, v_ball=15.0):
+    """EaglePassOptionParams; 16 samples, 0.7 s, 5 m/s, 4 / s and a 15 m/s ball are conventional choices, not fitted to data."""
+    return EaglePassOptionParams(int(cells_per_metre), int(samples), float(t_react), float(v_max), float(beta), float(v_ball))
+
+
+def pass_options_size(params):
+    """(gw, gh) of the grids these parameters give (include/eagle.h eagle_pass_options_size; no GPU involved)."""
+    gw, gh = C.c_int(0), C.c_int(0)
+    L = load()
+    rc = L.eagle_pass_options_size(C.byref(params), C.byref(gw), C.byref(gh))
+    if rc:
+        raise EagleError(f"eagle_pass_options_size failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return gw.value, gh.value
+
+
 def load_params(fps, max_gap=None, zone_edges=(2.0, 4.0, 5.5, 7.0), effort_speed=(5.5, 7.0), accel=2.0, min_frames=None):
     """EagleLoadParams; max_gap None: fps frames; min_frames None: max(1, fps // 2) for both durations (one int: both).  The edges (m/s), the speeds a
     high-speed run and a sprint start at, 2 m/s^2 and half a second are conventional choices, not fitted to data."""
@@ -1546,6 +1612,39 @@ def op_possession(values, frames, columns, team_mapping, params, cap=None, devic
     if rc:
         raise EagleError(f"eagle_op_possession failed ({rc}): {L.eagle_last_error(None).decode()}")
     return cand, owner, dist, ev[: min(n.value, len(ev))].copy(), n.value
+
+
+def pass_site_columns(columns, team_mapping):
+    """The site columns of a table as include/eagle.h states them: Player pitch columns whose mapping entry is >= 0, in table order."""
+    if not (isinstance(columns, np.ndarray) and columns.dtype == POSTCOL_DTYPE):
+        columns = np.array([(k, i, v, 0) for k, i, v in columns], POSTCOL_DTYPE)
+    tm = {} if team_mapping is None else {int(k): int(v) for k, v in team_mapping.items()}
+    return np.array([c for c, col in enumerate(columns) if col["kind"] == POST_PLAYER and not col["video"] and tm.get(int(col["id"]), -1) >= 0], np.int32)
+
+
+def op_pass_options(values, velocities, columns, team_mapping, cand, owner, params, row0=0, n=None, grids=True, options=True, device=0):
+    """The pass-option launches on a constructed table (include/eagle.h eagle_op_pass_options): cand / owner int32 [rows] as op_possession gives them
+    -> (grids uint8 [n, gh, gw] or None, records PASS_ROW_DTYPE [n], options int16 [n, n_sites] or None)."""
+    L = load()
+    values, columns = _table_args("op_pass_options", values, columns)
+    velocities = np.ascontiguousarray(velocities, np.float64)
+    cand, owner = np.ascontiguousarray(cand, np.int32), np.ascontiguousarray(owner, np.int32)
+    cols, rows = values.shape[:2]
+    if velocities.shape != values.shape or cand.shape != (rows,) or owner.shape != (rows,):
+        raise EagleError("op_pass_options: velocities must have the shape of values, cand and owner one entry per row")
+    ids, vals, nt = _team_arrays(team_mapping)
+    n = rows - row0 if n is None else n
+    gw, gh = pass_options_size(params)
+    ns = len(pass_site_columns(columns, team_mapping)) if options else 0
+    g = np.zeros((max(n, 0), gh, gw), np.uint8) if grids else None
+    recs = np.zeros(max(n, 0), PASS_ROW_DTYPE)
+    opt = np.zeros((max(n, 0), ns), np.int16) if options else None
+    keep = np.zeros(8, np.float64)
+    rc = L.eagle_op_pass_options(device, _ptr(values, keep), _ptr(velocities, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt,
+                                 _ptr(cand, keep), _ptr(owner, keep), C.byref(params), int(row0), int(n), _ptr(g, keep), _ptr(recs, keep), _ptr(opt, keep))
+    if rc:
+        raise EagleError(f"eagle_op_pass_options failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return g, recs, opt
 
 
 def op_physical(velocities, frames, columns, params, cap=None, device=0):

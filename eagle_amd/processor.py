@@ -101,6 +101,12 @@ class Processor:
         from . import physical as ph
         return ph.physical(self.model.handle, table, fps, max_gap, zone_edges, effort_speed, accel, min_frames)
 
+    def pass_options(self, table, cells_per_metre=1, samples=16, t_react=0.7, v_max=5.0, beta=4.0, v_ball=15.0, rows=None, grids=True):
+        """Where the owner of the ball could play in each kept frame of a processed table with velocities (kinematics above) and possession: a grid per
+        row, a figure per teammate, the best of them, and how every pass that was played compares: see eagle_amd/options.py."""
+        from . import options as op
+        return op.pass_options(self.model.handle, table, cells_per_metre, samples, t_react, v_max, beta, v_ball, rows, grids)
+
     def shape(self, table):
         """Each team as a body in every kept frame of a processed table (centroid, length, width, hull area, stretch, lines, hull) and what that adds up
         to over the clip: see eagle_amd/shape.py."""

@@ -635,6 +635,69 @@ int eagle_op_physical(int device, const double* velocities, const int32_t* frame
                       double* speed, double* accel, uint8_t* zone, EagleLoadTotals* totals, int totals_cap, int* n_persons, EagleLoadEffort* efforts,
                       int efforts_cap, int* n_efforts);
 
+/* ---- pass options: where the ball owner can play, per row (own specification: tests/options_ref.py defines every output bit) ----------------------------
+ * float32 without contraction, correctly rounded sqrtf and division, the library's own expf (csrc/dmath.h).  Cell centres, the reaction point
+ * q = p + v t_react with its clamp to +-2^20, the fp32 rounding of positions and velocities and the non-finite-velocity rule are the control grid's.
+ * SITE COLUMNS  the Player pitch columns (video == 0) whose FIRST mapping entry with the column's id is >= 0 (a negative entry is "unknown": no site;
+ *               goalkeepers are never sites); their group is 0 for team value 0, else 1.  n_sites counts them, in table order (eagle_pass_options_layout).
+ *               A column's site of a row: its cell when it is present with |x|, |y| <= 1024.  The ball is the one Ball pitch column.
+ * ROW STATUS    the first that applies: EAGLE_PASS_NO_OWNER owner[r] < 0; _IN_FLIGHT cand[r] != owner[r] (the owner of record is not at the ball);
+ *               _NO_TEAM the owner's column is not a site column; _OFF_DOMAIN the ball cell is not within |x|, |y| <= 1024 (absent, or no ball column);
+ *               _ACTIVE otherwise.  A row that is not active has a grid of zeros, options all -1, best_col = best_byte = -1 and zero counts.
+ * ACTIVE ROW    b = the ball cell in fp32; attackers = the sites of the owner's group except the owner's own column, defenders = the sites of the other
+ *               group.  For a target c: dx = cx - bx, dy = cy - by, L = sqrtf(dx dx + dy dy); for k = 1 .. K (K = samples) f_k = (float)k / (float)K, the
+ *               sample s_k = (bx + dx f_k, by + dy f_k), the ball time T_k = (L f_k) / v_ball; t_D(s) = t_react + sqrtf(min over defenders of ex ex + ey ey)
+ *               / v_max with ex = sx - qx, ey = sy - qy, t_A(s) the same over attackers, every min from FLT_MAX.  Lane safety: m = min over k < K of
+ *               t_D(s_k) - T_k, safety = 1 / (1 + expf(-(beta m))), 1 when K == 1.  Reception at s_K as computed: reach = 1 / (1 + expf(-(beta (t_D(s_K) -
+ *               t_A(s_K))))).  Without defenders safety = reach = 1.  byte = (int)floorf(safety reach 255 + 0.5); 0 without attackers.
+ * OUTPUTS       grid u8 [gh][gw] (gw = 105 R, gh = 68 R, grid row 0 at pitch y = 0): the byte at every cell centre.  options int16 [n_sites]: for a present
+ *               attacker the byte at its own reaction point q_i, everything else -1.  The row record: best_col / best_byte = the largest option (a tie:
+ *               the earlier column), sum = the exact sum of the row's grid bytes (0 when no grid was asked for), group = the owner's group when its
+ *               column is a site column (whatever the status), else -1.
+ * Four launches (options.hip) on the handle's main stream: sites, grid (only with a grid), options, best.  The constants (16 samples, 0.7 s, 5 m/s, 4 / s,
+ * a 15 m/s ball) are conventional choices, not fitted to data.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers, cells_per_metre outside {1, 2, 4}, samples outside 1 .. 64, t_react, v_max, beta
+ * outside control's ranges, v_ball outside 0.001 .. 1e6, a table without a team mapping, without velocities, without a possession result (handle
+ * entries), the table of another handle, a row window outside the table, more than EAGLE_PASS_MAX_SITES site columns, more than one Ball pitch column,
+ * a column of unknown kind, cand / owner entries that are neither -1 nor a column index (operator entry), a device-memory need beyond the table's
+ * budget.  n == 0 is success and writes nothing. */
+#define EAGLE_PASS_ACTIVE 0
+#define EAGLE_PASS_NO_OWNER 1
+#define EAGLE_PASS_IN_FLIGHT 2
+#define EAGLE_PASS_NO_TEAM 3
+#define EAGLE_PASS_OFF_DOMAIN 4
+#define EAGLE_PASS_MAX_SITES 1024  /* a row's two lists then fit in LDS together (8 bytes per entry) */
+typedef struct EaglePassOptionParams {
+    int32_t cells_per_metre;       /* 1, 2 or 4 */
+    int32_t samples;               /* K: 1 .. 64 lane samples (a usual choice: 16) */
+    float t_react, v_max, beta;    /* seconds, m/s, 1/s: control's ranges */
+    float v_ball;                  /* m/s: 0.001 .. 1e6 (a usual choice: 15) */
+    int32_t reserved[2];
+} EaglePassOptionParams;           /* 32 bytes */
+typedef struct EaglePassOptionRow {
+    int32_t status;                /* EAGLE_PASS_* */
+    int32_t owner_col;             /* owner[r] */
+    int32_t group;                 /* the owner's group, -1 when its column is not a site column */
+    int32_t n_mates, n_defenders;  /* attackers and defenders present on the row (0 unless active) */
+    int32_t best_col, best_byte;   /* the largest option and its table column; -1 without an option */
+    int32_t reserved;
+    int64_t sum;                   /* the sum of the row's grid bytes */
+} EaglePassOptionRow;              /* 40 bytes */
+int eagle_pass_options_size(const EaglePassOptionParams* p, int* gw, int* gh);                               /* = eagle_control_size's */
+/* *n_sites = the number of site columns of the table; at most cap of their table columns are written, in table order. */
+int eagle_pass_options_layout(const EaglePostTable* t, int32_t* site_cols, int cap, int* n_sites);
+/* rows row0 .. row0 + n - 1 of a table with velocities and possession -> grids [n][gh][gw], records [n], options [n][n_sites] in HBM; d_grid may be
+ * NULL (the grid kernel is then not launched, sum = 0) and d_options too; returns when they are complete */
+int eagle_pass_options_device(EagleHandle* h, EaglePostTable* t, int row0, int n, const EaglePassOptionParams* p, uint8_t* d_grid, EaglePassOptionRow* d_rows,
+                              int16_t* d_options);
+/* Same, to host memory, in passes of what 32 MB of device staging hold. */
+int eagle_pass_options(EagleHandle* h, EaglePostTable* t, int row0, int n, const EaglePassOptionParams* p, uint8_t* grid, EaglePassOptionRow* rows_out, int16_t* options);
+/* Operator entry (host buffers in / out, no handle) for constructed tables; cand and owner [rows] as eagle_op_possession gives them; options
+ * [n][n_sites] with n_sites as the columns and the mapping give it; grid and options may be NULL. */
+int eagle_op_pass_options(int device, const double* values, const double* velocities, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                          const int32_t* team_vals, int n_team, const int32_t* cand, const int32_t* owner, const EaglePassOptionParams* p, int row0, int n,
+                          uint8_t* grid, EaglePassOptionRow* rows_out, int16_t* options);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
