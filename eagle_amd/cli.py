@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -148,7 +148,27 @@ def main(argv=None):
     ap.add_argument("--pass-options-pictures", action="store_true",
                     help="with --pass-options: also write <out>/pass_options_<k>.ppm, the option surface at the release row of pass event k in the owner's team "
                          "colour, at --minimap-scale pixels per metre")
+    ap.add_argument("--roles", action="store_true",
+                    help="with --processed: also write <out>/roles.json, each team's mean formation from an exact per-frame assignment of its players to roles: the "
+                         "role positions, lines and label (4-4-2), the rows per id and role, every change of role and the stints per role (10 roles, 8 present, 8 "
+                         "rounds and 3 lines are conventional choices, not fitted to data)")
+    ap.add_argument("--roles-count", type=int, default=None, metavar="R", help="with --roles: the number of roles per team, 2 .. 10 (default 10)")
+    ap.add_argument("--roles-min-present", type=int, default=None, metavar="M",
+                    help="with --roles: the fewest players of a team a frame must show to be assigned, 2 .. R (default 8, or R below that)")
+    ap.add_argument("--roles-iterations", type=int, default=None, metavar="T", help="with --roles: the rounds of assignment and re-estimation, 1 .. 32 (default 8)")
+    ap.add_argument("--roles-lines", type=int, default=None, metavar="L", help="with --roles: the lines a team is split into, 2 .. 4 (default 3)")
+    ap.add_argument("--roles-rows", action="store_true", help="with --roles: also write the id playing each role per kept frame and team into roles.json")
     a = ap.parse_args(argv)
+    if a.roles and not a.processed:
+        ap.error("--roles works on the processed table: it needs --processed")
+    if not a.roles and (a.roles_rows or any(v is not None for v in (a.roles_count, a.roles_min_present, a.roles_iterations, a.roles_lines))):
+        ap.error("--roles-count, --roles-min-present, --roles-iterations, --roles-lines and --roles-rows set up the roles: they need --roles")
+    if a.roles:
+        R = 10 if a.roles_count is None else a.roles_count
+        a.roles_set = (R, min(8, R) if a.roles_min_present is None else a.roles_min_present, 8 if a.roles_iterations is None else a.roles_iterations,
+                       3 if a.roles_lines is None else a.roles_lines)
+        if not (2 <= R <= 10 and 2 <= a.roles_set[1] <= R and 1 <= a.roles_set[2] <= 32 and 2 <= a.roles_set[3] <= min(4, R)):
+            ap.error("--roles: R within 2 .. 10, M within 2 .. R, T within 1 .. 32 and L within 2 .. min(4, R)")
     if a.pass_options and not a.processed:
         ap.error("--pass-options works on the processed table: it needs --processed")
     if (a.pass_options_grid is not None or a.pass_options_pictures) and not a.pass_options:
@@ -294,6 +314,10 @@ def main(argv=None):
                 json.dump(sh.to_json(sh.shape(model.handle, table)), f)
         elif a.minimap_hulls is not None:
             model.handle.team_shape(table)
+        if a.roles:
+            from . import roles as ro
+            with open(os.path.join(a.out, "roles.json"), "w") as f:
+                json.dump(ro.to_json(ro.roles(model.handle, table, *a.roles_set, per_row=a.roles_rows)), f)
         if (a.minimap_passes or a.pass_pictures or a.pass_options) and not a.possession:
             model.handle.possession(table, lib.possession_params(a.fps))
         if a.pass_options:

@@ -304,6 +304,9 @@ struct EaglePostTable {
     bool has_phys = false;
     std::vector<EagleLoadTotals> phys_totals;
     std::vector<EagleLoadEffort> phys_efforts;
+    void* d_roles = nullptr;             // roles (eagle_post_roles): EagleRoleRow [rows][2] | EagleRoleModel | role i8 [roles_members][rows], each from a 256-byte
+    int roles_members = 0;               // boundary; resident until eagle_post_free
+    bool has_roles = false;
 };
 
 namespace eagle {

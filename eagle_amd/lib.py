@@ -94,6 +94,22 @@ SHAPE_DTYPE = np.dtype([("sum_x", "<i8"), ("sum_y", "<i8"), ("sum_xx", "<i8"), (
                         ("col_min_x", "<i4"), ("col_max_x", "<i4"), ("col_min_y", "<i4"), ("col_max_y", "<i4"), ("reserved", "<i4", 2)])      # EagleTeamShape (96 bytes)
 
 
+class EagleRoleParams(C.Structure):
+    """include/eagle.h EagleRoleParams: the number of roles R (2 .. ROLE_CAP), the fewest present members of a row that is assigned (2 .. R), the rounds."""
+    _fields_ = [("roles", C.c_int32), ("min_present", C.c_int32), ("iterations", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+ROLE_CAP = 10                                                                # include/eagle.h EAGLE_ROLE_*
+ROLE_EMPTY, ROLE_TOO_FEW, ROLE_ACTIVE, ROLE_TOO_MANY = 0, 1, 2, 3
+ROLE_STATUS_NAMES = ("empty", "too_few", "active", "too_many")
+ROLE_MODEL_OK, ROLE_NO_SEEDS = 0, 1
+ROLE_ROW_DTYPE = np.dtype([("cost", "<i8"), ("n", "<i4"), ("status", "<i4"), ("cx", "<i4"), ("cy", "<i4"), ("col", "<i4", ROLE_CAP)])            # EagleRoleRow (64 bytes)
+ROLE_GROUP_DTYPE = np.dtype([("sum", "<i8", (ROLE_CAP, 2)), ("sum2", "<i8", (ROLE_CAP, 2)), ("mean", "<i4", (ROLE_CAP, 2)), ("count", "<i4", ROLE_CAP),
+                             ("status", "<i4"), ("active_rows", "<i4")])                                                                          # EagleRoleGroup (448 bytes)
+ROLE_MODEL_DTYPE = np.dtype([("group", ROLE_GROUP_DTYPE, 2), ("changed", "<i4", 32)])                                                             # EagleRoleModel (1024 bytes)
+assert C.sizeof(EagleRoleParams) == 32 and (ROLE_ROW_DTYPE.itemsize, ROLE_GROUP_DTYPE.itemsize, ROLE_MODEL_DTYPE.itemsize) == (64, 448, 1024)     # roles.hip asserts them too
+
+
 class EagleKinematicsParams(C.Structure):
     """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
@@ -323,6 +339,11 @@ def load():
     L.eagle_minimap_set_hulls.argtypes = [vp, hp]
     L.eagle_op_team_shape.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, vp, vp]
     L.eagle_op_minimap_hulls.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, mp, hp, tp, vp, i32, vp, vp, i32, i32, i32, i32, yl, vp]
+    rp = C.POINTER(EagleRoleParams)
+    L.eagle_post_roles.argtypes = [vp, vp, rp]
+    L.eagle_post_roles_values.argtypes = [vp, vp, vp, vp]
+    L.eagle_post_device_roles.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+    L.eagle_op_roles.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, rp, vp, vp, vp]
     lp = C.POINTER(EagleLoadParams)
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
@@ -363,7 +384,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_occupancy_picture", "eagle_op_occupancy", "eagle_op_occupancy_picture", "eagle_minimap_set_trails", "eagle_trajectory_picture",
            "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_post_team_shape", "eagle_post_team_shape_values",
            "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
-           "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
+           "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -878,6 +900,26 @@ class Handle:
         a, b = C.c_void_p(), C.c_void_p()
         self._check(self.L.eagle_post_device_team_shape(table._t, C.byref(a), C.byref(b)), "post_device_team_shape")
         return a.value, b.value
+
+    # --- roles (include/eagle.h, eagle_post_roles) -------------------------------------------------------------------------------
+    def roles(self, table, params=None):
+        """The role assignment of a PostTable of this handle (it needs a team mapping), computed on the GPU and kept with the table (a second call
+        replaces the first; a refused one leaves it) -> (ROLE_ROW_DTYPE [rows, 2], int8 [members, rows], ROLE_MODEL_DTYPE [1]); params role_params(...).
+        The members are the table's member columns in group order (eagle_amd.shape.member_columns).  eagle_amd.roles derives lines and labels."""
+        p = role_params() if params is None else params
+        self._check(self.L.eagle_post_roles(self._h, table._t, C.byref(p)), "post_roles")
+        nm = self.roles_device(table)[3]
+        rows = len(table.rows)
+        rec, mr, model = np.zeros((rows, 2), ROLE_ROW_DTYPE), np.full((nm, rows), -1, np.int8), np.zeros(1, ROLE_MODEL_DTYPE)
+        keep = np.zeros(4, np.float64)
+        self._check(self.L.eagle_post_roles_values(table._t, _ptr(rec, keep), _ptr(mr, keep), _ptr(model, keep)), "post_roles_values")
+        return rec, mr, model
+
+    def roles_device(self, table):
+        """(records, member roles, model, members) in HBM ((None, None, None, 0) before the first roles call of the table)."""
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        self._check(self.L.eagle_post_device_roles(table._t, C.byref(a), C.byref(b), C.byref(c), C.byref(n)), "post_device_roles")
+        return a.value, b.value, c.value, n.value
 
     def set_hulls(self, table, half_width=1):
         """The half width (pixels, 1 .. 8; or an EagleHullParams) the minimap's hull layer (MM_HULLS) of this table is drawn with; None: forget it."""
@@ -1930,6 +1972,33 @@ def op_team_shape(values, columns, team_mapping, device=0):
     if rc:
         raise EagleError(f"eagle_op_team_shape failed ({rc}): {L.eagle_last_error(None).decode()}")
     return rec, hull
+
+
+def role_params(roles=10, min_present=8, iterations=8):
+    """EagleRoleParams.  Ten outfield roles, a view that shows eight of them and eight rounds are conventional choices, not fitted to data."""
+    return EagleRoleParams(int(roles), int(min_present), int(iterations))
+
+
+def op_roles(values, columns, team_mapping, params=None, device=0):
+    """The role launches on a constructed table (include/eagle.h eagle_op_roles): values float64 [cols][rows][2], columns [(kind, id, video)]
+    -> (ROLE_ROW_DTYPE [rows, 2], int8 [members, rows], ROLE_MODEL_DTYPE [1])."""
+    L = load()
+    values, columns = _table_args("op_roles", values, columns)
+    cols, rows = values.shape[:2]
+    ids, vals, nt = _team_arrays(team_mapping)
+    first = {}
+    for i, v in zip(() if ids is None else ids.tolist(), () if vals is None else vals.tolist()):
+        first.setdefault(i, v)
+    nm = sum(1 for k in columns if not k["video"] and int(k["kind"]) == POST_PLAYER and first.get(int(k["id"]), -1) >= 0)
+    rec, mr, model = np.zeros((rows, 2), ROLE_ROW_DTYPE), np.full((nm, rows), -1, np.int8), np.zeros(1, ROLE_MODEL_DTYPE)
+    rec["col"] = -1
+    p = role_params() if params is None else params
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_roles(device, _ptr(values, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(p), _ptr(rec, keep), _ptr(mr, keep),
+                          _ptr(model, keep))
+    if rc:
+        raise EagleError(f"eagle_op_roles failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return rec, mr, model
 
 
 def op_minimap_hulls(values, frames, columns, team_mapping, params, hull, trail=None, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None,

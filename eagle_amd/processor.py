@@ -112,3 +112,9 @@ class Processor:
         to over the clip: see eagle_amd/shape.py."""
         from . import shape as sh
         return sh.shape(self.model.handle, table)
+
+    def roles(self, table, roles=10, min_present=8, iterations=8, lines=3, per_row=False):
+        """What the players of a processed table DO, whatever ids the tracker gave them: each team's mean formation from an exact per-frame assignment of
+        its players to roles, its lines and label (4-4-2), the rows per id and role, every change of role and the stints per role: see eagle_amd/roles.py."""
+        from . import roles as ro
+        return ro.roles(self.model.handle, table, roles, min_present, iterations, lines, per_row)

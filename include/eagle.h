@@ -698,6 +698,72 @@ int eagle_op_pass_options(int device, const double* values, const double* veloci
                           const int32_t* team_vals, int n_team, const int32_t* cand, const int32_t* owner, const EaglePassOptionParams* p, int row0, int n,
                           uint8_t* grid, EaglePassOptionRow* rows_out, int16_t* options);
 
+/* ---- player roles: per row the exact least-cost assignment of a team's present players to R role positions, re-estimated from the assignment (own
+ * specification: tests/roles_ref.py defines every output bit) ----
+ * MEMBERS, GROUPS, PRESENT and the quantisation q are the team shape's (above).  A role is not a tracker id: a fragment that ends and the one that
+ * replaces it land in the same role, and two players who exchange places leave the roles where they are.
+ *   ROW      n = present members; status EMPTY (n == 0), TOO_FEW (n < min_present), TOO_MANY (n > roles), else ACTIVE.  Centre cx = floor((2 sum qx + n) /
+ *            (2 n)) (0 when n == 0), cy likewise; a present member's centred position is u = q - c, |u| <= 2^21.  The players of a row are its present
+ *            members in table-column order.
+ *   SEEDS    per member column cnt = the ACTIVE rows on which it is present and S = the sums of u over them; the columns of a group ranked by (cnt
+ *            descending, column ascending), the first `roles` with cnt > 0 seed roles 0, 1, ... at floor((2 S + cnt) / (2 cnt)) per axis.  Fewer such
+ *            columns: the group's model status is NO_SEEDS, its rows report role -1 and cost 0, the group has no means, counts or sums.
+ *   ROUND    for every ACTIVE row of a seeded group c[i][j] = |u_i - M_j|^2 (int64; a row's total < 2^49); sigma = the injective map players -> roles of
+ *            least total cost and, among those, the lexicographically smallest sequence (sigma(0), sigma(1), ...).  Then M_j = floor((2 S_j + cnt_j) /
+ *            (2 cnt_j)) over the (row, player) pairs given role j; a role nobody played keeps its position.  changed[k] = the (row, group) pairs whose
+ *            sigma differs from round k-1's, over both groups (round 0: all of them).
+ *   RESULT   after `iterations` rounds: the assignment of the last round, its costs, and the positions it was computed AGAINST (mean); count, sum, sum2:
+ *            cnt_j and the sums of u and u^2 per axis over that assignment.  Entries at and beyond `roles` are 0.  Once changed[k] == 0 no later round
+ *            changes anything; the launches stop there and the entries of changed behind k are 0.
+ * The defaults (10 roles, 8 present, 8 rounds) are conventional choices, not fitted to data.
+ * Launches (roles.hip) on the handle's main stream read the table where eagle_postprocess left it; what the call allocates is held against the table's
+ * max_bytes before the first launch.  The handle's records, staging buffers and graphs are not involved.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output alone: NULL table or parameters, a table without a mapping, parameters
+ * outside their ranges or non-zero reserved words, more than EAGLE_SHAPE_MAX_MEMBERS members, a column of unknown kind.  A refused call leaves an
+ * earlier result of the table in place.  rows == 0 is success and writes nothing. */
+#define EAGLE_ROLE_CAP 10
+#define EAGLE_ROLE_EMPTY 0         /* EagleRoleRow::status */
+#define EAGLE_ROLE_TOO_FEW 1
+#define EAGLE_ROLE_ACTIVE 2
+#define EAGLE_ROLE_TOO_MANY 3
+#define EAGLE_ROLE_MODEL_OK 0      /* EagleRoleGroup::status */
+#define EAGLE_ROLE_NO_SEEDS 1
+typedef struct EagleRoleParams {
+    int32_t roles;                 /* R: 2 .. EAGLE_ROLE_CAP (10) */
+    int32_t min_present;           /* 2 .. roles (8) */
+    int32_t iterations;            /* T: 1 .. 32 (8) */
+    int32_t reserved[5];           /* 0 */
+} EagleRoleParams;                 /* 32 bytes */
+typedef struct EagleRoleRow {
+    int64_t cost;                  /* the assignment's total cost, q^2; 0 unless ACTIVE in a seeded group */
+    int32_t n;                     /* present members */
+    int32_t status;                /* EAGLE_ROLE_EMPTY .. EAGLE_ROLE_TOO_MANY */
+    int32_t cx, cy;                /* the centre, q */
+    int32_t col[EAGLE_ROLE_CAP];   /* the table column playing role j, or -1 */
+} EagleRoleRow;                    /* 64 bytes */
+typedef struct EagleRoleGroup {
+    int64_t sum[EAGLE_ROLE_CAP][2];        /* of u per role and axis over the final assignment */
+    int64_t sum2[EAGLE_ROLE_CAP][2];       /* ... of u^2 */
+    int32_t mean[EAGLE_ROLE_CAP][2];       /* the role positions the final assignment was computed against, q round the row's centre */
+    int32_t count[EAGLE_ROLE_CAP];         /* (row, player) pairs per role */
+    int32_t status;                        /* EAGLE_ROLE_MODEL_OK / EAGLE_ROLE_NO_SEEDS */
+    int32_t active_rows;
+} EagleRoleGroup;                  /* 448 bytes */
+typedef struct EagleRoleModel {
+    EagleRoleGroup group[2];
+    int32_t changed[32];
+} EagleRoleModel;                  /* 1024 bytes */
+/* The result is kept with the table until eagle_post_free and replaces an earlier one. */
+int eagle_post_roles(EagleHandle* h, EaglePostTable* t, const EagleRoleParams* p);
+/* To the host; any pointer may be NULL.  member_roles: int8 [members][rows], members in group order (group 0's columns, then group 1's): the member's role
+ * on the row, or -1 (absent, the row not ACTIVE, the group without seeds). */
+int eagle_post_roles_values(EaglePostTable* t, EagleRoleRow* rows_out /* [rows][2] */, int8_t* member_roles, EagleRoleModel* model);
+/* In HBM; all NULL (and 0 members) before eagle_post_roles.  n_members may be NULL. */
+int eagle_post_device_roles(const EaglePostTable* t, const EagleRoleRow** d_rows, const int8_t** d_member_roles, const EagleRoleModel** d_model, int* n_members);
+/* Operator entry (host buffers in / out, no handle) for constructed tables, as eagle_op_team_shape; each output may be NULL. */
+int eagle_op_roles(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
+                   const EagleRoleParams* p, EagleRoleRow* rows_out, int8_t* member_roles, EagleRoleModel* model);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
