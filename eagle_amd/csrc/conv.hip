@@ -34,7 +34,8 @@ static int f16_ni(int ks, int kc) { return (ks * ks * (kc / 8) + 3) / 4; }
 // parity tests' EAGLE_CONV_FORCE strings.  Generic and weight-stationary forms have one instance per (ks, stride, kc, nt) in conv_inst_*.hip; an A-direct
 // form is one kernel (per residual count and ring depth) for 3x3 layers of the row's stride, kc and nt.
 enum FormKind { GENERIC, WSTAT, ADIRECT };                  // implicit GEMM; weight-stationary persistent; A-direct (weights straight into MFMA registers)
-enum StrideForm { S1, S2D, S2T };                           // A-direct: stride 1; stride 2 over the space-to-depth image; TRUE stride 2 on a column-plane halo
+enum StrideForm { S1, S2D, S2T, S1L };                      // A-direct: stride 1; stride 2 over the space-to-depth image; TRUE stride 2 on a column-plane halo;
+                                                            // stride 1 tiled over the linear pixel sequence of a map exactly `cols` wide (rows + 2 = the halo's map rows)
 enum WeightImage { W_F32, W_F16, W_F16_S2D, W_SPLIT, W_SPLIT_AD, W_SPLIT_S2D, W_SPLIT_M32 };    // layout written by conv_tile_weights
 struct Form {
     int prec, variant, kind;
@@ -72,7 +73,10 @@ static constexpr Form g_forms[] = {
     ad(F32S, 14, S2T, 4, 32, 12, 1, W_SPLIT_AD, conv_ad_split_kernel_s2t_bn192), ad(F32S, 15, S2T, 4, 32, 6, 1, W_SPLIT_AD, conv_ad_split_kernel_s2t_bn96),
     // split family, A-direct on 32x32x16 MFMA (conv_ad_split32.inc): tiles 4 x 32 (21) / 8 x 32 (22); the wave's two pixel blocks side by side (23 / 24)
     ad(F32S, 21, S1, 4, 32, 12, 2, W_SPLIT_M32, conv_ad_split32_kernel_bn192), ad(F32S, 22, S1, 8, 32, 6, 2, W_SPLIT_M32, conv_ad_split32_kernel_bn96),
-    ad(F32S, 23, S1, 2, 64, 12, 2, W_SPLIT_M32, conv_ad_split32_kernel_w64_bn192), ad(F32S, 24, S1, 4, 64, 6, 2, W_SPLIT_M32, conv_ad_split32_kernel_w64_bn96)};
+    ad(F32S, 23, S1, 2, 64, 12, 2, W_SPLIT_M32, conv_ad_split32_kernel_w64_bn192), ad(F32S, 24, S1, 4, 64, 6, 2, W_SPLIT_M32, conv_ad_split32_kernel_w64_bn96),
+    // ... BN 192 with items of 128 consecutive pixels of the row-major sequence, for maps exactly 30 columns wide: halo of 8 map rows x 32 records (27)
+    ad(F32S, 27, S1L, 6, 30, 12, 2, W_SPLIT_M32, conv_ad_split32_kernel_lin30)};
+static constexpr int LIN_PIXELS = 128;                      // pixels per item of the S1L forms
 
 static const Form* find_form(int precision, int variant)
 {
@@ -126,6 +130,7 @@ int conv_tiles_per_frame(int precision, const ConvConfig& c, int ho, int wo)
 {
     int th, tw;
     conv_tile_shape(precision, c, &th, &tw);
+    if (form_of(precision, c).sform == S1L) return (ho * wo + LIN_PIXELS - 1) / LIN_PIXELS;
     return ((wo + tw - 1) / tw) * ((ho + th - 1) / th);
 }
 
@@ -144,7 +149,7 @@ static const Inst* generic_inst(int precision, const ConvConfig& c)
 bool conv_supported(int precision, const ConvConfig& c)
 {
     const Form* f = find_form(precision, c.variant);
-    if (f && f->kind == ADIRECT) return c.ks == 3 && c.stride == (f->sform == S1 ? 1 : 2) && c.kc == f->kc && c.nt == f->nt;
+    if (f && f->kind == ADIRECT) return c.ks == 3 && c.stride == (f->sform == S1 || f->sform == S1L ? 1 : 2) && c.kc == f->kc && c.nt == f->nt;
     return f && generic_inst(precision, c);
 }
 
@@ -203,7 +208,8 @@ static ConvConfig choose_split(ConvConfig c, int wo, bool plain_epilogue)
 {
     const int prec = EAGLE_PREC_F32S, cin = c.cin, cout = c.cout_pad;
     ConvConfig q = c;
-    if (env_force("EAGLE_CONV_FORCE", &q.kc, &q.nt, &q.variant) && cin % q.kc == 0 && cout % (16 * q.nt) == 0 && conv_supported(prec, q)) {
+    if (env_force("EAGLE_CONV_FORCE", &q.kc, &q.nt, &q.variant) && cin % q.kc == 0 && cout % (16 * q.nt) == 0 && conv_supported(prec, q) &&
+        (form_of(prec, q).sform != S1L || (plain_epilogue && wo == form_of(prec, q).cols))) {      // a linear form is compiled for one map width
         if (form_of(prec, q).pw == 6) q.wx = 3;              // six sub-tiles per wave: the 8 x 48 tile
         if (lds_bytes(prec, q) <= 160 * 1024) return q;
     }
@@ -214,7 +220,17 @@ static ConvConfig choose_split(ConvConfig c, int wo, bool plain_epilogue)
     // 3x3 stride 1 with Cout = 96 k, any Cin = 16 k: the 32x32x16 A-direct forms (round 5), 4 x 32 tiles for BN = 192 (2 x 64 measured 1.5 % slower on 34 x 60),
     // 4 x 64 tiles for BN = 96 on maps wider than 32 columns, else 8 x 32 — same box, three alternating pairs through the whole pipeline against the 16x16x32
     // forms: 750.0 / 751.0 / 753.4 -> 761.3 / 761.5 / 761.8 frames/s (+1.4 %), 96->96 @68x120 208.5 -> 193.5 us.
-    if (!env_off("EAGLE_CONV_M32") && plain_epilogue && c.ks == 3 && c.stride == 1 && cin % 16 == 0 && cout % 96 == 0) return with_ad(c, 16, 21, wo > 32 ? 24 : 22);
+    // BN = 192 on maps exactly 30 columns wide (HRNet's 17 x 30 branch): items of 128 consecutive pixels of the row-major sequence (variant 27) instead of
+    // 4 x 32 rectangles, 16 instead of 20 32-pixel blocks per frame at the same halo traffic — same box, four alternating runs through the whole pipeline:
+    // 828.7 ... 834.3 -> 839.4 ... 845.2 frames/s (+1.2 %), 384->384 @17x30 222 -> 177 us isolated (docs/experiments.md 10.11).  The same form at 60 columns
+    // (34 x 60: 72 -> 64 blocks, but a halo of 372 records per item instead of 204) ran 5 % SLOWER per launch and gave a mixed +0.5 % in the pipeline: measured
+    // and taken out again, 34 x 60 stays on variant 21.  The 96-channel class stays on the 4 x 64 tile: a full-width halo for its 256 pixels at W = 120
+    // (120 KB) leaves one workgroup per CU, and its padding is 6.7 % only.
+    if (!env_off("EAGLE_CONV_M32") && plain_epilogue && c.ks == 3 && c.stride == 1 && cin % 16 == 0 && cout % 96 == 0) {
+        q = with_ad(c, 16, 21, wo > 32 ? 24 : 22);
+        if (q.variant == 21 && wo == 30) q.variant = 27;
+        return q;
+    }
     for (const Tuned& t : g_tuned_split)
         if (tuned_match(t, c, wo, &q)) {
             const Form* f = find_form(prec, q.variant);      // the A-direct kernels: ReLU / none after at most two residual adds, three chunks per loop body
@@ -488,6 +504,10 @@ void conv_launch(int precision, const ConvLaunch& L, hipStream_t s)
             fail(EAGLE_E_NOKERNEL, "A-direct conv needs 2-byte / split output, pre_act none, post_act in {none, ReLU} and, in the split family, Cin = 16 k (48 k for variants 8, 9 and 12 - 15)");
         if (f.sform == S2D) a.nchunks = 4 * c.cin / c.kc;  // chunks of the space-to-depth image
         a.tiles_x = (a.Wo + f.cols - 1) / f.cols; a.tiles_y = (a.Ho + f.rows - 1) / f.rows;
+        if (f.sform == S1L) {                               // items of LIN_PIXELS consecutive pixels: tiles_x = items per frame
+            if (a.Wo != f.cols || a.W != a.Wo || a.H != a.Ho) fail(EAGLE_E_NOKERNEL, "linear A-direct conv (variant %d) needs a map %d columns wide, got %d x %d", c.variant, f.cols, a.Ho, a.Wo);
+            a.tiles_x = (a.Ho * a.Wo + LIN_PIXELS - 1) / LIN_PIXELS; a.tiles_y = 1;
+        }
         a.gy = c.cout_pad / (c.nt * 16);
         const size_t lim = (size_t)1 << 31;
         if ((size_t)a.N * a.H * a.W * a.xcs * 2 >= lim || (size_t)a.N * a.Ho * a.Wo * std::max(std::max(a.ycs, a.r1 ? a.r1cs : 0), a.r2 ? a.r2cs : 0) * 2 >= lim)

@@ -49,4 +49,13 @@ ConvKernel conv_ad_split32_kernel_w64_bn96(int n_res, bool deep)
     return fn[deep ? 1 : 0][res_slot(n_res)];
 }
 
+// linear tiling of the 30-column maps: BN 192, items of 128 consecutive pixels (variant 27)
+ConvKernel conv_ad_split32_kernel_lin30(int n_res, bool deep)
+{
+    static const ConvKernel fn[2][3] = {
+        {conv_split_ad32_kernel<2, 2, 0, 3, 1, 30>, conv_split_ad32_kernel<2, 2, 1, 3, 1, 30>, conv_split_ad32_kernel<2, 2, 2, 3, 1, 30>},
+        {conv_split_ad32_kernel<2, 2, 0, 6, 1, 30>, conv_split_ad32_kernel<2, 2, 1, 6, 1, 30>, conv_split_ad32_kernel<2, 2, 2, 6, 1, 30>}};
+    return fn[deep ? 1 : 0][res_slot(n_res)];
+}
+
 }  // namespace eagle

@@ -49,6 +49,18 @@
 // 36 and 72 rows, the column remainder (60 -> 64, 120 -> 128) is the same: 6.7 % of the MFMAs on padding instead of 12.9 %.  Halo (PG + 2) rows x 66 records.
 // The epilogue strips are 128-byte records with the 16-byte unit XOR-swizzled by the pixel (unit ^ (pixel & 7)): no padding (the 4 x 64 tile of variant 24 then
 // fits two workgroups per CU to the byte: 2 x 32 KB halo ring + 4 x 4 KB strips = 80 KB), 2-way conflicts at most on the 8-byte strip writes, none on the 16-byte reads.
+// MAPW = 30 (variant 27; BN = 192 only): LINEAR tiling.  An item owns the 128 consecutive pixels L0 = 128 t .. L0 + 127 of the frame's row-major sequence
+// L = y W + x instead of a rectangle: wave pg the 32-pixel blocks 2 pg and 2 pg + 1, lane lx of block b pixel L0 + 32 b + lx.  17 x 30 = 510 pixels are 4 items
+// per frame where 4 x 32 tiles need 5 (25.5 % of their MFMAs on padding).  The halo holds WHOLE map rows of MAPW + 2 records (x = -1 .. W): rows y_first - 1 ..
+// y_first + LROWS, y_first = L0 / W, LROWS = 126 / W + 2 = 6 = the rows 128 consecutive pixels can touch -> 8 x 32 records = 20 slabs per slot, 56 KB of LDS with
+// the strips; 256 records x 400 items = the 204 x 500 of the 4 x 32 tiles: the halo traffic is unchanged.  Same slab decomposition and (iy, ix) bounds test; each
+// block has its own per-lane fragment base ((y - y_first) * HW_ + x) * PS, computed once per item, the tap offsets stay immediates.  Lanes past the frame's last
+// pixel read that pixel and store out of range.  The epilogue's pixel index is n H W + L.  Same chunk, tap and product order into the same accumulators as
+// variant 21: bit-identical results.  384->384 @17x30, B = 50: 222 -> 177 us isolated, +1.2 % frames/s in the pipeline (docs/experiments.md 10.11).
+// (MAPW = 60 for the 34 x 60 maps — 16 items per frame instead of 18, halo 6 x 62 records = 32 slabs, 80 KB — was built with it, bit-identical too, and taken
+//  out again: 372 x 800 halo records per launch against 204 x 900 cost more than 11 % fewer MFMAs gave, 180 -> 188 us isolated, a mixed +0.5 % in the pipeline.)
+// The 96-channel class stays on variant 24: a full-width halo at W = 120 (its 256 pixels: 6 x 122 records x 2 slots = 120 KB) leaves one workgroup per CU, and
+// its padding is 6.7 % only.
 // Weight image (conv_tile_weights): [Cout block][chunk][tap 0..8][hi | lo][BN / 32 blocks][lane 0..63][8].
 // ------------------------------------------------------------------------------------------------------------
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -72,10 +84,12 @@ __device__ __forceinline__ void split_store4x(char* dhi, char* dlo, float v0, fl
     const half4 lo = {(_Float16)(s0 - (float)hi[0]), (_Float16)(s1 - (float)hi[1]), (_Float16)(s2 - (float)hi[2]), (_Float16)(s3 - (float)hi[3])};
     *(half4*)dhi = hi; *(half4*)dlo = lo;
 }
-template <int CQ, int PG, int RES, int RING = 3, int NRH = 1>
+template <int CQ, int PG, int RES, int RING = 3, int NRH = 1, int MAPW = 0>
 __global__ __launch_bounds__(256, 2) void conv_split_ad32_kernel(ConvArgs a)
 {
     static_assert(CQ * PG == 4, "four waves per workgroup");
+    constexpr bool LIN = MAPW != 0;                       // the item owns 128 consecutive pixels of the frame's row-major sequence (map width MAPW, a.W == a.Wo == MAPW)
+    static_assert(!LIN || (CQ == 2 && PG == 2 && NRH == 1 && MAPW == 30), "linear tiling: the BN = 192 form on the 30-column map");
     static_assert(NRH == 1 || NRH == 2, "the wave's two pixel blocks: one above the other (1) or side by side (2)");
     static_assert(18 % RING == 0 && RING >= 3, "the weight ring holds a divisor of the 18 steps of a chunk");
     using rsrc_t = __amdgpu_buffer_rsrc_t;
@@ -84,7 +98,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_ad32_kernel(ConvArgs a)
     constexpr int KSTEP = (BN / 32) * 1024;              // bytes of one step of the weight image (one tap, hi or lo, the whole Cout block)
     // halo record: [hi g0][hi g1][lo g0][lo g1] + ONE pad slot = 80 bytes: 20 banks per pixel put the 16 pixels of a ds_read_b128 lane group on 16 distinct 4-bank columns
     constexpr int PS = 80, SPC = 18, AHEAD = RING - 1;
-    constexpr int HW_ = TW + 2, HPIX = (TH + 2) * HW_;
+    constexpr int LROWS = LIN ? (128 - 2) / (LIN ? MAPW : 1) + 2 : 0;      // map rows that 128 consecutive pixels touch at most: 6 at 30 columns
+    constexpr int HW_ = LIN ? MAPW + 2 : TW + 2, HPIX = (LIN ? LROWS + 2 : TH + 2) * HW_;      // linear: whole map rows y_first - 1 .. y_first + LROWS, columns -1 .. MAPW
     constexpr int HSLABS = ((HPIX * PS + 1023) / 1024 + NW - 1) / NW * NW, HB = HSLABS * 1024, HK = HSLABS / NW;
     constexpr int RS = 32 * 4, STRIP = 32 * RS;          // one pass: 32 pixels x 32 channels x 4 bytes, 16-byte units XOR-swizzled by the pixel
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -137,7 +152,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_ad32_kernel(ConvArgs a)
     int h_iy0, h_ix0, h_gb;                                // geometry of the item the next request belongs to (scalars)
     auto halo_origin = [&](int item) {
         int n, ty, tx, nb; decode(item, n, ty, tx, nb);
-        h_iy0 = ty * TH - 1; h_ix0 = tx * TW - 1;
+        if constexpr (LIN) { h_iy0 = (tx * 128) / MAPW - 1; h_ix0 = -1; }      // tx: the item's index in the frame (tiles_y = 1); the row of its first pixel
+        else { h_iy0 = ty * TH - 1; h_ix0 = tx * TW - 1; }
         h_gb = (((n * a.H + h_iy0) * a.W + h_ix0) * a.xcs + a.xoff) * 2;       // xcs / xoff: fp16 elements (two per logical channel)
     };
     halo_origin(h_item);
@@ -176,6 +192,18 @@ __global__ __launch_bounds__(256, 2) void conv_split_ad32_kernel(ConvArgs a)
     for (int item = item0; item < item_end; ++item) {
         int n, ty, tx, nb; decode(item, n, ty, tx, nb);
         const int oy0 = ty * TH, ox0 = tx * TW;
+        // linear tiling: lane lx of the wave's block p holds pixel L0 + 32 (2 pg + p) + lx of the frame; the lanes past the frame's last pixel read that pixel
+        // (their stores go out of range).  One B-fragment base per block: halo row y - y_first (+ ky), record x (+ kx).
+        const int L0 = tx * 128, npix = a.H * a.W;
+        int bbl[LIN ? NR : 1];
+        if constexpr (LIN) {
+            const int yf = L0 / MAPW;
+#pragma unroll
+            for (int p = 0; p < NR; ++p) {
+                const int L = min(L0 + (pg * NR + p) * 32 + lx, npix - 1), y = L / MAPW, x = L - y * MAPW;
+                bbl[p] = ((y - yf) * HW_ + x) * PS + kh * 16;
+            }
+        }
         f32x16 acc[MB][NR];
 #pragma unroll
         for (int i = 0; i < MB; ++i)
@@ -206,13 +234,23 @@ __global__ __launch_bounds__(256, 2) void conv_split_ad32_kernel(ConvArgs a)
             __builtin_amdgcn_s_barrier();
             issue_h();                                              // chunk gc + 1 into the slot chunk gc - 1 used
             const char* hb = Hb + (gc & 1) * HB + bbase;
+            const char* hbl[LIN ? NR : 1];
+            if constexpr (LIN) {
+#pragma unroll
+                for (int p = 0; p < NR; ++p) hbl[p] = Hb + (gc & 1) * HB + bbl[p];
+            }
             half8 Bh[2][NR], Bl[2][NR];
             auto read_b = [&](int slot, int tap) {
                 const int ky = tap / 3, kx = tap - ky * 3;
 #pragma unroll
                 for (int p = 0; p < NR; ++p) {      // block p: row p / NRH of the wave, 32-pixel column group p % NRH
-                    Bh[slot][p] = *(const half8*)(hb + ((p / NRH + ky) * HW_ + (p % NRH) * 32 + kx) * PS);
-                    Bl[slot][p] = *(const half8*)(hb + ((p / NRH + ky) * HW_ + (p % NRH) * 32 + kx) * PS + 32);
+                    if constexpr (LIN) {
+                        Bh[slot][p] = *(const half8*)(hbl[p] + (ky * HW_ + kx) * PS);
+                        Bl[slot][p] = *(const half8*)(hbl[p] + (ky * HW_ + kx) * PS + 32);
+                    } else {
+                        Bh[slot][p] = *(const half8*)(hb + ((p / NRH + ky) * HW_ + (p % NRH) * 32 + kx) * PS);
+                        Bl[slot][p] = *(const half8*)(hb + ((p / NRH + ky) * HW_ + (p % NRH) * 32 + kx) * PS + 32);
+                    }
                 }
             };
             read_b(0, 0);
@@ -253,6 +291,10 @@ __global__ __launch_bounds__(256, 2) void conv_split_ad32_kernel(ConvArgs a)
         }
         auto piece_off = [&](int pass, int i, int cs, int off) -> unsigned {      // pass = pixel block * MB + channel block; cs / off in fp16 elements
             const int row = pass / MB, mb = pass - row * MB;
+            if constexpr (LIN) {                            // NHWC pixel n H W + L; the tail of the frame's last block goes out of range
+                const int L = L0 + (pg * NR + row) * 32 + (ppx[i] & 0xFF), u = ppx[i] >> 8;
+                return L < npix ? (unsigned)(((n * npix + L) * cs + off + (co0 + mb * 32) * 2 + u * 8) * 2) : OOB;
+            }
             const int oy = oy0 + pg * NRV + row / NRH, ox2 = ox0 + (row % NRH) * 32 + (ppx[i] & 0xFF), u = ppx[i] >> 8;
             return (oy < a.Ho && ox2 < a.Wo) ? (unsigned)((((n * a.Ho + oy) * a.Wo + ox2) * cs + off + (co0 + mb * 32) * 2 + u * 8) * 2) : OOB;
         };

@@ -66,5 +66,6 @@ ConvKernel conv_ad_split32_kernel_bn192(int n_res, bool deep);         // the 32
 ConvKernel conv_ad_split32_kernel_bn96(int n_res, bool deep);
 ConvKernel conv_ad_split32_kernel_w64_bn192(int n_res, bool deep);     // ... with the wave's two pixel blocks side by side: tile 2 x 64 (variant 23) / 4 x 64 (variant 24)
 ConvKernel conv_ad_split32_kernel_w64_bn96(int n_res, bool deep);
+ConvKernel conv_ad_split32_kernel_lin30(int n_res, bool deep);         // ... BN 192 with items of 128 consecutive pixels of a 30-column map (variant 27)
 
 }  // namespace eagle
