@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -158,7 +158,24 @@ def main(argv=None):
     ap.add_argument("--roles-iterations", type=int, default=None, metavar="T", help="with --roles: the rounds of assignment and re-estimation, 1 .. 32 (default 8)")
     ap.add_argument("--roles-lines", type=int, default=None, metavar="L", help="with --roles: the lines a team is split into, 2 .. 4 (default 3)")
     ap.add_argument("--roles-rows", action="store_true", help="with --roles: also write the id playing each role per kept frame and team into roles.json")
+    ap.add_argument("--space", action="store_true",
+                    help="with --processed: also write <out>/space.json, the room every player has: the exact area of the pitch nearer to him than to anybody "
+                         "else, by thirds, his nearest opponent and the opponents within a radius, per id, per team and (with --possession) per owner and pass")
+    ap.add_argument("--space-grid", type=int, default=None, choices=[1, 2, 4], metavar="R", help="with --space: the cells per metre of the grid, 1, 2 or 4 (default 1)")
+    ap.add_argument("--space-radius", type=float, default=None, metavar="M",
+                    help="with --space: the marking radius in metres, > 0 and <= 1024 (default 3, a conventional choice, not fitted to data)")
+    ap.add_argument("--space-rows", action="store_true", help="with --space: also write the sites of every kept frame into space.json")
+    ap.add_argument("--space-map", action="store_true",
+                    help="with --space: also write <out>/space.npy (uint8 [rows, 68 R, 105 R]), per cell the index of its owner among the frame's sites, 255 on a skipped frame")
     a = ap.parse_args(argv)
+    if a.space and not a.processed:
+        ap.error("--space works on the processed table: it needs --processed")
+    if not a.space and (a.space_rows or a.space_map or a.space_grid is not None or a.space_radius is not None):
+        ap.error("--space-grid, --space-radius, --space-rows and --space-map set up the space report: they need --space")
+    if a.space:
+        a.space_set = (1 if a.space_grid is None else a.space_grid, 3.0 if a.space_radius is None else a.space_radius)
+        if not (a.space_set[1] == a.space_set[1] and 0.0 < a.space_set[1] <= 1024.0):
+            ap.error("--space-radius: M must be > 0 and <= 1024 metres")
     if a.roles and not a.processed:
         ap.error("--roles works on the processed table: it needs --processed")
     if not a.roles and (a.roles_rows or any(v is not None for v in (a.roles_count, a.roles_min_present, a.roles_iterations, a.roles_lines))):
@@ -331,6 +348,12 @@ def main(argv=None):
             if a.pass_options_pictures:
                 for k, img in op.pictures(model.handle, table, res, a.minimap_scale):
                     oc.write_ppm(os.path.join(a.out, "pass_options_%d.ppm" % k), img)
+        if a.space:
+            from . import space as spc
+            with open(os.path.join(a.out, "space.json"), "w") as f:
+                json.dump(spc.to_json(spc.space(model.handle, table, a.space_set[0], True, a.space_set[1], per_row=a.space_rows)), f)
+            if a.space_map:
+                np.save(os.path.join(a.out, "space.npy"), model.handle.space_grids(table, lib.space_params(a.space_set[0], 1, a.space_set[1])))
         entities = [c for c, k in enumerate(table.columns) if not k["video"] and int(k["kind"]) in (lib.POST_PLAYER, lib.POST_GOALKEEPER, lib.POST_BALL)]
         if a.trajectory is not None:
             from . import minimap as mm

@@ -307,6 +307,8 @@ struct EaglePostTable {
     void* d_roles = nullptr;             // roles (eagle_post_roles): EagleRoleRow [rows][2] | EagleRoleModel | role i8 [roles_members][rows], each from a 256-byte
     int roles_members = 0;               // boundary; resident until eagle_post_free
     bool has_roles = false;
+    void* d_space = nullptr;             // space (eagle_post_space): EagleSpaceRow [rows] | EagleSpaceSite [rows][32] | EagleSpaceTotals [space_members], each from a
+    int space_members = 0;               // 256-byte boundary; nullptr before the first call, resident until eagle_post_free
 };
 
 namespace eagle {

@@ -110,6 +110,22 @@ ROLE_MODEL_DTYPE = np.dtype([("group", ROLE_GROUP_DTYPE, 2), ("changed", "<i4", 
 assert C.sizeof(EagleRoleParams) == 32 and (ROLE_ROW_DTYPE.itemsize, ROLE_GROUP_DTYPE.itemsize, ROLE_MODEL_DTYPE.itemsize) == (64, 448, 1024)     # roles.hip asserts them too
 
 
+class EagleSpaceParams(C.Structure):
+    """include/eagle.h EagleSpaceParams: the grid's cells per metre (1, 2 or 4), whether the goalkeepers are sites (group 2), the marking radius in metres."""
+    _fields_ = [("cells_per_metre", C.c_int32), ("goalkeepers", C.c_int32), ("radius", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+SPACE_SITE_CAP = 32                                                          # include/eagle.h EAGLE_SPACE_*
+SPACE_EMPTY, SPACE_ACTIVE, SPACE_TOO_MANY, SPACE_NO_OWNER = 0, 1, 2, 255
+SPACE_STATUS_NAMES = ("empty", "active", "too_many")
+SPACE_ROW_DTYPE = np.dtype([("status", "<i4"), ("n_sites", "<i4"), ("n", "<i4", 3), ("cells", "<i4", (3, 3)), ("reserved", "<i4", 2)])              # EagleSpaceRow (64 bytes)
+SPACE_SITE_DTYPE = np.dtype([("near_d2", "<i8"), ("col", "<i4"), ("group", "<i4"), ("near_col", "<i4"), ("within", "<i4"), ("cells", "<i4", 3), ("qx", "<i4"),
+                             ("qy", "<i4"), ("reserved", "<i4")])                                                                                    # EagleSpaceSite (48 bytes)
+SPACE_TOTALS_DTYPE = np.dtype([("cells", "<i8", 3), ("within_sum", "<i8"), ("col", "<i4"), ("group", "<i4"), ("rows", "<i4"), ("min", "<i4"), ("max", "<i4"),
+                               ("opp_rows", "<i4"), ("within_rows", "<i4"), ("reserved", "<i4")])                                                    # EagleSpaceTotals (64 bytes)
+assert C.sizeof(EagleSpaceParams) == 32 and (SPACE_ROW_DTYPE.itemsize, SPACE_SITE_DTYPE.itemsize, SPACE_TOTALS_DTYPE.itemsize) == (64, 48, 64)       # space.hip asserts them too
+
+
 class EagleKinematicsParams(C.Structure):
     """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
@@ -344,6 +360,13 @@ def load():
     L.eagle_post_roles_values.argtypes = [vp, vp, vp, vp]
     L.eagle_post_device_roles.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
     L.eagle_op_roles.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, rp, vp, vp, vp]
+    sp = C.POINTER(EagleSpaceParams)
+    L.eagle_post_space.argtypes = [vp, vp, sp]
+    L.eagle_post_space_values.argtypes = [vp, vp, vp, vp]
+    L.eagle_post_device_space.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+    L.eagle_space_device_grids.argtypes = [vp, vp, i32, i32, sp, vp]
+    L.eagle_space_grids.argtypes = [vp, vp, i32, i32, sp, vp]
+    L.eagle_op_space.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, sp, i32, i32, vp, vp, vp, vp]
     lp = C.POINTER(EagleLoadParams)
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
@@ -385,7 +408,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_pass_picture", "eagle_op_minimap_trails", "eagle_op_trajectory_picture", "eagle_op_pass_picture", "eagle_post_team_shape", "eagle_post_team_shape_values",
            "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
            "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
-           "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
+           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
@@ -747,15 +771,15 @@ class Handle:
         """Candidate, owner and events of a PostTable of this handle, computed on the GPU and kept with the table (a second call replaces the first)
         -> (cand int32 [rows], owner int32 [rows]: table columns or -1, dist float64 [rows], events EVENT_DTYPE in row order)."""
         self._check(self.L.eagle_post_possession(self._h, table._t, C.byref(params)), "post_possession")
+        return self.possession_values(table) + (self.events(table),)
+
+    def possession_values(self, table):
+        """(cand int32 [rows], owner int32 [rows], dist float64 [rows]) of the table's last possession result (an EagleError before it)."""
         rows = len(table.rows)
         cand, owner, dist = np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.float64)
         keep = np.zeros(4, np.float64)
         self._check(self.L.eagle_post_possession_values(table._t, _ptr(cand, keep), _ptr(owner, keep), _ptr(dist, keep)), "post_possession_values")
-        n = C.c_int(0)
-        self._check(self.L.eagle_post_events(table._t, None, 0, C.byref(n)), "post_events")
-        ev = np.zeros(n.value, EVENT_DTYPE)
-        self._check(self.L.eagle_post_events(table._t, _ptr(ev, keep), n.value, C.byref(n)), "post_events")
-        return cand, owner, dist, ev
+        return cand, owner, dist
 
     def events(self, table):
         """The events of the table's last possession result (EVENT_DTYPE, row order; empty before it)."""
@@ -920,6 +944,40 @@ class Handle:
         a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
         self._check(self.L.eagle_post_device_roles(table._t, C.byref(a), C.byref(b), C.byref(c), C.byref(n)), "post_device_roles")
         return a.value, b.value, c.value, n.value
+
+    # --- space per player (include/eagle.h, eagle_post_space / eagle_space_grids) ------------------------------------------------
+    def space(self, table, params=None):
+        """The dominant regions and the marking of a PostTable of this handle (it needs a team mapping), computed on the GPU and kept with the table (a
+        second call replaces the first; a refused one leaves it) -> (SPACE_ROW_DTYPE [rows], SPACE_SITE_DTYPE [rows, 32], SPACE_TOTALS_DTYPE
+        [members]); params space_params(...).  eagle_amd.space derives square metres and metres."""
+        p = space_params() if params is None else params
+        self._check(self.L.eagle_post_space(self._h, table._t, C.byref(p)), "post_space")
+        nm = self.space_device(table)[3]
+        rows = len(table.rows)
+        rec, sites, totals = np.zeros(rows, SPACE_ROW_DTYPE), np.zeros((rows, SPACE_SITE_CAP), SPACE_SITE_DTYPE), np.zeros(nm, SPACE_TOTALS_DTYPE)
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_post_space_values(table._t, _ptr(rec, keep), _ptr(sites, keep), _ptr(totals, keep)), "post_space_values")
+        return rec, sites, totals
+
+    def space_device(self, table):
+        """(records, sites, totals, members) in HBM ((None, None, None, 0) before the first space call of the table)."""
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        self._check(self.L.eagle_post_device_space(table._t, C.byref(a), C.byref(b), C.byref(c), C.byref(n)), "post_device_space")
+        return a.value, b.value, c.value, n.value
+
+    def space_grids(self, table, params=None, row0=0, n=None):
+        """The owner maps of rows row0 .. row0 + n - 1 -> uint8 [n, gh, gw]: the owner's index into the row's site list, SPACE_NO_OWNER on a row that is
+        not active.  Computed from the table itself: the kept result is neither needed nor touched."""
+        p = space_params() if params is None else params
+        n = len(table.rows) - row0 if n is None else n
+        g = np.zeros((max(n, 0), 68 * p.cells_per_metre, 105 * p.cells_per_metre), np.uint8)
+        self._check(self.L.eagle_space_grids(self._h, table._t, int(row0), int(n), C.byref(p), _ptr(g, np.zeros(8, np.float64))), "space_grids")
+        return g
+
+    def space_device_grids(self, table, params, d_grid, row0=0, n=None):
+        """space_grids into device memory: n maps [n][gh][gw] at ``d_grid``."""
+        n = len(table.rows) - row0 if n is None else n
+        self._check(self.L.eagle_space_device_grids(self._h, table._t, int(row0), int(n), C.byref(params), d_grid), "space_device_grids")
 
     def set_hulls(self, table, half_width=1):
         """The half width (pixels, 1 .. 8; or an EagleHullParams) the minimap's hull layer (MM_HULLS) of this table is drawn with; None: forget it."""
@@ -1999,6 +2057,34 @@ def op_roles(values, columns, team_mapping, params=None, device=0):
     if rc:
         raise EagleError(f"eagle_op_roles failed ({rc}): {L.eagle_last_error(None).decode()}")
     return rec, mr, model
+
+
+def space_params(cells_per_metre=1, goalkeepers=1, radius=3.0):
+    """EagleSpaceParams.  A marking radius of 3 m is a conventional choice, not fitted to data."""
+    return EagleSpaceParams(int(cells_per_metre), int(goalkeepers), float(radius))
+
+
+def op_space(values, columns, team_mapping, params=None, row0=0, n=0, device=0):
+    """The space launches on a constructed table (include/eagle.h eagle_op_space): values float64 [cols][rows][2], columns [(kind, id, video)] ->
+    (SPACE_ROW_DTYPE [rows], SPACE_SITE_DTYPE [rows, 32], SPACE_TOTALS_DTYPE [members], owner maps uint8 [n, gh, gw] of rows row0 .. row0 + n - 1)."""
+    L = load()
+    values, columns = _table_args("op_space", values, columns)
+    cols, rows = values.shape[:2]
+    ids, vals, nt = _team_arrays(team_mapping)
+    p = space_params() if params is None else params
+    first = {}
+    for i, v in zip(() if ids is None else ids.tolist(), () if vals is None else vals.tolist()):
+        first.setdefault(i, v)
+    nm = sum(1 for k in columns if not k["video"] and ((int(k["kind"]) == POST_PLAYER and first.get(int(k["id"]), -1) >= 0)
+                                                       or (int(k["kind"]) == POST_GOALKEEPER and p.goalkeepers)))
+    rec, sites, totals = np.zeros(rows, SPACE_ROW_DTYPE), np.zeros((rows, SPACE_SITE_CAP), SPACE_SITE_DTYPE), np.zeros(nm, SPACE_TOTALS_DTYPE)
+    grid = np.zeros((max(int(n), 0), 68 * max(p.cells_per_metre, 0), 105 * max(p.cells_per_metre, 0)), np.uint8)
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_space(device, _ptr(values, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), nt, C.byref(p), int(row0), int(n),
+                          _ptr(rec, keep), _ptr(sites, keep), _ptr(totals, keep), _ptr(grid, keep))
+    if rc:
+        raise EagleError(f"eagle_op_space failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return rec, sites, totals, grid
 
 
 def op_minimap_hulls(values, frames, columns, team_mapping, params, hull, trail=None, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None,

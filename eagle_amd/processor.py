@@ -118,3 +118,10 @@ class Processor:
         its players to roles, its lines and label (4-4-2), the rows per id and role, every change of role and the stints per role: see eagle_amd/roles.py."""
         from . import roles as ro
         return ro.roles(self.model.handle, table, roles, min_present, iterations, lines, per_row)
+
+    def space(self, table, cells_per_metre=1, goalkeepers=True, radius=3.0, per_row=False):
+        """How much room every player of a processed table has: the exact area of the pitch nearer to him than to anybody else (by thirds), his nearest
+        opponent, the opponents within ``radius`` metres and his usual marker, per id and per team; with a possession result on the table also per owner
+        and pass: see eagle_amd/space.py."""
+        from . import space as sp
+        return sp.space(self.model.handle, table, cells_per_metre, goalkeepers, radius, per_row)

@@ -764,6 +764,92 @@ int eagle_post_device_roles(const EaglePostTable* t, const EagleRoleRow** d_rows
 int eagle_op_roles(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
                    const EagleRoleParams* p, EagleRoleRow* rows_out, int8_t* member_roles, EagleRoleModel* model);
 
+/* ---- space per player: the exact dominant region of every present member on the pitch grid, the nearest opponent and the opponents within a radius
+ * (own specification: tests/space_ref.py defines every output bit) ----
+ * GROUPS, MEMBERS, PRESENT and the quantisation q are the team shape's (above): groups 0 and 1 hold the Player pitch columns with a mapping entry (the
+ * first entry for an id counts), a member is present when x and y are finite and |x|, |y| <= 1024 m, q = floor(v * 1024 + 0.5); a mapping is required.
+ *   GOALKEEPERS  goalkeepers != 0 (the default): the Goalkeeper pitch columns, mapped or not, are the members of group 2, "neither team".  They own
+ *            cells; they are nobody's opponent and have no opponent.  goalkeepers == 0: they are no members, as in shape and roles.
+ *   SITES    of a row: its present members in table-column order, S of them.  status EMPTY (S == 0), TOO_MANY (S > EAGLE_SPACE_SITE_CAP), else ACTIVE.
+ *            The row record always holds status, n_sites = S and n[g], the present members per group.  A row that is not ACTIVE has no site
+ *            records, no cells and an owner map of 255.  Unused site slots: col = near_col = -1, near_d2 = -1, zeros.
+ *   GRID     cells_per_metre R in {1, 2, 4}, gw = 105 R, gh = 68 R, grid row 0 is pitch y = 0 (eagle_control_size's geometry).  The centre of cell (i, j)
+ *            in q is X = (2 i + 1) (512 / R), Y = (2 j + 1) (512 / R), integers for all three R.  d2 = (X - qx)^2 + (Y - qy)^2 in int64: |X - qx| <
+ *            2^21, so d2 < 2^43.  The cell's owner is the site of least d2, of equal d2 the earlier table column: coincident sites leave everything
+ *            to the earlier one; a site off the pitch is a site like any other.
+ *   THIRDS   cell (i, j) lies in third 0 when i < 35 R, in third 1 when i < 70 R, else in third 2.  A site's cells[t]: the cells it owns in third t; the
+ *            row's cells[g][t]: their sum over the sites of group g.  On an ACTIVE row all cells add up to gw gh exactly.
+ *   MARKING  of a site of group 0 or 1 over the row's sites of the other of those two groups: near_d2 = the least squared distance in q^2 (int64, <=
+ *            2^43), near_col = that site's column, the earlier column on a tie; -1, -1 without such a site.  within = the number of those sites with
+ *            d2 <= rq^2, inclusive, rq = floor(radius * 1024 + 0.5); radius is finite, > 0 and <= 1024.  A site of group 2 reports -1, -1, 0.
+ *   TOTALS   per member, in group order 0, 1, 2 and by column inside a group, over the ACTIVE rows on which it is present: rows, the sums of cells[3],
+ *            min and max of its cell total (0 when rows == 0), the rows with an opponent (near_col >= 0), the rows with within > 0, the sum of
+ *            within.  Rows are counted, not weighted by the frame step to the next row.
+ *   OWNER MAP  of a row window (row0, n): u8 [n][gh][gw], the owner's index into the row's site list; 255 on a row that is not ACTIVE.
+ * The default radius of 3 m is a conventional choice, not fitted to data.  The nearest-site rule ignores velocity (that is the control surface's job).
+ * Launches (space.hip) on the handle's main stream read the table where eagle_postprocess left it; what the call allocates is held against the table's
+ * max_bytes before the first launch.  The handle's records, staging buffers and graphs are not involved.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output alone: NULL table or parameters, a table without a mapping, cells_per_metre
+ * outside {1, 2, 4}, a radius that is not finite or outside (0, 1024], non-zero reserved words, more than EAGLE_SHAPE_MAX_MEMBERS members over the
+ * three groups, a column of unknown kind, a row window outside the table, a device-memory need beyond the budget.  A refused call leaves an earlier
+ * result of the table in place.  rows == 0 (n == 0 for a window) is success and writes nothing. */
+#define EAGLE_SPACE_SITE_CAP 32
+#define EAGLE_SPACE_EMPTY 0        /* EagleSpaceRow::status */
+#define EAGLE_SPACE_ACTIVE 1
+#define EAGLE_SPACE_TOO_MANY 2
+#define EAGLE_SPACE_NO_OWNER 255   /* the owner map of a row that is not ACTIVE */
+typedef struct EagleSpaceParams {
+    int32_t cells_per_metre;       /* 1, 2 or 4 */
+    int32_t goalkeepers;           /* != 0: the goalkeepers are group 2 (1) */
+    double radius;                 /* metres: finite, > 0, <= 1024 (3) */
+    int32_t reserved[4];           /* 0 */
+} EagleSpaceParams;                /* 32 bytes */
+typedef struct EagleSpaceRow {
+    int32_t status;                /* EAGLE_SPACE_EMPTY .. EAGLE_SPACE_TOO_MANY */
+    int32_t n_sites;               /* S, also beyond the cap */
+    int32_t n[3];                  /* present members per group */
+    int32_t cells[3][3];           /* [group][third]; 0 unless ACTIVE */
+    int32_t reserved[2];           /* 0 */
+} EagleSpaceRow;                   /* 64 bytes */
+typedef struct EagleSpaceSite {
+    int64_t near_d2;               /* the nearest opponent's squared distance, q^2; -1 without one */
+    int32_t col;                   /* the site's table column; -1: an unused slot */
+    int32_t group;                 /* 0, 1 or 2 */
+    int32_t near_col;              /* the nearest opponent's table column, or -1 */
+    int32_t within;                /* opponents with d2 <= rq^2 */
+    int32_t cells[3];              /* the cells it owns, per third */
+    int32_t qx, qy;                /* its position, q */
+    int32_t reserved;              /* 0 */
+} EagleSpaceSite;                  /* 48 bytes */
+typedef struct EagleSpaceTotals {
+    int64_t cells[3];              /* the sums of the member's cells per third */
+    int64_t within_sum;
+    int32_t col, group;            /* the member's table column and group */
+    int32_t rows;                  /* ACTIVE rows on which it is present */
+    int32_t min, max;              /* of its cell total over those rows; 0 when rows == 0 */
+    int32_t opp_rows;              /* ... with near_col >= 0 */
+    int32_t within_rows;           /* ... with within > 0 */
+    int32_t reserved;              /* 0 */
+} EagleSpaceTotals;                /* 64 bytes */
+/* The result is kept with the table until eagle_post_free and replaces an earlier one.  The members depend on the parameters, so a call computes into a
+ * buffer of its own and frees the earlier result only when the new one is complete: a refused call and a call that fails later both leave the earlier
+ * result in place.  What is held against max_bytes is what the call allocates (the new result and its member lists); until the swap the earlier result
+ * stands beside it, so for the length of a call the table may hold up to one earlier result more than the budget names. */
+int eagle_post_space(EagleHandle* h, EaglePostTable* t, const EagleSpaceParams* p);
+/* To the host: rows_out [rows], sites_out [rows][EAGLE_SPACE_SITE_CAP], totals_out [members]; any pointer may be NULL. */
+int eagle_post_space_values(EaglePostTable* t, EagleSpaceRow* rows_out, EagleSpaceSite* sites_out, EagleSpaceTotals* totals_out);
+/* In HBM; all NULL (and 0 members) before eagle_post_space.  n_members may be NULL. */
+int eagle_post_device_space(const EaglePostTable* t, const EagleSpaceRow** d_rows, const EagleSpaceSite** d_sites, const EagleSpaceTotals** d_totals, int* n_members);
+/* The owner maps of rows row0 .. row0 + n - 1 -> u8 [n][gh][gw] in HBM; returns when they are complete.  The call computes the sites of the window itself:
+ * it neither needs nor touches the table's kept result. */
+int eagle_space_device_grids(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleSpaceParams* p, uint8_t* d_grid);
+/* Same, to host memory, in passes of what 32 MB of device staging hold. */
+int eagle_space_grids(EagleHandle* h, EaglePostTable* t, int row0, int n, const EagleSpaceParams* p, uint8_t* grid);
+/* Operator entry (host buffers in / out, no handle) for constructed tables, as eagle_op_team_shape: rows_out, sites_out and totals_out cover the whole
+ * table, grid the window (row0, n); each output may be NULL. */
+int eagle_op_space(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
+                   const EagleSpaceParams* p, int row0, int n, EagleSpaceRow* rows_out, EagleSpaceSite* sites_out, EagleSpaceTotals* totals_out, uint8_t* grid);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
