@@ -43,12 +43,7 @@ static void clip_open(EagleHandle* h, const uint8_t* d_bgr, int n)
     const EagleConfig& cf = h->cfg;
     EagleHandle::Clip& c = h->clip;
     c.cv.bgr = d_bgr; c.cv.n = n; c.cv.h = cf.frame_h; c.cv.w = cf.frame_w;
-    c.cv.lh[0] = cf.frame_h; c.cv.lw[0] = cf.frame_w; c.cv.levels = 0;
-    for (int l = 1; l <= 2; ++l) {                       // cv2 maxLevel = 2 (cm.py:65); a level must exceed the 15x15 window
-        c.cv.lh[l] = (c.cv.lh[l - 1] + 1) / 2; c.cv.lw[l] = (c.cv.lw[l - 1] + 1) / 2;
-        if (c.cv.lw[l] <= 15 || c.cv.lh[l] <= 15) break;
-        c.cv.levels = l;
-    }
+    clip_view_levels(c.cv);
     c.open = true;
     for (int l = 0; l < 3; ++l) {
         HIP_CHECK(hipMalloc((void**)&c.g[l], std::max<size_t>((size_t)n * c.cv.lh[l] * c.cv.lw[l], 16)));

@@ -186,6 +186,8 @@ struct ChainState {
     unsigned char lk_status[EAGLE_N_LANDMARKS];
     int flow_n; EagleFlowKp flow[EAGLE_N_LANDMARKS];       // operator mode: the filtered dict calculate_optical_flow returns
 };
+// cv.lh / cv.lw / cv.levels of a cv.h x cv.w frame: cv2 maxLevel = 2 (cm.py:65), and a level must exceed the 15x15 window
+void clip_view_levels(ClipView& cv);
 void gray_pyramid_launch(const uint8_t* d_bgr, int n, int h, int w, uint8_t* g0, uint8_t* g1, uint8_t* g2, hipStream_t s);
 void lk_launch(const ClipView& cv, int src_frame, int dst_frame, ChainState* st, const MemList* mem, int kint, hipStream_t s);
 // ---- ECC camera motion (ecc.hip, K17) ---------------------------------------------------------------------------------------------

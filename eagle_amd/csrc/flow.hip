@@ -61,6 +61,17 @@ __global__ __launch_bounds__(256) void pyrdown_kernel(const uint8_t* __restrict_
     }
 }
 
+void clip_view_levels(ClipView& cv)
+{
+    cv.lh[0] = cv.h; cv.lw[0] = cv.w; cv.levels = 0;
+    bool stop = false;
+    for (int l = 1; l <= 2; ++l) {                       // every level gets its size (K11 writes all three); K12 reads levels 0 .. cv.levels
+        cv.lh[l] = (cv.lh[l - 1] + 1) / 2; cv.lw[l] = (cv.lw[l - 1] + 1) / 2;
+        stop = stop || cv.lw[l] <= 15 || cv.lh[l] <= 15;
+        if (!stop) cv.levels = l;
+    }
+}
+
 void gray_pyramid_launch(const uint8_t* d_bgr, int n, int h, int w, uint8_t* g0, uint8_t* g1, uint8_t* g2, hipStream_t s)
 {
     const size_t npix = (size_t)n * h * w;

@@ -353,6 +353,68 @@ int eagle_op_conv2d_argmax(int device, int precision, const float* x, int n, int
     API_END(hh)
 }
 
+// ---- the optical-flow kernels without a handle or weights (tests/test_gpu_lk.py) ------------------------------------------------------------
+// n dense BGR frames -> a ClipView as eagle_clip_open makes it (same level rule, same K11 launch), its buffers owned by `net`
+static void flow_op_view(Net& net, const char* what, const uint8_t* bgr, int n, int h, int w, ClipView& cv, uint8_t* g[3])
+{
+    if (!bgr || n < 1 || h < 32 || w < 32) fail(EAGLE_E_INVALID, "%s: n >= 1 frames of at least 32 x 32 pixels required (n %d, %d x %d)", what, n, h, w);
+    cv.bgr = (const uint8_t*)net.upload(bgr, (size_t)n * h * w * 3);
+    cv.n = n; cv.h = h; cv.w = w;
+    clip_view_levels(cv);
+    for (int l = 0; l < 3; ++l) {
+        g[l] = (uint8_t*)net.get(std::max<size_t>((size_t)n * cv.lh[l] * cv.lw[l], 16));
+        cv.g[l] = g[l];
+    }
+    gray_pyramid_launch(cv.bgr, n, h, w, g[0], g[1], g[2], nullptr);
+}
+
+int eagle_op_gray_pyramid(int device, const uint8_t* bgr, int n, int h, int w, uint8_t* g0, uint8_t* g1, uint8_t* g2, int* levels_out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!g0 || !g1 || !g2 || !levels_out) fail(EAGLE_E_INVALID, "eagle_op_gray_pyramid: null argument");
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    ClipView cv; uint8_t* g[3];
+    flow_op_view(net, "eagle_op_gray_pyramid", bgr, n, h, w, cv, g);
+    HIP_CHECK(hipDeviceSynchronize());
+    uint8_t* out[3] = {g0, g1, g2};
+    for (int l = 0; l < 3; ++l) HIP_CHECK(hipMemcpy(out[l], g[l], (size_t)n * cv.lh[l] * cv.lw[l], hipMemcpyDeviceToHost));
+    *levels_out = cv.levels;
+    API_END(hh)
+}
+
+int eagle_op_flow(int device, const uint8_t* bgr, int n, int h, int w, int src_frame, int dst_frame, int hue_frame, const EagleFlowKp* in, int n_in,
+                  EagleFlowKp* out, int* n_out, float* next_pts, uint8_t* status)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (src_frame < 0 || src_frame >= n || dst_frame < 0 || dst_frame >= n || hue_frame < 0 || hue_frame >= n || n_in < 0 || n_in > EAGLE_N_LANDMARKS ||
+        (!in && n_in > 0) || !out || !n_out)
+        fail(EAGLE_E_INVALID, "eagle_op_flow: frames inside the clip and 0 <= n_in <= %d required", EAGLE_N_LANDMARKS);
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    ClipView cv; uint8_t* g[3];
+    flow_op_view(net, "eagle_op_flow", bgr, n, h, w, cv, g);
+    *n_out = 0;
+    if (n_in == 0) { HIP_CHECK(hipDeviceSynchronize()); return EAGLE_OK; }      // cm.py:429: empty dict in -> empty dict out
+    std::vector<ChainState> zs(1);                        // exactly eagle_clip_flow's step on a scratch state
+    ChainState& z = zs[0];
+    memset(&z, 0, sizeof(z));
+    z.stalled = -1; z.n_prev = n_in;
+    for (int k = 0; k < n_in; ++k) z.prev[k] = in[k];
+    ChainState* st = (ChainState*)net.upload(&z, sizeof(z));
+    lk_launch(cv, src_frame, dst_frame, st, nullptr, 1, nullptr);
+    flow_filter_launch(cv, st, hue_frame, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(&z, st, sizeof(z), hipMemcpyDeviceToHost));
+    *n_out = z.flow_n;
+    for (int k = 0; k < z.flow_n; ++k) out[k] = z.flow[k];
+    if (next_pts) memcpy(next_pts, z.lk_next, sizeof(float) * 2 * n_in);
+    if (status) memcpy(status, z.lk_status, n_in);
+    API_END(hh)
+}
+
 // ---- the OSNet (ReID) kernels of reid.hip one launch at a time (tests/test_gpu_reid_ops.py) ------------------------------------------------
 // Every activation operand is a slice view: `c` channels at channel `off` of a buffer with `cs` floats per pixel.  Whatever lies outside the
 // slice holds EAGLE_OP_SENTINEL_BITS (a quiet NaN) when the kernel starts, and output buffers come back whole: a read outside an input slice

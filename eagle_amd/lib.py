@@ -385,6 +385,8 @@ def load():
     L.eagle_op_maxpool5.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp]
     L.eagle_op_upsample2.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp]
     L.eagle_op_split_to_f32.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.eagle_op_gray_pyramid.argtypes = [i32, u8p, i32, i32, i32, u8p, u8p, u8p, C.POINTER(i32)]
+    L.eagle_op_flow.argtypes = [i32, u8p, i32, i32, i32, i32, i32, i32, vp, i32, vp, C.POINTER(i32), fp, u8p]
     _lib = L
     return L
 
@@ -410,7 +412,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
            "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
            "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
-           "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32"]
+           "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
+           "eagle_op_flow"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 E_REFERENCE_RAISES = -7
@@ -1998,6 +2001,42 @@ def op_split_to_f32(x, c, x_off, y, y_off, device=0):
     returned whole with every bit outside the slice as it was."""
     assert y is not None, "the two storage formats differ: input and output cannot share a buffer"
     return _op_slice_pair("eagle_op_split_to_f32", None, x, c, x_off, y, y_off, None, device)
+
+
+# --- the optical-flow kernels without a handle or weights (include/eagle.h eagle_op_gray_pyramid / eagle_op_flow) ----------------
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def op_gray_pyramid(frames, device=0):
+    """gray_kernel + pyrdown_kernel (csrc/flow.hip, K11) on BGR u8 frames [n, h, w, 3] -> ([g0, g1, g2] u8 [n, lh, lw], levels): the gray frames, their
+    two pyrDown levels and the highest level the tracker uses, by the rule of eagle_clip_open."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, h, w, _ = frames.shape
+    h1, w1 = (h + 1) // 2, (w + 1) // 2
+    g = [np.zeros((n, h, w), np.uint8), np.zeros((n, h1, w1), np.uint8), np.zeros((n, (h1 + 1) // 2, (w1 + 1) // 2), np.uint8)]
+    levels = C.c_int(-1)
+    rc = L.eagle_op_gray_pyramid(device, _u8p(frames), n, h, w, _u8p(g[0]), _u8p(g[1]), _u8p(g[2]), C.byref(levels))
+    if rc:
+        raise EagleError(f"eagle_op_gray_pyramid failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return g, levels.value
+
+
+def op_flow(frames, src_frame, dst_frame, hue_frame, kps, device=0):
+    """calculate_optical_flow (cm.py:419-478) on BGR u8 frames [n, h, w, 3] as Handle.clip_flow(raw=True) runs it (K11, lk_kernel, flow_filter_kernel)
+    -> (filtered FLOWKP_DTYPE array in dict order, next points [n_in, 2] f32, status [n_in] u8)."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, h, w, _ = frames.shape
+    kps = np.ascontiguousarray(kps, FLOWKP_DTYPE)
+    out = np.zeros(N_LANDMARKS, FLOWKP_DTYPE); n_out = C.c_int(0)
+    nxt = np.zeros((max(len(kps), 1), 2), np.float32); st = np.zeros(max(len(kps), 1), np.uint8)
+    rc = L.eagle_op_flow(device, _u8p(frames), n, h, w, src_frame, dst_frame, hue_frame, kps.ctypes.data_as(C.c_void_p), len(kps),
+                         out.ctypes.data_as(C.c_void_p), C.byref(n_out), _fp(nxt), _u8p(st))
+    if rc:
+        raise EagleError(f"eagle_op_flow failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out[: n_out.value].copy(), nxt[: len(kps)], st[: len(kps)]
 
 
 # --- trails, pass arrows and the owner ring; the trajectory and the pass still -------------------------------------------------

@@ -1097,6 +1097,15 @@ int eagle_op_upsample2(int device, int precision, const float* x, int n, int h, 
 /* the mixed detector's seam: a split-format slice to an fp32 slice, exactly (hi + lo) / 16.  x is stored as split pairs, y [n][h][w][y_cs] (in/out) as fp32, bit for bit */
 int eagle_op_split_to_f32(int device, const float* x, int n, int h, int w, int c, int x_cs, int x_off, int y_cs, int y_off, float* y);
 
+/* The optical-flow kernels (flow.hip K11 / K12, the filter stage of geom.hip) on n dense BGR frames [h][w][3], without a handle or weights: what
+ * eagle_clip_open and eagle_clip_flow run, with the same pyramid-level rule.  EAGLE_E_INVALID for h < 32, w < 32 (the limits of EagleConfig) or n < 1.
+ * eagle_op_gray_pyramid: gray [n][h][w] and the two pyrDown levels [n][(h+1)/2][(w+1)/2], [n][((h+1)/2+1)/2][((w+1)/2+1)/2] of every frame (all three are always
+ * computed); *levels_out = the highest level the tracker uses (cv2 maxLevel 2; a level must exceed the 15 x 15 window).
+ * eagle_op_flow: calculate_optical_flow(frames[hue_frame], gray[src_frame], kps, gray[dst_frame]) as eagle_clip_flow; 0 <= n_in <= EAGLE_N_LANDMARKS. */
+int eagle_op_gray_pyramid(int device, const uint8_t* bgr, int n, int h, int w, uint8_t* g0, uint8_t* g1, uint8_t* g2, int* levels_out);
+int eagle_op_flow(int device, const uint8_t* bgr, int n, int h, int w, int src_frame, int dst_frame, int hue_frame, const EagleFlowKp* in, int n_in,
+                  EagleFlowKp* out /* EAGLE_N_LANDMARKS */, int* n_out, float* next_pts /* 2*n_in or NULL */, uint8_t* status /* n_in or NULL */);
+
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
  * Keys: "lk_threads" (64 | 256), "lk_dbg" (1 trace, 2 LDS guard words, 4 end-of-level verification, 8 L1-bypassing loads), "lk_excl_lds" (bytes), "lk_trace", "lk_counters". */
