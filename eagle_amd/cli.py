@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -167,7 +167,48 @@ def main(argv=None):
     ap.add_argument("--space-rows", action="store_true", help="with --space: also write the sites of every kept frame into space.json")
     ap.add_argument("--space-map", action="store_true",
                     help="with --space: also write <out>/space.npy (uint8 [rows, 68 R, 105 R]), per cell the index of its owner among the frame's sites, 255 on a skipped frame")
+    ap.add_argument("--shots", action="store_true",
+                    help="also write <out>/shots.json: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at "
+                         "the pitch, and put the shot count into metadata.json (the thresholds are conventional choices, not fitted to footage)")
+    ap.add_argument("--shots-cut", type=float, default=None, metavar="C", help="with --shots or --trim-to-shot: the score of a cut, 0 .. 1 (default 0.30)")
+    ap.add_argument("--shots-low", type=float, default=None, metavar="L",
+                    help="with --shots or --trim-to-shot: the score below which the picture has returned behind a flash, 0 .. C (default 0.10)")
+    ap.add_argument("--shots-grass", type=float, default=None, metavar="G",
+                    help="with --shots or --trim-to-shot: the mean share of grass pixels from which a shot looks at the pitch, 0 .. 1 (default 0.35)")
+    ap.add_argument("--shots-window", type=int, default=None, metavar="W",
+                    help="with --shots or --trim-to-shot: the longest gradual transition in frames, at least 2 (default max(2, round(0.4 fps)))")
+    ap.add_argument("--shots-min-len", type=int, default=None, metavar="N",
+                    help="with --shots or --trim-to-shot: the fewest frames of a usable shot, at least 1 (default --fps)")
+    ap.add_argument("--trim-to-shot", default=None, metavar="{auto,K}",
+                    help="keep only the frames of shot K of the clip (auto: the longest usable shot, the earliest on a tie) for everything that follows, the "
+                         "trimming the reference asks its users to do by hand; metadata.json records the shot's first frame and count")
     a = ap.parse_args(argv)
+    shot_set = {"cut": a.shots_cut, "low": a.shots_low, "grass_thr": a.shots_grass, "window": a.shots_window, "min_len": a.shots_min_len}
+    if not (a.shots or a.trim_to_shot is not None) and any(v is not None for v in shot_set.values()):
+        ap.error("--shots-cut, --shots-low, --shots-grass, --shots-window and --shots-min-len set up the shots: they need --shots or --trim-to-shot")
+    if a.shots or a.trim_to_shot is not None:
+        if a.fps < 1:
+            ap.error("--shots and --trim-to-shot need --fps of at least 1")
+        for k in ("cut", "low", "grass_thr"):
+            if shot_set[k] is not None:
+                if not 0.0 <= shot_set[k] <= 1.0:                       # (nan fails both comparisons)
+                    ap.error("--shots-cut, --shots-low and --shots-grass take a share of 0 .. 1")
+                shot_set[k] = int(shot_set[k] * 65536 + 0.5)
+        from . import shots as _shots
+        resolved = dict(_shots.default_params(a.fps), **{k: v for k, v in shot_set.items() if v is not None})
+        if resolved["low"] > resolved["cut"]:
+            ap.error("--shots-low must not be above --shots-cut")
+        if resolved["window"] < 2:
+            ap.error("--shots-window takes at least 2 frames")
+        if resolved["min_len"] < 1:
+            ap.error("--shots-min-len takes at least 1 frame")
+        if a.trim_to_shot is not None and a.trim_to_shot != "auto":
+            try:
+                a.trim_to_shot = int(a.trim_to_shot)
+            except ValueError:
+                a.trim_to_shot = -1
+            if a.trim_to_shot < 0:
+                ap.error("--trim-to-shot takes `auto` or the index of a shot, 0 or above")
     if a.space and not a.processed:
         ap.error("--space works on the processed table: it needs --processed")
     if not a.space and (a.space_rows or a.space_map or a.space_grid is not None or a.space_radius is not None):
@@ -266,6 +307,25 @@ def main(argv=None):
                             precision=a.precision, detector_precision=a.detector_precision, allow_saturation=a.allow_saturation, device=a.device, seed=a.seed,
                             hrnet_state_dict=hs, detector_state_dict=ys, tracker=a.tracker, camera_motion=a.camera_motion or False,
                             reid=a.reid, reid_state_dict=({("reid." + k): v for k, v in load_state_dict(a.reid_weights).items()} if a.reid_weights else None))
+    shot_meta = {}
+    if a.shots or a.trim_to_shot is not None:
+        from . import shots as _shots
+        found = model.shots(frames, a.fps, **shot_set)
+        shot_meta["shots"] = len(found.shots)
+        if a.shots:
+            os.makedirs(a.out, exist_ok=True)
+            with open(os.path.join(a.out, "shots.json"), "w") as f:
+                json.dump(_shots.to_json(found), f)
+        if a.trim_to_shot is not None:
+            k = _shots.longest_usable(found) if a.trim_to_shot == "auto" else a.trim_to_shot
+            if k is None:
+                raise SystemExit(f"error: --trim-to-shot auto: none of the clip's {len(found.shots)} shots looks at the pitch for at least {found.params['min_len']} frames")
+            if k >= len(found.shots):
+                raise SystemExit(f"error: --trim-to-shot {k}: the clip has {len(found.shots)} shots")
+            first, count = int(found.shots[k]["first"]), int(found.shots[k]["count"])
+            shot_meta["trim"] = {"shot": int(k), "first": first, "count": count}
+            frames = frames[first:first + count]
+            n = count
     t0 = time.perf_counter()
     nh, nk = (a.fps, a.fps) if a.every_frame else (a.num_homography, a.num_keypoint_detection)
     from . import lib
@@ -382,6 +442,7 @@ def main(argv=None):
         team_mapping = Processor(model).get_team_mapping(frames, coordinates)
         write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420"), a.fps)
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
+    meta.update(shot_meta)
     with open(os.path.join(a.out, "metadata.json"), "w") as f:
         json.dump(meta, f, default=str)
     print(f"{n} frames in {dt:.3f} s -> {os.path.join(a.out, 'raw_coordinates.json')}")

@@ -143,6 +143,12 @@ class CoordinateModel:
             return recs
         return np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1)
 
+    def shots(self, frames, fps, pixel_format="bgr", **overrides):
+        """Where the clip is cut and which of its shots look at the pitch (eagle_amd/shots.py find_shots): run it in front of get_coordinates,
+        which assumes one continuous shot.  Nothing consumes the result unless the caller does."""
+        from . import shots as sh
+        return sh.find_shots(self.handle, frames, fps, pixel_format, **overrides)
+
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The frames with their records drawn on them (the reference's annotated video, main.py:43-81; include/eagle.h eagle_annotate_frames):
         uint8 [n, h, w, 3] for out_format "bgr", [n, 3h/2, w] for "nv12" / "i420".  ``frames`` as get_coordinates takes them (pixel_format "bgr",

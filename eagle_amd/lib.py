@@ -126,6 +126,21 @@ SPACE_TOTALS_DTYPE = np.dtype([("cells", "<i8", 3), ("within_sum", "<i8"), ("col
 assert C.sizeof(EagleSpaceParams) == 32 and (SPACE_ROW_DTYPE.itemsize, SPACE_SITE_DTYPE.itemsize, SPACE_TOTALS_DTYPE.itemsize) == (64, 48, 64)       # space.hip asserts them too
 
 
+class EagleShotParams(C.Structure):
+    """include/eagle.h EagleShotParams: cut, low and grass_thr in 1 / 65536, the window W in frames, the least length of a usable shot in frames."""
+    _fields_ = [("cut", C.c_int32), ("low", C.c_int32), ("grass_thr", C.c_int32), ("window", C.c_int32), ("min_len", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+SHOT_SIGNATURE = 1537                                                        # include/eagle.h EAGLE_SHOT_*
+SHOT_START, SHOT_AFTER_CUT, SHOT_AFTER_TRANSITION, SHOT_TRANSITION = 0, 1, 2, 3
+SHOT_KIND_NAMES = ("start", "after_cut", "after_transition", "transition")
+SHOT_FRAME_FLASH, SHOT_FRAME_HARD, SHOT_FRAME_GRADUAL_END, SHOT_FRAME_IN_TRANSITION = 1, 2, 4, 8
+SHOT_PITCH, SHOT_SHORT, SHOT_USABLE = 1, 2, 4
+SHOT_FRAME_DTYPE = np.dtype([("d1", "<i4"), ("d2", "<i4"), ("dW", "<i4"), ("sg", "<i4"), ("st", "<i4"), ("grass", "<u4"), ("flags", "<i4"), ("reserved", "<i4")])  # EagleShotFrame (32 bytes)
+SHOT_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("kind", "<i4"), ("flags", "<i4"), ("grass_sum", "<i8"), ("reserved", "<i4", 2)])                      # EagleShot (32 bytes)
+assert C.sizeof(EagleShotParams) == 32 and (SHOT_FRAME_DTYPE.itemsize, SHOT_DTYPE.itemsize) == (32, 32)                                                # shots.hip asserts them too
+
+
 class EagleKinematicsParams(C.Structure):
     """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
@@ -367,6 +382,10 @@ def load():
     L.eagle_space_device_grids.argtypes = [vp, vp, i32, i32, sp, vp]
     L.eagle_space_grids.argtypes = [vp, vp, i32, i32, sp, vp]
     L.eagle_op_space.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, sp, i32, i32, vp, vp, vp, vp]
+    shp = C.POINTER(EagleShotParams)
+    L.eagle_shots_device_frames.argtypes = [vp, vp, i32, shp, vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_shots_frames.argtypes = [vp, vp, i32, i64, i64, i64, shp, vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_op_shots.argtypes = [i32, vp, i32, i32, i32, shp, vp, vp, i32, C.POINTER(C.c_int), vp]
     lp = C.POINTER(EagleLoadParams)
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
@@ -411,7 +430,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
            "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
            "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
-           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
            "eagle_op_flow"]
 
@@ -655,6 +674,38 @@ class Handle:
             return self.yuv_to_bgr_device(d, n, pixel_format)
         finally:
             self.free(d)
+
+    # --- shots: cuts, transitions and flashes of a clip (include/eagle.h, eagle_shots_*) ---------------------------------------------
+    def shots_device(self, dptr, n, params=None, cap=None, **kw):
+        """n dense BGR frames of the handle's size resident in HBM -> (frames [n] of SHOT_FRAME_DTYPE, shots [m] of SHOT_DTYPE).  params: an
+        EagleShotParams, or keywords for shot_params(...) (cut, low, grass_thr in 1 / 65536; window, min_len in frames; fps picks the defaults)."""
+        p = shot_params(**kw) if params is None else params
+        n = int(n)
+        rows, shots, m = _shot_outputs(n, cap)
+        self._check(self.L.eagle_shots_device_frames(self._h, dptr, n, C.byref(p), rows.ctypes.data_as(C.c_void_p), shots.ctypes.data_as(C.c_void_p), len(shots),
+                                                     C.byref(m)), "shots_device_frames")
+        return rows, shots[:m.value].copy()
+
+    def shots(self, frames, params=None, cap=None, max_staging_bytes=0, strides=None, **kw):
+        """frames: uint8 [n, h, w, 3] BGR in host memory, handed over as the view it is (process() has the rules), uploaded in passes of
+        ``max_staging_bytes`` (0: 64 MB) -> (frames, shots) as shots_device."""
+        p = shot_params(**kw) if params is None else params
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[1:] != (self.cfg.frame_h, self.cfg.frame_w, 3):
+            raise EagleError(f"shots: frames must be uint8 [n, {self.cfg.frame_h}, {self.cfg.frame_w}, 3] (got {frames.dtype} {frames.shape})")
+        n, h, w, _ = frames.shape
+        fs, rs, ps, cs = frames.strides
+        if n == 1:
+            fs = max(fs, rs * (h - 1) + 3 * w)
+        if not (cs == 1 and ps == 3 and rs >= 3 * w and fs >= rs * (h - 1) + 3 * w):
+            frames = np.ascontiguousarray(frames)
+            fs, rs = h * w * 3, w * 3
+        if strides is not None:
+            fs, rs = strides
+        rows, shots, m = _shot_outputs(n, cap)
+        self._check(self.L.eagle_shots_frames(self._h, C.c_void_p(frames.ctypes.data), n, int(rs), int(fs), int(max_staging_bytes), C.byref(p),
+                                              rows.ctypes.data_as(C.c_void_p), shots.ctypes.data_as(C.c_void_p), len(shots), C.byref(m)), "shots_frames")
+        return rows, shots[:m.value].copy()
 
     # --- annotated output (include/eagle.h, eagle_annotate_*) --------------------------------------------------
     def annotate_device(self, d_bgr, n, recs, d_out, team_mapping=None, fmt="bgr", layout=None):
@@ -2124,6 +2175,40 @@ def op_space(values, columns, team_mapping, params=None, row0=0, n=0, device=0):
     if rc:
         raise EagleError(f"eagle_op_space failed ({rc}): {L.eagle_last_error(None).decode()}")
     return rec, sites, totals, grid
+
+
+def shot_params(cut=None, low=None, grass_thr=None, window=None, min_len=None, fps=25):
+    """EagleShotParams.  Unset fields take eagle_amd.shots.default_params(fps): cut 0.30, low 0.10 and grass_thr 0.35 in 1 / 65536, a window of
+    max(2, round(0.4 fps)) frames and min_len = fps frames: conventional choices, not fitted to footage."""
+    from . import shots as _shots
+    d = _shots.default_params(fps)
+    for k, v in (("cut", cut), ("low", low), ("grass_thr", grass_thr), ("window", window), ("min_len", min_len)):
+        if v is not None:
+            d[k] = int(v)
+    return EagleShotParams(d["cut"], d["low"], d["grass_thr"], d["window"], d["min_len"])
+
+
+def _shot_outputs(n, cap):
+    """a clip of n frames has at most n shots"""
+    return np.zeros(max(n, 0), SHOT_FRAME_DTYPE), np.zeros(max(n, 1) if cap is None else int(cap), SHOT_DTYPE), C.c_int(0)
+
+
+def op_shots(frames, params=None, cap=None, signatures=True, device=0, **kw):
+    """The shots launches on constructed frames (include/eagle.h eagle_op_shots): frames uint8 [n, h, w, 3], any h, w >= 4 ->
+    (signatures u32 [n, 1537] or None, frames [n] of SHOT_FRAME_DTYPE, shots [m] of SHOT_DTYPE)."""
+    L = load()
+    p = shot_params(**kw) if params is None else params
+    frames = np.ascontiguousarray(frames, np.uint8)
+    if frames.ndim != 4 or frames.shape[3] != 3:
+        raise EagleError(f"op_shots: frames must be [n, h, w, 3] (got {frames.shape})")
+    n, h, w, _ = frames.shape
+    rows, shots, m = _shot_outputs(n, cap)
+    sig = np.zeros((n, SHOT_SIGNATURE), np.uint32) if signatures else None
+    keep = np.zeros(8, np.uint8)
+    rc = L.eagle_op_shots(device, _ptr(frames, keep), n, h, w, C.byref(p), _ptr(rows, keep), _ptr(shots, keep), len(shots), C.byref(m), None if sig is None else _ptr(sig, keep))
+    if rc:
+        raise EagleError(f"eagle_op_shots failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return sig, rows, shots[:m.value].copy()
 
 
 def op_minimap_hulls(values, frames, columns, team_mapping, params, hull, trail=None, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None,

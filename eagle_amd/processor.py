@@ -49,6 +49,11 @@ class Processor:
         table = postprocess.process_data(self.model.handle, recs, fps, self.model.handle.cfg.frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids)
         return table, table.team_mapping if merge_ids else team_mapping
 
+    def shots(self, frames, fps, pixel_format="bgr", **overrides):
+        """The cuts, transitions, flashes and shots of a clip, and which shots look at the pitch: see eagle_amd/shots.py."""
+        from . import shots as sh
+        return sh.find_shots(self.model.handle, frames, fps, pixel_format, **overrides)
+
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The annotated frames of a clip (the reference's annotated video, main.py:43-81), drawn on the GPU: see CoordinateModel.annotate.
         ``table``: draw the processed table (process_data above) instead of the raw records."""

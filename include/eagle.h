@@ -850,6 +850,79 @@ int eagle_space_grids(EagleHandle* h, EaglePostTable* t, int row0, int n, const 
 int eagle_op_space(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
                    const EagleSpaceParams* p, int row0, int n, EagleSpaceRow* rows_out, EagleSpaceSite* sites_out, EagleSpaceTotals* totals_out, uint8_t* grid);
 
+/* ---- shots: the camera cuts, gradual transitions and photo flashes of a clip, and which of its shots look at the pitch (own specification:
+ * tests/shots_ref.py defines every output bit) ----
+ * The stage in front of the networks: every other stage assumes one continuous shot of the main camera.  Input: n dense BGR frames [h][w][3], P = h w.
+ *   SIGNATURE  of a frame, EAGLE_SHOT_SIGNATURE = 1537 u32: hist [512], the pixels per bin (b >> 5) 64 + (g >> 5) 8 + (r >> 5); tile [16][64], a 4 x 4 grid
+ *            of tiles of th = h / 4 rows and tw = w / 4 columns over the top-left 4 th x 4 tw pixels, tile 4 ty + tx counting the bins (b >> 6) 16 +
+ *            (g >> 6) 4 + (r >> 6) (the up to 3 remaining rows and columns count in hist and grass only; A = th tw); grass, the pixels with g >= 48 and
+ *            g - max(r, b) >= 16.
+ *   SCORE    of a frame pair in 1 / 65536, integers throughout: sg = 65536 sum |hist_a - hist_b| / (2 P); st = 65536 u / (16 A), u the sum of the 8
+ *            smallest of the 16 tile distances sum_64 |tile_a - tile_b| (the 8 largest are dropped: captions, local motion); S = max(sg, st).
+ *   FRAMES   per frame i: d1 = S(i-1, i), d2 = S(i-2, i), dW = S(i-W, i), 0 where the earlier frame does not exist; sg and st of the d1 pair; grass.
+ *   FLASH    f >= 1, d1[f] >= cut, f + 1 < n and d2[f+1] < low: the picture returns to what it was.  A flash in the last frame is a cut.
+ *   HARD CUT i >= 1, d1[i] >= cut, neither i nor i - 1 a flash.
+ *   GRADUAL  i is eligible when i >= W, dW[i] >= cut, no hard cut lies in [i-W+1, i] and neither i nor i - W is a flash; it ends a transition when
+ *            dW[i] is greater than dW of every eligible frame of [i-W+1, i-1] and at least dW of every eligible frame of [i+1, i+W-1] (the first
+ *            maximum).  The frames [i-W+1, i-1] are then IN_TRANSITION and form a shot of kind TRANSITION; a new shot starts at i.  Two ends lie at
+ *            least W frames apart.
+ *   SHOTS    the runs between boundaries (frame 0, a hard cut, a transition's first frame, a gradual end), in frame order.  kind: TRANSITION, else
+ *            AFTER_TRANSITION at a gradual end, else AFTER_CUT, else START.  grass_sum: the sum of grass over its frames.  PITCH: kind != TRANSITION
+ *            and grass_sum 65536 >= grass_thr P count; SHORT: count < min_len; USABLE: PITCH and not SHORT.
+ * The defaults (eagle_amd/shots.py: cut 0.30, low 0.10, grass_thr 0.35, W = max(2, round(0.4 fps)), min_len = fps) are conventional choices; nothing
+ * here is fitted to or validated on broadcast footage.  The stage finds boundaries: beyond "looks at grass" it does not classify camera angles, and a
+ * wipe longer than W frames shows only through the grass share of what follows it.
+ * Launches (shots.hip) on the handle's main stream; the signatures (6148 bytes per frame) are allocated per call and freed.  The handle's records,
+ * staging buffers and graphs are not involved.
+ * EAGLE_E_INVALID with a message that names the value, before any launch and leaving every output alone: NULL pointers (frames with n > 0, parameters,
+ * n_shots; frames_out with n > 0), n < 0, cap < 0, window < 2, min_len < 1, a threshold outside 0 .. 65536, low > cut, non-zero reserved words; in the
+ * operator entry h < 4, w < 4 or h w > 2^30; in the host entry strides below a dense frame's.  More shots than cap (or shots_out NULL with shots to report):
+ * EAGLE_E_INVALID, *n_shots holds the count, the other outputs are left alone.  n == 0 is success with *n_shots = 0. */
+#define EAGLE_SHOT_SIGNATURE 1537
+#define EAGLE_SHOT_START 0             /* EagleShot::kind */
+#define EAGLE_SHOT_AFTER_CUT 1
+#define EAGLE_SHOT_AFTER_TRANSITION 2
+#define EAGLE_SHOT_TRANSITION 3
+#define EAGLE_SHOT_FRAME_FLASH 1       /* EagleShotFrame::flags */
+#define EAGLE_SHOT_FRAME_HARD 2
+#define EAGLE_SHOT_FRAME_GRADUAL_END 4
+#define EAGLE_SHOT_FRAME_IN_TRANSITION 8
+#define EAGLE_SHOT_PITCH 1             /* EagleShot::flags */
+#define EAGLE_SHOT_SHORT 2
+#define EAGLE_SHOT_USABLE 4
+typedef struct EagleShotParams {
+    int32_t cut;                   /* 1 / 65536: 0 .. 65536 */
+    int32_t low;                   /* 1 / 65536: 0 .. cut */
+    int32_t grass_thr;             /* 1 / 65536: 0 .. 65536 */
+    int32_t window;                /* W >= 2 frames */
+    int32_t min_len;               /* >= 1 frames */
+    int32_t reserved[3];           /* 0 */
+} EagleShotParams;                 /* 32 bytes */
+typedef struct EagleShotFrame {
+    int32_t d1, d2, dW;            /* S against the frame 1, 2 and W earlier */
+    int32_t sg, st;                /* of the d1 pair */
+    uint32_t grass;
+    int32_t flags;                 /* EAGLE_SHOT_FRAME_* */
+    int32_t reserved;              /* 0 */
+} EagleShotFrame;                  /* 32 bytes */
+typedef struct EagleShot {
+    int32_t first, count;
+    int32_t kind;                  /* EAGLE_SHOT_START .. EAGLE_SHOT_TRANSITION */
+    int32_t flags;                 /* EAGLE_SHOT_PITCH | _SHORT | _USABLE */
+    int64_t grass_sum;
+    int32_t reserved[2];           /* 0 */
+} EagleShot;                       /* 32 bytes */
+/* n frames of the handle's size, dense, resident in HBM -> frames_out [n], shots_out [*n_shots <= cap]; returns when they are complete. */
+int eagle_shots_device_frames(EagleHandle* h, const uint8_t* d_bgr, int n, const EagleShotParams* p, EagleShotFrame* frames_out, EagleShot* shots_out, int cap, int* n_shots);
+/* Same for frames in host memory (pageable or pinned; row_stride >= 3 w, frame_stride >= (h - 1) row_stride + 3 w, 0 = dense), uploaded in passes of what
+ * max_staging_bytes (0: 64 MB; always at least one frame) of device staging hold.  The signatures of all n frames stay resident over the passes and the
+ * scores are formed behind the last one, so the result does not depend on the size of a pass. */
+int eagle_shots_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t row_stride, int64_t frame_stride, int64_t max_staging_bytes, const EagleShotParams* p,
+                       EagleShotFrame* frames_out, EagleShot* shots_out, int cap, int* n_shots);
+/* Operator entry (host buffers in / out, no handle): dense frames of any h, w >= 4; signatures_out (may be NULL): [n][EAGLE_SHOT_SIGNATURE] u32. */
+int eagle_op_shots(int device, const uint8_t* bgr, int n, int h, int w, const EagleShotParams* p, EagleShotFrame* frames_out, EagleShot* shots_out, int cap, int* n_shots,
+                   uint32_t* signatures_out);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
