@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -182,7 +182,49 @@ def main(argv=None):
     ap.add_argument("--trim-to-shot", default=None, metavar="{auto,K}",
                     help="keep only the frames of shot K of the clip (auto: the longest usable shot, the earliest on a tie) for everything that follows, the "
                          "trimming the reference asks its users to do by hand; metadata.json records the shot's first frame and count")
+    ap.add_argument("--topview", action="store_true",
+                    help="also write <out>/topview.y4m: every frame warped onto the pitch plane with its homography (the picture that shows whether the homography "
+                         "puts the painted lines where the pitch model has them); needs neither --processed nor a tracker")
+    ap.add_argument("--topview-scale", type=int, default=None, metavar="S", help="with --topview: pixels per metre, even, 2 .. 32 (default 8)")
+    ap.add_argument("--topview-margin", type=int, default=None, metavar="M", help="with --topview: pixels round the pitch, even, 0 .. 64 (default two metres' worth, at most 64)")
+    ap.add_argument("--topview-markings", action="store_true", help="with --topview: draw the pitch model's markings over the pictures, in red")
+    ap.add_argument("--topview-carry", action="store_true",
+                    help="with --topview: a frame without a homography of its own uses the latest earlier one, which is what the reference projects with")
+    ap.add_argument("--topview-mosaic", action="store_true",
+                    help="with --topview: also write <out>/topview_mosaic.ppm (the mean of the warped frames: the pitch without the players), <out>/topview_count.npy "
+                         "(how many frames each pixel has) and <out>/topview.json (per frame its coverage and its distance from the mosaic, the clip's median and the "
+                         "suspect frames)")
+    ap.add_argument("--topview-mask-boxes", type=float, default=None, metavar="PAD",
+                    help="with --topview-mosaic: leave the inside of every detection box, widened by PAD pixels, out of the mosaic")
+    ap.add_argument("--topview-step", type=int, default=None, metavar="K", help="with --topview-mosaic: build the mosaic from every K-th frame (default 1)")
+    ap.add_argument("--topview-min-count", type=int, default=None, metavar="C", help="with --topview-mosaic: a mosaic pixel needs C frames (default 1)")
+    ap.add_argument("--topview-suspect", type=float, default=None, metavar="R",
+                    help="with --topview-mosaic: list the frames whose residual exceeds R times the clip's median (default 2.0, a conventional choice, not fitted to footage)")
     a = ap.parse_args(argv)
+    if not a.topview and (a.topview_markings or a.topview_carry or a.topview_mosaic or
+                          any(v is not None for v in (a.topview_scale, a.topview_margin, a.topview_mask_boxes, a.topview_step, a.topview_min_count, a.topview_suspect))):
+        ap.error("--topview-scale, --topview-margin, --topview-markings, --topview-carry, --topview-mosaic, --topview-mask-boxes, --topview-step, --topview-min-count and "
+                 "--topview-suspect set up the top view: they need --topview")
+    if a.topview:
+        if not a.topview_mosaic and any(v is not None for v in (a.topview_mask_boxes, a.topview_step, a.topview_min_count, a.topview_suspect)):
+            ap.error("--topview-mask-boxes, --topview-step, --topview-min-count and --topview-suspect set up the mosaic: they need --topview-mosaic")
+        S = 8 if a.topview_scale is None else a.topview_scale
+        if not (2 <= S <= 32 and S % 2 == 0):
+            ap.error("--topview-scale takes an even number of pixels per metre within 2 .. 32")
+        M = min(64, 2 * S) if a.topview_margin is None else a.topview_margin
+        if not (0 <= M <= 64 and M % 2 == 0):
+            ap.error("--topview-margin takes an even number of pixels within 0 .. 64")
+        if a.topview_step is not None and a.topview_step < 1:
+            ap.error("--topview-step takes at least 1")
+        if a.topview_min_count is not None and a.topview_min_count < 1:
+            ap.error("--topview-min-count takes at least 1")
+        if a.topview_mask_boxes is not None and not 0.0 <= a.topview_mask_boxes < float("inf"):      # (nan fails both comparisons)
+            ap.error("--topview-mask-boxes takes a finite padding of 0 pixels or more")
+        if a.topview_suspect is not None and not 0.0 < a.topview_suspect < float("inf"):
+            ap.error("--topview-suspect takes a finite ratio above 0")
+        a.topview_set = dict(scale=S, margin=M, markings=a.topview_markings)
+        a.mosaic_set = dict(a.topview_set, mask_boxes=a.topview_mask_boxes is not None, box_pad=a.topview_mask_boxes or 0.0, step=a.topview_step or 1,
+                            min_count=a.topview_min_count or 1)
     shot_set = {"cut": a.shots_cut, "low": a.shots_low, "grass_thr": a.shots_grass, "window": a.shots_window, "min_len": a.shots_min_len}
     if not (a.shots or a.trim_to_shot is not None) and any(v is not None for v in shot_set.values()):
         ap.error("--shots-cut, --shots-low, --shots-grass, --shots-window and --shots-min-len set up the shots: they need --shots or --trim-to-shot")
@@ -442,6 +484,16 @@ def main(argv=None):
         team_mapping = Processor(model).get_team_mapping(frames, coordinates)
         write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420"), a.fps)
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
+    if a.topview:
+        from . import topview as tv
+        from .annotate import write_y4m
+        write_y4m(os.path.join(a.out, "topview.y4m"), model.topview(frames, coordinates, carry=a.topview_carry, out_format="i420", **a.topview_set), a.fps)
+        if a.topview_mosaic:
+            res = model.mosaic(frames, coordinates, carry=a.topview_carry, **a.mosaic_set)
+            tv.write_ppm(os.path.join(a.out, "topview_mosaic.ppm"), res.mosaic)
+            np.save(os.path.join(a.out, "topview_count.npy"), res.cnt)
+            with open(os.path.join(a.out, "topview.json"), "w") as f:
+                json.dump(tv.to_json(res, carry=a.topview_carry, suspect=tv.SUSPECT if a.topview_suspect is None else a.topview_suspect), f)
     meta.update(shot_meta)
     with open(os.path.join(a.out, "metadata.json"), "w") as f:
         json.dump(meta, f, default=str)

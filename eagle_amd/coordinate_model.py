@@ -149,6 +149,18 @@ class CoordinateModel:
         from . import shots as sh
         return sh.find_shots(self.handle, frames, fps, pixel_format, **overrides)
 
+    def topview(self, frames, coords_or_records, carry=False, out_format="bgr", **kw):
+        """The frames warped onto the pitch plane with the homography of their records (eagle_amd/topview.py topview): uint8 [n, Hc, W, 3], or
+        [n, 3 Hc / 2, W] for "nv12" / "i420".  ``coords_or_records`` as annotate takes them; a frame that did not solve its own homography has none
+        unless ``carry`` hands it the latest earlier one."""
+        from . import topview as tv
+        return tv.topview(self.handle, frames, self._records_of(coords_or_records, carried_as_plain=True), carry, out_format, **kw)
+
+    def mosaic(self, frames, coords_or_records, carry=False, **kw):
+        """The mean of the warped frames, its count map and every frame's distance from it (eagle_amd/topview.py mosaic)."""
+        from . import topview as tv
+        return tv.mosaic(self.handle, frames, self._records_of(coords_or_records, carried_as_plain=True), carry, **kw)
+
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The frames with their records drawn on them (the reference's annotated video, main.py:43-81; include/eagle.h eagle_annotate_frames):
         uint8 [n, h, w, 3] for out_format "bgr", [n, 3h/2, w] for "nv12" / "i420".  ``frames`` as get_coordinates takes them (pixel_format "bgr",

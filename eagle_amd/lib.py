@@ -141,6 +141,18 @@ SHOT_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("kind", "<i4"), ("fl
 assert C.sizeof(EagleShotParams) == 32 and (SHOT_FRAME_DTYPE.itemsize, SHOT_DTYPE.itemsize) == (32, 32)                                                # shots.hip asserts them too
 
 
+class EagleTopviewParams(C.Structure):
+    """include/eagle.h EagleTopviewParams: the canvas (scale, margin), the colours as B | G << 8 | R << 16, whether the markings are painted, whether
+    the detection boxes mask the mosaic (padded by box_pad pixels), the mosaic's frames (first, step) and the least count of a mosaic pixel."""
+    _fields_ = [("scale", C.c_int32), ("margin", C.c_int32), ("background", C.c_uint32), ("markings", C.c_int32), ("marking_colour", C.c_uint32),
+                ("mask_boxes", C.c_int32), ("box_pad", C.c_double), ("first", C.c_int32), ("step", C.c_int32), ("min_count", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+TOPVIEW_VIDEO, TOPVIEW_MOSAIC, TOPVIEW_RESIDUAL = 1, 2, 4                    # include/eagle.h EAGLE_TOPVIEW_*
+TOPVIEW_MAX_FRAMES = 1 << 23
+assert C.sizeof(EagleTopviewParams) == 56                                    # topview.hip asserts it too
+
+
 class EagleKinematicsParams(C.Structure):
     """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
@@ -386,6 +398,16 @@ def load():
     L.eagle_shots_device_frames.argtypes = [vp, vp, i32, shp, vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_shots_frames.argtypes = [vp, vp, i32, i64, i64, i64, shp, vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_op_shots.argtypes = [i32, vp, i32, i32, i32, shp, vp, vp, i32, C.POINTER(C.c_int), vp]
+    tvp, lay = C.POINTER(EagleTopviewParams), C.POINTER(EagleYuvLayout)
+    L.eagle_topview_size.argtypes = [tvp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.eagle_topview_device_frames.argtypes = [vp, vp, i32, vp, vp, tvp, i32, lay, vp]
+    L.eagle_topview_frames.argtypes = [vp, vp, i32, vp, vp, tvp, i32, lay, vp]
+    L.eagle_topview_mosaic_device.argtypes = [vp, vp, i32, vp, vp, vp, tvp, vp, i32]
+    L.eagle_topview_mosaic_finish.argtypes = [vp, vp, tvp, vp, vp]
+    L.eagle_topview_residual_device.argtypes = [vp, vp, i32, vp, vp, vp, tvp, vp, vp, vp, vp]
+    L.eagle_topview_mosaic_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, tvp, vp, i32]
+    L.eagle_topview_residual_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, tvp, vp, vp, vp, vp]
+    L.eagle_op_topview.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, tvp, i32, i32, lay, vp, vp, vp, vp, vp, vp]
     lp = C.POINTER(EagleLoadParams)
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
@@ -430,7 +452,9 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
            "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
            "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
-           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
+           "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
+           "eagle_op_topview", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
            "eagle_op_flow"]
 
@@ -706,6 +730,90 @@ class Handle:
         self._check(self.L.eagle_shots_frames(self._h, C.c_void_p(frames.ctypes.data), n, int(rs), int(fs), int(max_staging_bytes), C.byref(p),
                                               rows.ctypes.data_as(C.c_void_p), shots.ctypes.data_as(C.c_void_p), len(shots), C.byref(m)), "shots_frames")
         return rows, shots[:m.value].copy()
+
+    # --- top view: the frames on the pitch plane, their mosaic and residuals (include/eagle.h, eagle_topview_*) -------------------------
+    def device_alloc(self, nbytes):
+        d = C.c_void_p()
+        self._check(self.L.eagle_device_alloc(self._h, int(nbytes), C.byref(d)), "device_alloc")
+        return d
+
+    def _topview_clip(self, what, frames, Hs, valid, n=None):
+        """-> (frames or None, n, Hs float64 [n, 9], valid uint8 [n]); frames None: a device clip of n frames"""
+        if frames is not None:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            if frames.ndim != 4 or frames.shape[1:] != (self.cfg.frame_h, self.cfg.frame_w, 3):
+                raise EagleError(f"{what}: frames must be uint8 [n, {self.cfg.frame_h}, {self.cfg.frame_w}, 3] (got {frames.shape})")
+            n = len(frames)
+        return (frames, int(n)) + _topview_maps(what, Hs, valid, int(n))
+
+    def topview_device(self, d_bgr, n, Hs, valid, params, d_out, fmt="bgr", layout=None):
+        """n dense BGR frames resident in HBM + their homographies -> n warped frames at ``d_out`` (device) in ``fmt`` / ``layout``."""
+        _, n, Hs, valid = self._topview_clip("topview_device", None, Hs, valid, n)
+        lay = _yuv_layout(layout)
+        keep = np.zeros(16, np.uint8)
+        self._check(self.L.eagle_topview_device_frames(self._h, d_bgr, n, _ptr(Hs, keep), _ptr(valid, keep), C.byref(params), _out_pix(fmt),
+                                                       None if lay is None else C.byref(lay), d_out), "topview_device_frames")
+
+    def topview(self, frames, Hs, valid, params, fmt="bgr", layout=None, out=None):
+        """frames uint8 [n, h, w, 3] (host) -> the warped frames in host memory: uint8 [n, Hc, W, 3] ("bgr") or [n, 3 Hc / 2, W] ("nv12" / "i420") with
+        (W, Hc) = topview_size(params); with a ``layout`` a flat uint8 buffer of the layout's span (``out``: the caller's buffer)."""
+        frames, n, Hs, valid = self._topview_clip("topview", frames, Hs, valid)
+        w, h = topview_size(params)
+        lay = _yuv_layout(layout)
+        need = out_span(fmt, h, w, lay, n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+            if lay is None:
+                out = out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise EagleError(f"topview: out must be a contiguous uint8 array of at least {need} bytes")
+        keep = np.zeros(16, np.uint8)
+        self._check(self.L.eagle_topview_frames(self._h, _ptr(frames, keep), n, _ptr(Hs, keep), _ptr(valid, keep), C.byref(params), _out_pix(fmt),
+                                                None if lay is None else C.byref(lay), _ptr(out, keep)), "topview_frames")
+        return out
+
+    def topview_accumulator(self, params):
+        """A device accumulator u32 [Hc][W][4] for these parameters (free it with free()); the first mosaic call zeroes it (reset=True)."""
+        w, h = topview_size(params)
+        return self.device_alloc(w * h * 16)
+
+    def topview_mosaic_add(self, frames, Hs, valid, params, d_acc, recs=None, reset=True, n=None, max_staging_bytes=0):
+        """Adds the frames first, first + step, ... to ``d_acc``.  frames: uint8 [n, h, w, 3] in host memory (uploaded in passes of ``max_staging_bytes``)
+        or a device pointer with ``n``.  recs: the records, needed with params.mask_boxes."""
+        dev, d_bgr = isinstance(frames, C.c_void_p), frames
+        frames, n, Hs, valid = self._topview_clip("topview_mosaic_add", None if dev else frames, Hs, valid, n)
+        recs = _topview_recs(recs, n)
+        keep = np.zeros(16, np.uint8)
+        if dev:
+            rc = self.L.eagle_topview_mosaic_device(self._h, d_bgr, n, _ptr(Hs, keep), _ptr(valid, keep), _ptr(recs, keep), C.byref(params), d_acc, int(bool(reset)))
+        else:
+            rc = self.L.eagle_topview_mosaic_frames(self._h, _ptr(frames, keep), n, int(max_staging_bytes), _ptr(Hs, keep), _ptr(valid, keep), _ptr(recs, keep), C.byref(params),
+                                                    d_acc, int(bool(reset)))
+        self._check(rc, "topview_mosaic")
+
+    def topview_mosaic_finish(self, d_acc, params):
+        """-> (mosaic uint8 [Hc, W, 3], cnt uint32 [Hc, W])"""
+        w, h = topview_size(params)
+        pic, cnt = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.uint32)
+        self._check(self.L.eagle_topview_mosaic_finish(self._h, d_acc, C.byref(params), pic.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)), "topview_mosaic_finish")
+        return pic, cnt
+
+    def topview_residuals(self, frames, Hs, valid, params, d_acc, recs=None, n=None, max_staging_bytes=0):
+        """The residual triples of every frame against the finished accumulator -> (res_sum uint64 [n], res_cnt uint32 [n], covered uint32 [n]);
+        frames as topview_mosaic_add takes them."""
+        dev, d_bgr = isinstance(frames, C.c_void_p), frames
+        frames, n, Hs, valid = self._topview_clip("topview_residuals", None if dev else frames, Hs, valid, n)
+        recs = _topview_recs(recs, n)
+        rs, rc_, cv = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        keep = np.zeros(16, np.uint8)
+        if dev:
+            rc = self.L.eagle_topview_residual_device(self._h, d_bgr, n,_ptr(Hs, keep), _ptr(valid, keep), _ptr(recs, keep), C.byref(params), d_acc, _ptr(rs, keep),
+                                                      _ptr(rc_, keep), _ptr(cv, keep))
+        else:
+            rc = self.L.eagle_topview_residual_frames(self._h, _ptr(frames, keep), n, int(max_staging_bytes), _ptr(Hs, keep), _ptr(valid, keep), _ptr(recs, keep),
+                                                      C.byref(params), d_acc, _ptr(rs, keep), _ptr(rc_, keep), _ptr(cv, keep))
+        self._check(rc, "topview_residual")
+        return rs, rc_, cv
 
     # --- annotated output (include/eagle.h, eagle_annotate_*) --------------------------------------------------
     def annotate_device(self, d_bgr, n, recs, d_out, team_mapping=None, fmt="bgr", layout=None):
@@ -2209,6 +2317,85 @@ def op_shots(frames, params=None, cap=None, signatures=True, device=0, **kw):
     if rc:
         raise EagleError(f"eagle_op_shots failed ({rc}): {L.eagle_last_error(None).decode()}")
     return sig, rows, shots[:m.value].copy()
+
+
+def topview_params(scale=8, margin=None, background=0x000000, markings=False, marking_colour=0xFF0000, mask_boxes=False, box_pad=0.0, first=0, step=1, min_count=1):
+    """EagleTopviewParams; margin None: two metres' worth of pixels, at most 64 (the minimap's default).  Colours are B | G << 8 | R << 16; black, red
+    and min_count = 1 are conventional choices."""
+    if margin is None:
+        margin = min(64, 2 * int(scale))
+    return EagleTopviewParams(int(scale), int(margin), int(background), int(bool(markings)), int(marking_colour), int(bool(mask_boxes)), float(box_pad), int(first),
+                              int(step), int(min_count))
+
+
+def topview_size(params):
+    """(W, Hc) of the canvas these parameters give (include/eagle.h eagle_topview_size; no GPU involved)."""
+    w, h = C.c_int(0), C.c_int(0)
+    L = load()
+    rc = L.eagle_topview_size(C.byref(params), C.byref(w), C.byref(h))
+    if rc:
+        raise EagleError(f"eagle_topview_size failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return w.value, h.value
+
+
+def _topview_maps(what, Hs, valid, n):
+    Hs = np.ascontiguousarray(Hs, np.float64).reshape(-1, 9)
+    valid = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+    if len(Hs) != n or len(valid) != n:
+        raise EagleError(f"{what}: {n} frames but {len(Hs)} homographies and {len(valid)} valid flags")
+    return Hs, valid
+
+
+def _topview_recs(recs, n):
+    if recs is None:
+        return None
+    recs = np.ascontiguousarray(recs, RESULT_DTYPE).reshape(-1)
+    if len(recs) != n:
+        raise EagleError(f"topview: {n} frames but {len(recs)} records")
+    return recs
+
+
+def op_topview(frames, Hs, valid, params, boxes=None, mode=TOPVIEW_VIDEO, fmt="bgr", layout=None, out=None, device=0):
+    """The top-view launches on constructed frames (include/eagle.h eagle_op_topview): frames uint8 [n, h, w, 3] of any size, Hs [n, 9], valid [n],
+    boxes a list of n float32 [k, 4] arrays (or None) -> a dict with "video" (mode & TOPVIEW_VIDEO: [n, Hc, W, 3] / [n, 3 Hc / 2, W] when dense, else
+    the flat buffer ``out`` or a zeroed one written in ``layout``), "mosaic" and "cnt" (TOPVIEW_MOSAIC), "res_sum", "res_cnt", "covered"
+    (TOPVIEW_RESIDUAL)."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    if frames.ndim != 4 or frames.shape[3] != 3:
+        raise EagleError(f"op_topview: frames must be [n, h, w, 3] (got {frames.shape})")
+    n, h, w, _ = frames.shape
+    Hs, valid = _topview_maps("op_topview", Hs, valid, n)
+    W, Hc = topview_size(params)
+    keep = np.zeros(16, np.uint8)
+    flat, off = None, None
+    if boxes is not None:
+        if len(boxes) != n:
+            raise EagleError(f"op_topview: {n} frames but {len(boxes)} box lists")
+        per = [np.ascontiguousarray(b, np.float32).reshape(-1, 4) for b in boxes]
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(b) for b in per])]), np.int32)
+        flat = np.ascontiguousarray(np.concatenate(per) if per else np.zeros((0, 4)), np.float32)
+    res = {}
+    lay = _yuv_layout(layout)
+    if mode & TOPVIEW_VIDEO:
+        need = out_span(fmt, Hc, W, lay, n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise EagleError(f"op_topview: out must be a contiguous uint8 array of at least {need} bytes")
+        res["video"] = out
+    if mode & TOPVIEW_MOSAIC:
+        res["mosaic"], res["cnt"] = np.zeros((Hc, W, 3), np.uint8), np.zeros((Hc, W), np.uint32)
+    if mode & TOPVIEW_RESIDUAL:
+        res["res_sum"], res["res_cnt"], res["covered"] = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    g = lambda k: _ptr(res.get(k), keep)
+    rc = L.eagle_op_topview(device, _ptr(frames, keep), n, h, w, _ptr(Hs, keep), _ptr(valid, keep), _ptr(flat, keep), _ptr(off, keep), C.byref(params), int(mode),
+                            _out_pix(fmt), None if lay is None else C.byref(lay), g("video"), g("mosaic"), g("cnt"), g("res_sum"), g("res_cnt"), g("covered"))
+    if rc:
+        raise EagleError(f"eagle_op_topview failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if (mode & TOPVIEW_VIDEO) and lay is None:
+        res["video"] = out.reshape((n, Hc, W, 3) if _out_pix(fmt) == 0 else (n, Hc * 3 // 2, W))
+    return res
 
 
 def op_minimap_hulls(values, frames, columns, team_mapping, params, hull, trail=None, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None,

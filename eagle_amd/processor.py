@@ -54,6 +54,10 @@ class Processor:
         from . import shots as sh
         return sh.find_shots(self.model.handle, frames, fps, pixel_format, **overrides)
 
+    def topview(self, frames, coords_or_records, carry=False, out_format="bgr", **kw):
+        """The frames warped onto the pitch plane with their homographies: see CoordinateModel.topview and eagle_amd/topview.py."""
+        return self.model.topview(frames, coords_or_records, carry, out_format, **kw)
+
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The annotated frames of a clip (the reference's annotated video, main.py:43-81), drawn on the GPU: see CoordinateModel.annotate.
         ``table``: draw the processed table (process_data above) instead of the raw records."""

@@ -923,6 +923,89 @@ int eagle_shots_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t row_st
 int eagle_op_shots(int device, const uint8_t* bgr, int n, int h, int w, const EagleShotParams* p, EagleShotFrame* frames_out, EagleShot* shots_out, int cap, int* n_shots,
                    uint32_t* signatures_out);
 
+/* ---- top view: the frames warped onto the pitch plane, their mean (a mosaic of the pitch without the players) and per frame the distance of its
+ * warp from that mean (own specification: tests/topview_ref.py defines every output byte) ----
+ * What shows whether a frame's homography H (row-major, image -> pitch) puts the painted lines where the pitch model has them, and which frames of a
+ * clip have an H that jumped.  Input: n dense BGR frames [h][w][3], Hs [n][9], valid [n].
+ *   CANVAS   the minimap's: scale S even in 2 .. 32, margin M even in 0 .. 64, W = 105 S + 2 M, Hc = 68 S + 2 M.  Pixel (X, Y) stands for the pitch
+ *            point x = (X - M) / S, y = 68 - (Y - M) / S (float64, one operation each), so the minimap's marking mask fits without a shift.
+ *   MAP      per frame on the host, float64, every product and sum a single operation: A = adj(H), the cofactors A0 = h4 h8 - h5 h7, A1 = h2 h7 - h1 h8,
+ *            A2 = h1 h5 - h2 h4, A3 = h5 h6 - h3 h8, A4 = h0 h8 - h2 h6, A5 = h2 h3 - h0 h5, A6 = h3 h7 - h4 h6, A7 = h1 h6 - h0 h7, A8 = h0 h4 - h1 h3;
+ *            det = (h0 A0 + h1 A3) + h2 A6; sb = (h6 (w - 1) / 2 + h7 (h - 1)) + h8, the projective weight of the frame's bottom-centre pixel.  The
+ *            frame has NO MAP when valid is 0, when any of H, A, det, sb is not finite, when det == 0 or sb == 0.  Else G = A when det and sb have
+ *            the same sign, G = -A otherwise: exactly the pitch points on the same side of the horizon as the bottom of the picture are kept, and H
+ *            and c H (c != 0) give the same bytes.
+ *   SAMPLE   u' = ((G0 x) + (G1 y)) + G2, v' and w' likewise from rows 1 and 2; u = u' / w', v = v' / w'; tu = u 256 + 0.5, tv = v 256 + 0.5.  The
+ *            pixel is COVERED iff w' > 0, 0 <= tu < 256 (w - 1) + 1 and 0 <= tv < 256 (h - 1) + 1 (NaN fails).  Then U = floor(tu), x0 = U >> 8,
+ *            fx = U & 255, x1 = min(x0 + 1, w - 1), likewise in y, and each channel is ((256 - fx)(256 - fy) p00 + fx (256 - fy) p10 +
+ *            (256 - fx) fy p01 + fx fy p11 + 32768) >> 16.  Pixel centres lie at integers; no parity with cv2.warpPerspective is claimed.
+ *   VIDEO    covered pixels get the sample, the others `background`; with `markings` the minimap's marking mask of (S, M) is painted on top in
+ *            `marking_colour`.  BGR, NV12 or I420 in the caller's layout, as eagle_annotate_* (same conversion, same layout rules).
+ *   MOSAIC   over the frames first, first + step, ...: u32 sums sumB, sumG, sumR and cnt per canvas pixel (the accumulator, u32 [Hc][W][4]).  A frame adds
+ *            its sample iff the pixel is covered and, with mask_boxes, (u, v) lies in no box det[0 .. n_det) of the frame's record (any class):
+ *            x1 - box_pad <= u <= x2 + box_pad and y1 - box_pad <= v <= y2 + box_pad in float64, the float boxes widened exactly.  The picture:
+ *            channel = (2 sum + cnt) / (2 cnt) (integer division) where cnt >= min_count, `background` elsewhere, markings on request; dense BGR
+ *            [Hc][W][3], and cnt as u32 [Hc][W].  At most EAGLE_TOPVIEW_MAX_FRAMES frames, below which the sums cannot overflow.
+ *   RESIDUAL for every frame f of the clip (first and step do not matter here): over the pixels f would add to the mosaic (covered, not masked)
+ *            where the accumulator has cnt >= min_count, res_sum[f] = the sum of |sample - mosaic channel| over B, G, R and res_cnt[f] their number;
+ *            covered[f] = the covered pixels with M <= X < M + 105 S and M <= Y < M + 68 S.  The frame's own sample is part of the mosaic.
+ * All accumulation is in integers: no result depends on how the kernels split the work, two runs give the same bytes.  Limits: bilinear only, no
+ * anti-aliasing where the view is minified, no lens distortion; a plain mean, not a median, so a player who stands still through the clip and is not
+ * box-masked leaves a ghost; nothing is validated on real footage.  Launches (topview.hip) on the handle's main stream; device memory is allocated
+ * per call and freed (the marking mask is the handle's, shared with the minimap); records, staging buffers and graphs of the handle are not involved.
+ * EAGLE_E_INVALID with a message, before any launch: NULL pointers (parameters, outputs; frames, Hs, valid with n > 0), scale or margin outside the
+ * ranges above, step < 1, first < 0, min_count < 1, box_pad negative or not finite, a colour above 0xffffff, non-zero reserved words, n < 0, n above
+ * EAGLE_TOPVIEW_MAX_FRAMES for a mosaic, mask_boxes without records (or with an n_det outside 0 .. EAGLE_MAX_DET), every layout error eagle_annotate_*
+ * refuses, a negative max_staging_bytes; in the operator entry a frame side outside 1 .. 16384 or an unknown mode.  n == 0 succeeds and writes nothing;
+ * a mosaic of 0 frames is all background with cnt = 0. */
+#define EAGLE_TOPVIEW_MAX_FRAMES (1 << 23)
+#define EAGLE_TOPVIEW_VIDEO 1          /* eagle_op_topview: mode bits */
+#define EAGLE_TOPVIEW_MOSAIC 2
+#define EAGLE_TOPVIEW_RESIDUAL 4
+typedef struct EagleTopviewParams {
+    int32_t scale, margin;         /* S, M */
+    uint32_t background;           /* B | G << 8 | R << 16 (conventionally black) */
+    int32_t markings;              /* != 0: paint the marking mask */
+    uint32_t marking_colour;       /* B | G << 8 | R << 16 (conventionally red, 0xff0000) */
+    int32_t mask_boxes;            /* != 0: mosaic and residual leave out the samples inside the frame's detection boxes */
+    double box_pad;                /* pixels, >= 0 */
+    int32_t first, step;           /* the mosaic's frames: first, first + step, ... */
+    int32_t min_count;             /* >= 1 (conventionally 1) */
+    int32_t reserved[3];           /* 0 */
+} EagleTopviewParams;              /* 56 bytes */
+int eagle_topview_size(const EagleTopviewParams* p, int* w, int* h);
+/* n frames of the handle's size, dense, resident in HBM -> n pictures at d_out (device) in out_format / out_layout; returns when they are complete.
+ * Hs [n][9] and valid [n] are host memory. */
+int eagle_topview_device_frames(EagleHandle* h, const uint8_t* d_bgr, int n, const double* Hs, const uint8_t* valid, const EagleTopviewParams* p, int out_format,
+                                const EagleYuvLayout* out_layout, void* d_out);
+/* Same, dense frames in host memory -> pictures in host memory, in passes of what 64 MB of device staging hold (pinned or pageable destination, as
+ * eagle_minimap_frames). */
+int eagle_topview_frames(EagleHandle* h, const uint8_t* bgr, int n, const double* Hs, const uint8_t* valid, const EagleTopviewParams* p, int out_format,
+                         const EagleYuvLayout* out_layout, uint8_t* out);
+/* The frames first, first + step, ... of a clip resident in HBM are added to the accumulator d_acc (device, u32 [Hc][W][4], eagle_device_alloc; reset != 0:
+ * zeroed first, so that several clips or calls can share one).  recs (host, [n]): NULL unless mask_boxes.  Returns when the sums are complete. */
+int eagle_topview_mosaic_device(EagleHandle* h, const uint8_t* d_bgr, int n, const double* Hs, const uint8_t* valid, const EagleFrameResult* recs,
+                                const EagleTopviewParams* p, uint32_t* d_acc, int reset);
+/* The accumulator -> the mosaic picture bgr_out [Hc][W][3] and cnt_out u32 [Hc][W] (host). */
+int eagle_topview_mosaic_finish(EagleHandle* h, const uint32_t* d_acc, const EagleTopviewParams* p, uint8_t* bgr_out, uint32_t* cnt_out);
+/* The residual triples of all n frames against the finished accumulator -> res_sum, res_cnt, covered (host, [n]). */
+int eagle_topview_residual_device(EagleHandle* h, const uint8_t* d_bgr, int n, const double* Hs, const uint8_t* valid, const EagleFrameResult* recs,
+                                  const EagleTopviewParams* p, const uint32_t* d_acc, uint64_t* res_sum, uint32_t* res_cnt, uint32_t* covered);
+/* The last two steps for a clip in host memory (dense [n][h][w][3]): the frames a step needs are uploaded in passes of what max_staging_bytes (0: 64 MB;
+ * always at least one frame) of device staging hold; the accumulator stays resident across the passes, the clip is read once per step, and the result
+ * does not depend on the size of a pass. */
+int eagle_topview_mosaic_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t max_staging_bytes, const double* Hs, const uint8_t* valid, const EagleFrameResult* recs,
+                                const EagleTopviewParams* p, uint32_t* d_acc, int reset);
+int eagle_topview_residual_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t max_staging_bytes, const double* Hs, const uint8_t* valid, const EagleFrameResult* recs,
+                                  const EagleTopviewParams* p, const uint32_t* d_acc, uint64_t* res_sum, uint32_t* res_cnt, uint32_t* covered);
+/* Operator entry (host buffers in / out, no handle): dense frames of any h x w within 1 .. 16384 per side.  boxes [box_off[n]][4] = x1, y1, x2, y2 and
+ * box_off [n + 1] (ascending from 0, at most EAGLE_MAX_DET per frame) stand for the records; NULL unless mask_boxes.  mode: EAGLE_TOPVIEW_VIDEO (out, in
+ * out_format / out_layout) | _MOSAIC (mosaic_out [Hc][W][3], cnt_out [Hc][W]) | _RESIDUAL (res_sum, res_cnt, covered [n], against the mosaic of this
+ * call's frames); outputs of modes not asked for may be NULL. */
+int eagle_op_topview(int device, const uint8_t* bgr, int n, int h, int w, const double* Hs, const uint8_t* valid, const float* boxes, const int32_t* box_off,
+                     const EagleTopviewParams* p, int mode, int out_format, const EagleYuvLayout* out_layout, uint8_t* out, uint8_t* mosaic_out, uint32_t* cnt_out,
+                     uint64_t* res_sum, uint32_t* res_cnt, uint32_t* covered);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
