@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -165,6 +165,17 @@ def main(argv=None):
     ap.add_argument("--space-radius", type=float, default=None, metavar="M",
                     help="with --space: the marking radius in metres, > 0 and <= 1024 (default 3, a conventional choice, not fitted to data)")
     ap.add_argument("--space-rows", action="store_true", help="with --space: also write the sites of every kept frame into space.json")
+    ap.add_argument("--offside", action="store_true",
+                    help="with --processed: also write <out>/offside.json, the offside line of each team in every kept frame (the deepest of the second-last opponent, "
+                         "the halfway line and the ball), who was beyond it and by how much, per id how often; with --possession also a verdict per pass: was the "
+                         "receiver onside, close or offside when the ball was played (eagle_amd/offside.py)")
+    ap.add_argument("--offside-direction", choices=["auto", "right", "left"], default=None,
+                    help="with --offside: the way the team with value 0 attacks, towards x = 105 (right) or x = 0 (left); auto (the default) votes over the frames")
+    ap.add_argument("--offside-tolerance", type=float, default=None, metavar="M",
+                    help="with --offside: a receiver within M metres of the line is `close`; >= 0 and <= 1024 (default 0.5, a conventional choice, not fitted to data)")
+    ap.add_argument("--offside-no-assumed-keeper", action="store_true",
+                    help="with --offside: do not take a goalkeeper the camera does not see to stand on his goal line (the line is then the second-last opponent seen)")
+    ap.add_argument("--offside-rows", action="store_true", help="with --offside: also write the line and the margins of every kept frame into offside.json")
     ap.add_argument("--space-map", action="store_true",
                     help="with --space: also write <out>/space.npy (uint8 [rows, 68 R, 105 R]), per cell the index of its owner among the frame's sites, 255 on a skipped frame")
     ap.add_argument("--shots", action="store_true",
@@ -259,6 +270,14 @@ def main(argv=None):
         a.space_set = (1 if a.space_grid is None else a.space_grid, 3.0 if a.space_radius is None else a.space_radius)
         if not (a.space_set[1] == a.space_set[1] and 0.0 < a.space_set[1] <= 1024.0):
             ap.error("--space-radius: M must be > 0 and <= 1024 metres")
+    if a.offside and not a.processed:
+        ap.error("--offside works on the processed table: it needs --processed")
+    if not a.offside and (a.offside_rows or a.offside_no_assumed_keeper or a.offside_direction is not None or a.offside_tolerance is not None):
+        ap.error("--offside-direction, --offside-tolerance, --offside-no-assumed-keeper and --offside-rows set up the offside report: they need --offside")
+    if a.offside:
+        a.offside_set = (a.offside_direction or "auto", 0.5 if a.offside_tolerance is None else a.offside_tolerance)
+        if not 0.0 <= a.offside_set[1] <= 1024.0:
+            ap.error("--offside-tolerance: M must be >= 0 and <= 1024 metres")
     if a.roles and not a.processed:
         ap.error("--roles works on the processed table: it needs --processed")
     if not a.roles and (a.roles_rows or any(v is not None for v in (a.roles_count, a.roles_min_present, a.roles_iterations, a.roles_lines))):
@@ -456,6 +475,10 @@ def main(argv=None):
                 json.dump(spc.to_json(spc.space(model.handle, table, a.space_set[0], True, a.space_set[1], per_row=a.space_rows)), f)
             if a.space_map:
                 np.save(os.path.join(a.out, "space.npy"), model.handle.space_grids(table, lib.space_params(a.space_set[0], 1, a.space_set[1])))
+        if a.offside:
+            from . import offside as ofs
+            with open(os.path.join(a.out, "offside.json"), "w") as f:
+                json.dump(ofs.to_json(ofs.offside(model.handle, table, a.offside_set[0], a.offside_set[1], not a.offside_no_assumed_keeper, per_row=a.offside_rows)), f)
         entities = [c for c, k in enumerate(table.columns) if not k["video"] and int(k["kind"]) in (lib.POST_PLAYER, lib.POST_GOALKEEPER, lib.POST_BALL)]
         if a.trajectory is not None:
             from . import minimap as mm

@@ -640,7 +640,7 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
 void eagle_post_free(EaglePostTable* t)
 {
     if (!t) return;
-    if (t->d_values || t->d_vel || t->d_poss || t->d_occ || t->d_shape || t->d_phys || t->d_roles || t->d_space) (void)hipSetDevice(t->h->cfg.device);
+    if (t->d_values || t->d_vel || t->d_poss || t->d_occ || t->d_shape || t->d_phys || t->d_roles || t->d_space || t->d_offside) (void)hipSetDevice(t->h->cfg.device);
     if (t->d_values) (void)hipFree(t->d_values);
     if (t->d_vel) (void)hipFree(t->d_vel);
     if (t->d_poss) (void)hipFree(t->d_poss);
@@ -649,6 +649,7 @@ void eagle_post_free(EaglePostTable* t)
     if (t->d_phys) (void)hipFree(t->d_phys);
     if (t->d_roles) (void)hipFree(t->d_roles);
     if (t->d_space) (void)hipFree(t->d_space);
+    if (t->d_offside) (void)hipFree(t->d_offside);
     delete t;
 }
 

@@ -309,6 +309,9 @@ struct EaglePostTable {
     bool has_roles = false;
     void* d_space = nullptr;             // space (eagle_post_space): EagleSpaceRow [rows] | EagleSpaceSite [rows][32] | EagleSpaceTotals [space_members], each from a
     int space_members = 0;               // 256-byte boundary; nullptr before the first call, resident until eagle_post_free
+    void* d_offside = nullptr;           // offside (eagle_post_offside): EagleOffsideRow [rows][2] | margins i32 [offside_members][rows] | EagleOffsideTotals
+    int offside_members = 0;             // [offside_members] | EagleOffsideClip | EagleOffsideEvent [offside_events], each from a 256-byte boundary; nullptr
+    int offside_events = 0;              // before the first call, resident until eagle_post_free
 };
 
 namespace eagle {

@@ -126,6 +126,33 @@ SPACE_TOTALS_DTYPE = np.dtype([("cells", "<i8", 3), ("within_sum", "<i8"), ("col
 assert C.sizeof(EagleSpaceParams) == 32 and (SPACE_ROW_DTYPE.itemsize, SPACE_SITE_DTYPE.itemsize, SPACE_TOTALS_DTYPE.itemsize) == (64, 48, 64)       # space.hip asserts them too
 
 
+class EagleOffsideParams(C.Structure):
+    """include/eagle.h EagleOffsideParams: which way group 0 attacks (OFFSIDE_DIR_*), whether an unseen keeper is taken to stand on the goal line, the
+    tolerance of a verdict in metres."""
+    _fields_ = [("direction", C.c_int32), ("assume_keeper", C.c_int32), ("tolerance", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+OFFSIDE_DIR_AUTO, OFFSIDE_DIR_RIGHT, OFFSIDE_DIR_LEFT = 0, 1, 2                # include/eagle.h EAGLE_OFFSIDE_*
+OFFSIDE_DIR_NAMES = ("unresolved", "right", "left")
+OFFSIDE_OK, OFFSIDE_NO_DIRECTION, OFFSIDE_TOO_FEW = 0, 1, 2
+OFFSIDE_STATUS_NAMES = ("ok", "no_direction", "too_few")
+OFFSIDE_KEEPER_ASSUMED, OFFSIDE_BY_DEFENDER, OFFSIDE_BY_BALL, OFFSIDE_BY_HALF, OFFSIDE_NO_BALL = 1, 2, 4, 8, 16
+OFFSIDE_EV_OK, OFFSIDE_EV_NOT_PASS, OFFSIDE_EV_NO_RECEIVER, OFFSIDE_EV_NO_LINE = 0, 1, 2, 3
+OFFSIDE_EV_STATUS_NAMES = ("ok", "not_pass", "no_receiver", "no_line")
+OFFSIDE_ONSIDE, OFFSIDE_CLOSE, OFFSIDE_OFFSIDE = 1, 2, 3
+OFFSIDE_VERDICT_NAMES = (None, "onside", "close", "offside")
+OFFSIDE_NONE, OFFSIDE_U_MAX, OFFSIDE_U_HALF = -2 ** 31, 107520, 53760
+OFFSIDE_ROW_DTYPE = np.dtype([("status", "<i4"), ("flags", "<i4"), ("line_qx", "<i4"), ("second_col", "<i4"), ("n_att", "<i4"), ("n_def", "<i4"),
+                              ("keepers_seen", "<i4"), ("n_off", "<i4"), ("max_margin", "<i4"), ("max_col", "<i4"), ("reserved", "<i4", 2)])          # EagleOffsideRow (48 bytes)
+OFFSIDE_TOTALS_DTYPE = np.dtype([("col", "<i4"), ("group", "<i4"), ("rows", "<i4"), ("off_rows", "<i4"), ("max_margin", "<i4"), ("reserved", "<i4", 3)])  # EagleOffsideTotals (32 bytes)
+OFFSIDE_EVENT_DTYPE = np.dtype([("status", "<i4"), ("verdict", "<i4"), ("margin", "<i4"), ("line_qx", "<i4"), ("n_off", "<i4"), ("bypassed", "<i4"),
+                                ("group", "<i4"), ("reserved", "<i4")])                                                                                 # EagleOffsideEvent (32 bytes)
+OFFSIDE_CLIP_DTYPE = np.dtype([("direction", "<i4"), ("requested", "<i4"), ("neg", "<i4"), ("pos", "<i4"), ("zero", "<i4"), ("n_members", "<i4", 2),
+                               ("n_keepers", "<i4")])                                                                                                   # EagleOffsideClip (32 bytes)
+assert C.sizeof(EagleOffsideParams) == 32 and (OFFSIDE_ROW_DTYPE.itemsize, OFFSIDE_TOTALS_DTYPE.itemsize, OFFSIDE_EVENT_DTYPE.itemsize,
+                                               OFFSIDE_CLIP_DTYPE.itemsize) == (48, 32, 32, 32)                                                      # offside.hip asserts them too
+
+
 class EagleShotParams(C.Structure):
     """include/eagle.h EagleShotParams: cut, low and grass_thr in 1 / 65536, the window W in frames, the least length of a usable shot in frames."""
     _fields_ = [("cut", C.c_int32), ("low", C.c_int32), ("grass_thr", C.c_int32), ("window", C.c_int32), ("min_len", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -394,6 +421,12 @@ def load():
     L.eagle_space_device_grids.argtypes = [vp, vp, i32, i32, sp, vp]
     L.eagle_space_grids.argtypes = [vp, vp, i32, i32, sp, vp]
     L.eagle_op_space.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, sp, i32, i32, vp, vp, vp, vp]
+    ofp = C.POINTER(EagleOffsideParams)
+    L.eagle_post_offside.argtypes = [vp, vp, ofp]
+    L.eagle_post_offside_values.argtypes = [vp, vp, vp, vp, vp]
+    L.eagle_post_offside_events.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_post_device_offside.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.eagle_op_offside.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, ofp, vp, i32, vp, vp, vp, vp, vp]
     shp = C.POINTER(EagleShotParams)
     L.eagle_shots_device_frames.argtypes = [vp, vp, i32, shp, vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_shots_frames.argtypes = [vp, vp, i32, i64, i64, i64, shp, vp, vp, i32, C.POINTER(C.c_int)]
@@ -452,7 +485,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_device_team_shape", "eagle_minimap_set_hulls", "eagle_op_team_shape", "eagle_op_minimap_hulls", "eagle_post_physical", "eagle_post_physical_values",
            "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
            "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
-           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
+           "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_post_offside", "eagle_post_offside_values", "eagle_post_offside_events",
+           "eagle_post_device_offside", "eagle_op_offside", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
            "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
            "eagle_op_topview", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
@@ -1140,6 +1174,36 @@ class Handle:
         """space_grids into device memory: n maps [n][gh][gw] at ``d_grid``."""
         n = len(table.rows) - row0 if n is None else n
         self._check(self.L.eagle_space_device_grids(self._h, table._t, int(row0), int(n), C.byref(params), d_grid), "space_device_grids")
+
+    # --- offside (include/eagle.h, eagle_post_offside) ----------------------------------------------------------------------------
+    def offside(self, table, params=None):
+        """The offside lines and margins of a PostTable of this handle (it needs a team mapping), computed on the GPU and kept with the table (a second
+        call replaces the first; a refused one leaves it) -> (OFFSIDE_ROW_DTYPE [rows, 2], margins int32 [members, rows], OFFSIDE_TOTALS_DTYPE
+        [members], OFFSIDE_CLIP_DTYPE [1]); params offside_params(...).  With a possession result on the table the passes get their verdicts
+        (offside_events).  eagle_amd.offside derives metres."""
+        p = offside_params() if params is None else params
+        self._check(self.L.eagle_post_offside(self._h, table._t, C.byref(p)), "post_offside")
+        nm = self.offside_device(table)[5]
+        rows = len(table.rows)
+        rec, mg, totals, clip = np.zeros((rows, 2), OFFSIDE_ROW_DTYPE), np.zeros((nm, rows), np.int32), np.zeros(nm, OFFSIDE_TOTALS_DTYPE), np.zeros(1, OFFSIDE_CLIP_DTYPE)
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_post_offside_values(table._t, _ptr(rec, keep), _ptr(mg, keep), _ptr(totals, keep), _ptr(clip, keep)), "post_offside_values")
+        return rec, mg, totals, clip
+
+    def offside_events(self, table):
+        """The event records of the table's last offside result (OFFSIDE_EVENT_DTYPE, one per possession event, in event order; empty before it)."""
+        n = C.c_int(0)
+        self._check(self.L.eagle_post_offside_events(table._t, None, 0, C.byref(n)), "post_offside_events")
+        ev = np.zeros(n.value, OFFSIDE_EVENT_DTYPE)
+        self._check(self.L.eagle_post_offside_events(table._t, _ptr(ev, np.zeros(4, np.float64)), n.value, C.byref(n)), "post_offside_events")
+        return ev
+
+    def offside_device(self, table):
+        """(records, margins, totals, clip record, event records, members, events) in HBM ((None,) * 5 + (0, 0) before the first offside call)."""
+        d = [C.c_void_p() for _ in range(5)]
+        nm, ne = C.c_int(0), C.c_int(0)
+        self._check(self.L.eagle_post_device_offside(table._t, *[C.byref(x) for x in d], C.byref(nm), C.byref(ne)), "post_device_offside")
+        return tuple(x.value for x in d) + (nm.value, ne.value)
 
     def set_hulls(self, table, half_width=1):
         """The half width (pixels, 1 .. 8; or an EagleHullParams) the minimap's hull layer (MM_HULLS) of this table is drawn with; None: forget it."""
@@ -2283,6 +2347,39 @@ def op_space(values, columns, team_mapping, params=None, row0=0, n=0, device=0):
     if rc:
         raise EagleError(f"eagle_op_space failed ({rc}): {L.eagle_last_error(None).decode()}")
     return rec, sites, totals, grid
+
+
+def offside_params(direction=OFFSIDE_DIR_AUTO, assume_keeper=1, tolerance=0.5):
+    """EagleOffsideParams.  A tolerance of 0.5 m is a conventional choice, not fitted to data."""
+    return EagleOffsideParams(int(direction), int(assume_keeper), float(tolerance))
+
+
+def op_offside(values, columns, team_mapping, params=None, events=None, frames=None, device=0):
+    """The offside launches on a constructed table (include/eagle.h eagle_op_offside): values float64 [cols][rows][2], columns [(kind, id, video)],
+    team_mapping {id: team} or (id, team) pairs of which the first for an id counts, events EVENT_DTYPE or None -> (OFFSIDE_ROW_DTYPE [rows, 2], margins
+    int32 [members, rows], OFFSIDE_TOTALS_DTYPE [members], OFFSIDE_CLIP_DTYPE [1], OFFSIDE_EVENT_DTYPE [events])."""
+    L = load()
+    values, columns = _table_args("op_offside", values, columns)
+    cols, rows = values.shape[:2]
+    pairs = None if team_mapping is None else list(team_mapping.items() if isinstance(team_mapping, dict) else team_mapping)
+    ids = None if pairs is None else np.ascontiguousarray([int(k) for k, _ in pairs], np.int32)
+    vals = None if pairs is None else np.ascontiguousarray([int(v) for _, v in pairs], np.int32)
+    first = {}
+    for i, v in pairs or ():
+        first.setdefault(int(i), int(v))
+    nm = sum(1 for k in columns if not k["video"] and int(k["kind"]) == POST_PLAYER and first.get(int(k["id"]), -1) >= 0)
+    p = offside_params() if params is None else params
+    events = np.zeros(0, EVENT_DTYPE) if events is None else np.ascontiguousarray(events, EVENT_DTYPE)
+    frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
+    rec, mg, totals, clip = np.zeros((rows, 2), OFFSIDE_ROW_DTYPE), np.zeros((nm, rows), np.int32), np.zeros(nm, OFFSIDE_TOTALS_DTYPE), np.zeros(1, OFFSIDE_CLIP_DTYPE)
+    ev = np.zeros(len(events), OFFSIDE_EVENT_DTYPE)
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_offside(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep),
+                            0 if pairs is None else len(pairs), C.byref(p), _ptr(events, keep), len(events), _ptr(rec, keep), _ptr(mg, keep), _ptr(totals, keep),
+                            _ptr(clip, keep), _ptr(ev, keep))
+    if rc:
+        raise EagleError(f"eagle_op_offside failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return rec, mg, totals, clip, ev
 
 
 def shot_params(cut=None, low=None, grass_thr=None, window=None, min_len=None, fps=25):

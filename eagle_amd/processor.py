@@ -134,3 +134,10 @@ class Processor:
         and pass: see eagle_amd/space.py."""
         from . import space as sp
         return sp.space(self.model.handle, table, cells_per_metre, goalkeepers, radius, per_row)
+
+    def offside(self, table, direction="auto", tolerance=0.5, assume_keeper=True, per_row=False):
+        """Where the offside line stood for each team in every kept frame of a processed table, who was beyond it and by how much, how often per id; with
+        a possession result on the table also, per pass, whether the receiver was onside, close or offside when the ball was played: see
+        eagle_amd/offside.py."""
+        from . import offside as of
+        return of.offside(self.model.handle, table, direction, tolerance, assume_keeper, per_row)

@@ -850,6 +850,130 @@ int eagle_space_grids(EagleHandle* h, EaglePostTable* t, int row0, int n, const 
 int eagle_op_space(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals, int n_team,
                    const EagleSpaceParams* p, int row0, int n, EagleSpaceRow* rows_out, EagleSpaceSite* sites_out, EagleSpaceTotals* totals_out, uint8_t* grid);
 
+/* ---- offside: per row and attacking team the offside line and every attacker's margin beyond it, per pass event a verdict about the receiver (own
+ * specification: tests/offside_ref.py defines every output bit) ----
+ * GROUPS, MEMBERS, PRESENT and the quantisation q are the team shape's (above): groups 0 and 1 hold the Player pitch columns with a non-negative mapping
+ * entry (the first entry for an id counts), a member is present when x and y are finite and |x|, |y| <= 1024 m, q = floor(v * 1024 + 0.5) in float64; a
+ * mapping is required.  Integers only behind that one step.
+ *   KEEPERS    the Goalkeeper pitch columns, mapped or not.
+ *   BALL       the one Ball pitch column; absent when the table has none or carries EAGLE_POST_NO_BALL, else present on a row by the members' rule.
+ *   DIRECTION  EagleOffsideParams::direction: RIGHT, group 0 attacks towards x = 105; LEFT, towards x = 0; AUTO, a vote over the rows on which both
+ *            groups have a present member: s_r = sign(sum_x0 n1 - sum_x1 n0) (int64, the products stay below 2^45), neg = #{s_r < 0}, pos = #{s_r > 0},
+ *            zero = #{s_r == 0}; neg > pos: group 0 defends the left and attacks RIGHT; pos > neg: LEFT; else unresolved: every row has status
+ *            NO_DIRECTION and nothing else is computed (rows, margins, totals and events are as on any row that is not OK).  The votes are counted
+ *            for a forced direction too.  The clip record holds the resolved direction (0: unresolved), the requested one and the counts.
+ *   DEPTH      for the attacking group a with the defenders d = 1 - a: u = qx when a attacks right, else u = 107520 - qx (105 * 1024).  Greater u is
+ *            nearer the defenders' goal line; U_HALF = 53760.
+ *   DEFENDERS  of a row: the present members of d and every present keeper with u > U_HALF (a keeper "seen"; one exactly on the halfway line is
+ *            nobody's), K of them (n_def).
+ *   SECOND     a keeper was seen or assume_keeper == 0: the second-largest of the K depths as a multiset (two level defenders: second == largest);
+ *            K < 2 gives status TOO_FEW.  No keeper seen and assume_keeper != 0 (the default): the keeper is taken to stand on the goal line behind
+ *            everyone, second = the largest depth, K < 1 gives TOO_FEW, flag KEEPER_ASSUMED.  second_col = the earliest table column among the
+ *            defenders at depth second.
+ *   LINE       line = max(second, U_HALF, u_ball), the ball's term only when the ball is present on the row (else flag NO_BALL).  One of the flags
+ *            BY_DEFENDER, BY_BALL, BY_HALF names the term that set it, on a tie in that order.  line_qx is the line as a pitch coordinate: u mapped
+ *            back to qx.
+ *   MARGINS    every present member of a: m = u - line (int32; |u| < 2^22), in an offside position iff m > 0, level is onside.  An absent member and
+ *            every member on a row that is not OK: EAGLE_OFFSIDE_NONE.  The row record holds n_att (the present members of a), n_def, n_off = #{m >
+ *            0}, max_margin = the greatest margin and max_col = the earliest column attaining it (NONE and -1 without an attacker).  A row that is
+ *            TOO_FEW still holds n_att, n_def and keepers_seen; everything else of a row that is not OK is 0 / -1 / NONE.
+ *   TOTALS     per member, in group order 0, 1 and by column inside a group, over the OK rows (of its group's record) on which it is present: rows,
+ *            off_rows = #{m > 0}, max_margin (NONE when rows == 0).
+ *   EVENTS     one record per event handed in (the table's possession events; none without a possession result), in their order.  status NOT_PASS:
+ *            kind != EAGLE_EVENT_PASS; NO_RECEIVER: to_col is no member of group 0 or 1; NO_LINE: the record of the receiver's group at release_row
+ *            is not OK, or the receiver is absent there; else OK: group = the receiver's, margin = its margin at release_row, line_qx and n_off
+ *            that record's, verdict with tq = floor(tolerance * 1024 + 0.5): OFFSIDE when m > tq, else CLOSE when m > -tq, else ONSIDE (tolerance 0:
+ *            never CLOSE); bypassed = the members of d present at release_row and at receive_row with u(release) > u_ball(release) and u(receive)
+ *            <= u_ball(receive), -1 when the ball is absent at either row.  A record that is not OK: verdict 0, margin NONE, line_qx 0, n_off 0,
+ *            bypassed -1, group = the receiver's for NO_LINE and -1 otherwise.
+ * The default tolerance of 0.5 m is a conventional choice, not fitted to data.  Four launches (offside.hip: vote, rows, totals, events) on the handle's
+ * main stream read the table where eagle_postprocess left it; what the call allocates is held against the table's max_bytes before the first launch.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output and an earlier result alone: NULL table or parameters, a table without a
+ * mapping, an unknown direction, a tolerance that is not finite or outside [0, 1024], non-zero reserved words, more than EAGLE_SHAPE_MAX_MEMBERS members
+ * and keepers, more than one Ball pitch column, a column of unknown kind, a pass event whose release_row or receive_row lies outside the table, a
+ * device-memory need beyond the budget.  rows == 0 is success and writes nothing. */
+#define EAGLE_OFFSIDE_DIR_AUTO 0   /* EagleOffsideParams::direction, EagleOffsideClip::direction (there 0: unresolved) */
+#define EAGLE_OFFSIDE_DIR_RIGHT 1  /* group 0 attacks towards x = 105 */
+#define EAGLE_OFFSIDE_DIR_LEFT 2   /* group 0 attacks towards x = 0 */
+#define EAGLE_OFFSIDE_OK 0         /* EagleOffsideRow::status */
+#define EAGLE_OFFSIDE_NO_DIRECTION 1
+#define EAGLE_OFFSIDE_TOO_FEW 2
+#define EAGLE_OFFSIDE_KEEPER_ASSUMED 1     /* EagleOffsideRow::flags */
+#define EAGLE_OFFSIDE_BY_DEFENDER 2
+#define EAGLE_OFFSIDE_BY_BALL 4
+#define EAGLE_OFFSIDE_BY_HALF 8
+#define EAGLE_OFFSIDE_NO_BALL 16
+#define EAGLE_OFFSIDE_EV_OK 0      /* EagleOffsideEvent::status */
+#define EAGLE_OFFSIDE_EV_NOT_PASS 1
+#define EAGLE_OFFSIDE_EV_NO_RECEIVER 2
+#define EAGLE_OFFSIDE_EV_NO_LINE 3
+#define EAGLE_OFFSIDE_ONSIDE 1     /* EagleOffsideEvent::verdict; 0: none */
+#define EAGLE_OFFSIDE_CLOSE 2
+#define EAGLE_OFFSIDE_OFFSIDE 3
+#define EAGLE_OFFSIDE_NONE (-2147483647 - 1)       /* no margin: INT32_MIN */
+#define EAGLE_OFFSIDE_U_MAX 107520 /* 105 * 1024 */
+#define EAGLE_OFFSIDE_U_HALF 53760
+typedef struct EagleOffsideParams {
+    int32_t direction;             /* EAGLE_OFFSIDE_DIR_* (AUTO) */
+    int32_t assume_keeper;         /* != 0: an unseen keeper stands on the goal line (1) */
+    double tolerance;              /* metres: finite, >= 0, <= 1024 (0.5) */
+    int32_t reserved[4];           /* 0 */
+} EagleOffsideParams;              /* 32 bytes */
+typedef struct EagleOffsideRow {
+    int32_t status;                /* EAGLE_OFFSIDE_OK .. EAGLE_OFFSIDE_TOO_FEW */
+    int32_t flags;                 /* EAGLE_OFFSIDE_KEEPER_ASSUMED .. EAGLE_OFFSIDE_NO_BALL; 0 unless OK */
+    int32_t line_qx;               /* the line as a pitch coordinate, q; 0 unless OK */
+    int32_t second_col;            /* the second-last opponent's table column; -1 unless OK */
+    int32_t n_att, n_def;          /* present attackers; defenders K, seen keepers included; 0 on NO_DIRECTION */
+    int32_t keepers_seen;
+    int32_t n_off;                 /* attackers with m > 0 */
+    int32_t max_margin;            /* EAGLE_OFFSIDE_NONE without an attacker or unless OK */
+    int32_t max_col;               /* the earliest column attaining it, or -1 */
+    int32_t reserved[2];           /* 0 */
+} EagleOffsideRow;                 /* 48 bytes */
+typedef struct EagleOffsideTotals {
+    int32_t col, group;            /* the member's table column and group */
+    int32_t rows;                  /* OK rows on which it is present */
+    int32_t off_rows;              /* ... with m > 0 */
+    int32_t max_margin;            /* EAGLE_OFFSIDE_NONE when rows == 0 */
+    int32_t reserved[3];           /* 0 */
+} EagleOffsideTotals;              /* 32 bytes */
+typedef struct EagleOffsideEvent {
+    int32_t status;                /* EAGLE_OFFSIDE_EV_* */
+    int32_t verdict;               /* EAGLE_OFFSIDE_ONSIDE .. EAGLE_OFFSIDE_OFFSIDE; 0 unless OK */
+    int32_t margin;                /* the receiver's at release_row, q; EAGLE_OFFSIDE_NONE unless OK */
+    int32_t line_qx;               /* the line at release_row */
+    int32_t n_off;                 /* the receiver's team in an offside position at release_row */
+    int32_t bypassed;              /* opponents the pass takes out of the game; -1: no ball at either row, or not OK */
+    int32_t group;                 /* the receiver's group; -1 for NOT_PASS and NO_RECEIVER */
+    int32_t reserved;              /* 0 */
+} EagleOffsideEvent;               /* 32 bytes */
+typedef struct EagleOffsideClip {
+    int32_t direction;             /* resolved: EAGLE_OFFSIDE_DIR_RIGHT or _LEFT; 0: unresolved */
+    int32_t requested;             /* EagleOffsideParams::direction */
+    int32_t neg, pos, zero;        /* the vote */
+    int32_t n_members[2];          /* members of groups 0 and 1 */
+    int32_t n_keepers;
+} EagleOffsideClip;                /* 32 bytes */
+/* The result is kept with the table until eagle_post_free.  A call computes into a buffer of its own and frees the earlier result only when the new one
+ * is complete, as eagle_post_space does: a refused call and a call that fails later both leave the earlier result in place.  The events are those of the
+ * table's possession result at the time of the call. */
+int eagle_post_offside(EagleHandle* h, EaglePostTable* t, const EagleOffsideParams* p);
+/* To the host: rows_out [rows][2] (the attacking group is the second index), margins int32 [members][rows] in group order, totals_out [members], one
+ * clip record; any pointer may be NULL. */
+int eagle_post_offside_values(EaglePostTable* t, EagleOffsideRow* rows_out, int32_t* margins, EagleOffsideTotals* totals_out, EagleOffsideClip* clip_out);
+/* *n = the number of event records of the last eagle_post_offside (0 before it); at most cap are written, in event order. */
+int eagle_post_offside_events(const EaglePostTable* t, EagleOffsideEvent* out, int cap, int* n);
+/* In HBM; all NULL (and 0 members, 0 events) before eagle_post_offside.  n_members and n_events may be NULL. */
+int eagle_post_device_offside(const EaglePostTable* t, const EagleOffsideRow** d_rows, const int32_t** d_margins, const EagleOffsideTotals** d_totals,
+                              const EagleOffsideClip** d_clip, const EagleOffsideEvent** d_events, int* n_members, int* n_events);
+/* Operator entry (host buffers in / out, no handle) for constructed tables, as eagle_op_space; frames [rows] is carried for symmetry with
+ * eagle_op_possession and not read (it may be NULL); events [n_events] as eagle_op_possession gives them (NULL with n_events == 0); every output may be
+ * NULL. */
+int eagle_op_offside(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids,
+                     const int32_t* team_vals, int n_team, const EagleOffsideParams* p, const EaglePossessionEvent* events, int n_events,
+                     EagleOffsideRow* rows_out, int32_t* margins, EagleOffsideTotals* totals_out, EagleOffsideClip* clip_out, EagleOffsideEvent* events_out);
+
 /* ---- shots: the camera cuts, gradual transitions and photo flashes of a clip, and which of its shots look at the pitch (own specification:
  * tests/shots_ref.py defines every output bit) ----
  * The stage in front of the networks: every other stage assumes one continuous shot of the main camera.  Input: n dense BGR frames [h][w][3], P = h w.
