@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -176,6 +176,21 @@ def main(argv=None):
     ap.add_argument("--offside-no-assumed-keeper", action="store_true",
                     help="with --offside: do not take a goalkeeper the camera does not see to stand on his goal line (the line is then the second-last opponent seen)")
     ap.add_argument("--offside-rows", action="store_true", help="with --offside: also write the line and the margins of every kept frame into offside.json")
+    ap.add_argument("--offside-view", action="store_true",
+                    help="with --processed --offside: also write <out>/offside_view.y4m, the annotated video of the table with the offside line lying on the grass under "
+                         "the players (a zone behind it, a ring under the second-last opponent and under every attacker beyond the line), and offside_view.json "
+                         "(eagle_amd/ground.py; the line is only as good as the frame's homography, which --topview shows)")
+    ap.add_argument("--offside-view-team", choices=["possession", "0", "1", "both"], default=None, metavar="T",
+                    help="with --offside-view: whose attack is shown: the team in possession on each frame (needs --possession, and is the default with it), "
+                         "team 0, 1 or both (the default without --possession)")
+    ap.add_argument("--offside-view-width", type=float, default=None, metavar="M",
+                    help="with --offside-view or --offside-stills: the width of the line in metres, > 0 and <= 10 (default 0.25, a conventional choice)")
+    ap.add_argument("--offside-view-no-zone", action="store_true", help="with --offside-view or --offside-stills: do not tint the zone between the line and the goal line")
+    ap.add_argument("--offside-view-no-key", action="store_true",
+                    help="with --offside-view or --offside-stills: draw over everything, players included, instead of only where the frame's pixel is grass")
+    ap.add_argument("--offside-stills", action="store_true",
+                    help="with --processed --offside --possession: write <out>/offside_<k>.ppm for every pass k with a verdict: the frame in which the ball was played with "
+                         "the receiver's team's line and a ring under the receiver, green (onside), yellow (close) or red (offside)")
     ap.add_argument("--space-map", action="store_true",
                     help="with --space: also write <out>/space.npy (uint8 [rows, 68 R, 105 R]), per cell the index of its owner among the frame's sites, 255 on a skipped frame")
     ap.add_argument("--shots", action="store_true",
@@ -274,6 +289,22 @@ def main(argv=None):
         ap.error("--offside works on the processed table: it needs --processed")
     if not a.offside and (a.offside_rows or a.offside_no_assumed_keeper or a.offside_direction is not None or a.offside_tolerance is not None):
         ap.error("--offside-direction, --offside-tolerance, --offside-no-assumed-keeper and --offside-rows set up the offside report: they need --offside")
+    if (a.offside_view or a.offside_stills) and not (a.processed and a.offside):
+        ap.error("--offside-view and --offside-stills draw the offside result of the processed table: they need --processed --offside")
+    if a.offside_stills and not a.possession:
+        ap.error("--offside-stills shows the passes: it needs --possession")
+    if not a.offside_view and a.offside_view_team is not None:
+        ap.error("--offside-view-team sets up the offside view: it needs --offside-view")
+    if not (a.offside_view or a.offside_stills) and (a.offside_view_width is not None or a.offside_view_no_zone or a.offside_view_no_key):
+        ap.error("--offside-view-width, --offside-view-no-zone and --offside-view-no-key set up the offside pictures: they need --offside-view or --offside-stills")
+    if a.offside_view_team == "possession" and not a.possession:
+        ap.error("--offside-view-team possession follows the owner of the ball: it needs --possession")
+    if a.offside_view or a.offside_stills:
+        team = a.offside_view_team or ("possession" if a.possession else "both")
+        a.offside_view_set = dict(team=int(team) if team in ("0", "1") else team, width=0.25 if a.offside_view_width is None else a.offside_view_width,
+                                  zone=not a.offside_view_no_zone, keyed=not a.offside_view_no_key)
+        if not 0.0 < a.offside_view_set["width"] <= 10.0:
+            ap.error("--offside-view-width: M must be > 0 and <= 10 metres")
     if a.offside:
         a.offside_set = (a.offside_direction or "auto", 0.5 if a.offside_tolerance is None else a.offside_tolerance)
         if not 0.0 <= a.offside_set[1] <= 1024.0:
@@ -479,6 +510,17 @@ def main(argv=None):
             from . import offside as ofs
             with open(os.path.join(a.out, "offside.json"), "w") as f:
                 json.dump(ofs.to_json(ofs.offside(model.handle, table, a.offside_set[0], a.offside_set[1], not a.offside_no_assumed_keeper, per_row=a.offside_rows)), f)
+        if a.offside_view:
+            from . import ground as gr
+            pics, info = gr.offside_view(model, frames, coordinates, table, out_format="i420", **a.offside_view_set)
+            write_y4m(os.path.join(a.out, "offside_view.y4m"), pics, a.fps)
+            with open(os.path.join(a.out, "offside_view.json"), "w") as f:
+                json.dump(info, f)
+        if a.offside_stills:
+            from . import ground as gr, occupancy as oc
+            st = {k: v for k, v in a.offside_view_set.items() if k != "team"}
+            for k, img, _ in gr.offside_stills(model, frames, coordinates, table, **st):
+                oc.write_ppm(os.path.join(a.out, "offside_%d.ppm" % k), img)
         entities = [c for c, k in enumerate(table.columns) if not k["video"] and int(k["kind"]) in (lib.POST_PLAYER, lib.POST_GOALKEEPER, lib.POST_BALL)]
         if a.trajectory is not None:
             from . import minimap as mm

@@ -161,6 +161,14 @@ class CoordinateModel:
         from . import topview as tv
         return tv.mosaic(self.handle, frames, self._records_of(coords_or_records, carried_as_plain=True), carry, **kw)
 
+    def ground(self, frames, coords_or_records, shapes, off, carry=True, out_format="bgr", params=None):
+        """The frames with shapes of the pitch plane blended into their grass (eagle_amd/ground.py, include/eagle.h eagle_ground_frames): shapes
+        lib.GROUND_SHAPE_DTYPE [off[n]] and off [n + 1], one list per frame, in 1 / 1024 m on the pitch; the homography of a frame is its record's,
+        with ``carry`` the latest earlier one where it has none -> (pictures uint8 [n, h, w, 3] or [n, 3h / 2, w], covered uint32 [n])."""
+        from . import topview as tv
+        Hs, valid, _ = tv.homographies(self._records_of(coords_or_records, carried_as_plain=True), carry)
+        return self.handle.ground(frames, Hs, valid, shapes, off, params, out_format)
+
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The frames with their records drawn on them (the reference's annotated video, main.py:43-81; include/eagle.h eagle_annotate_frames):
         uint8 [n, h, w, 3] for out_format "bgr", [n, 3h/2, w] for "nv12" / "i420".  ``frames`` as get_coordinates takes them (pixel_format "bgr",

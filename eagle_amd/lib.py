@@ -180,6 +180,23 @@ TOPVIEW_MAX_FRAMES = 1 << 23
 assert C.sizeof(EagleTopviewParams) == 56                                    # topview.hip asserts it too
 
 
+class EagleGroundShape(C.Structure):
+    """include/eagle.h EagleGroundShape: a band (a = x0, x1, y0, y1) or a ring (a = cx, cy, r0, r1) on the pitch plane in 1 / 1024 m, its colour as
+    B | G << 8 | R << 16, alpha 0 .. 256 per sub-sample, GROUND_KEYED: only where the source pixel is grass."""
+    _fields_ = [("kind", C.c_int32), ("a", C.c_int32 * 6), ("colour", C.c_uint32), ("alpha", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class EagleGroundParams(C.Structure):
+    """include/eagle.h EagleGroundParams: the grass key (g >= key_min and g - max(r, b) >= key_lead); no_cull = 1 for measurements (same bytes)."""
+    _fields_ = [("key_min", C.c_int32), ("key_lead", C.c_int32), ("no_cull", C.c_int32), ("reserved", C.c_int32)]
+
+
+GROUND_MAX_SHAPES = 16                                                       # include/eagle.h EAGLE_GROUND_*
+GROUND_BAND, GROUND_RING, GROUND_KEYED = 0, 1, 1
+GROUND_SHAPE_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4", 6), ("colour", "<u4"), ("alpha", "<i4"), ("flags", "<i4"), ("reserved", "<i4", 2)])          # EagleGroundShape (48 bytes)
+assert C.sizeof(EagleGroundShape) == 48 == GROUND_SHAPE_DTYPE.itemsize and C.sizeof(EagleGroundParams) == 16                                           # ground.hip asserts them too
+
+
 class EagleKinematicsParams(C.Structure):
     """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
@@ -441,6 +458,10 @@ def load():
     L.eagle_topview_mosaic_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, tvp, vp, i32]
     L.eagle_topview_residual_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, tvp, vp, vp, vp, vp]
     L.eagle_op_topview.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, tvp, i32, i32, lay, vp, vp, vp, vp, vp, vp]
+    grp = C.POINTER(EagleGroundParams)
+    L.eagle_ground_device_frames.argtypes = [vp, vp, i32, vp, vp, vp, vp, grp, i32, lay, vp, vp]
+    L.eagle_ground_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, grp, i32, lay, vp, vp]
+    L.eagle_op_ground.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, grp, i32, lay, vp, vp]
     lp = C.POINTER(EagleLoadParams)
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
@@ -488,7 +509,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_post_offside", "eagle_post_offside_values", "eagle_post_offside_events",
            "eagle_post_device_offside", "eagle_op_offside", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
            "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
-           "eagle_op_topview", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
+           "eagle_op_topview", "eagle_ground_device_frames", "eagle_ground_frames", "eagle_op_ground", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
            "eagle_op_flow"]
 
@@ -848,6 +869,42 @@ class Handle:
                                                       C.byref(params), d_acc, _ptr(rs, keep), _ptr(rc_, keep), _ptr(cv, keep))
         self._check(rc, "topview_residual")
         return rs, rc_, cv
+
+    # --- ground layer: shapes on the pitch plane blended into the camera picture (include/eagle.h, eagle_ground_*) ----------------------
+    def ground_device(self, d_bgr, n, Hs, valid, shapes, off, d_out, params=None, fmt="bgr", layout=None):
+        """n dense BGR frames resident in HBM + their homographies + the shapes of each (GROUND_SHAPE_DTYPE [off[n]], off [n + 1]) -> n pictures
+        at ``d_out`` (device, another buffer) in ``fmt`` / ``layout``; returns covered uint32 [n]."""
+        _, n, Hs, valid = self._topview_clip("ground_device", None, Hs, valid, n)
+        shapes, off = _ground_lists("ground_device", shapes, off, n)
+        p = ground_params() if params is None else params
+        lay = _yuv_layout(layout)
+        cov = np.zeros(n, np.uint32)
+        keep = np.zeros(16, np.uint8)
+        self._check(self.L.eagle_ground_device_frames(self._h, d_bgr, n, _ptr(Hs, keep), _ptr(valid, keep), _ptr(shapes, keep), _ptr(off, keep), C.byref(p), _out_pix(fmt),
+                                                      None if lay is None else C.byref(lay), d_out, _ptr(cov, keep)), "ground_device_frames")
+        return cov
+
+    def ground(self, frames, Hs, valid, shapes, off, params=None, fmt="bgr", layout=None, out=None, max_staging_bytes=0):
+        """frames uint8 [n, h, w, 3] (host) -> (the pictures in host memory: uint8 [n, h, w, 3] ("bgr") or [n, 3h / 2, w] ("nv12" / "i420"), with a
+        ``layout`` a flat uint8 buffer of the layout's span (``out``: the caller's buffer); covered uint32 [n]).  Uploaded in passes of
+        ``max_staging_bytes`` (0: 64 MB)."""
+        frames, n, Hs, valid = self._topview_clip("ground", frames, Hs, valid)
+        shapes, off = _ground_lists("ground", shapes, off, n)
+        p = ground_params() if params is None else params
+        h, w = self.cfg.frame_h, self.cfg.frame_w
+        lay = _yuv_layout(layout)
+        need = out_span(fmt, h, w, lay, n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+            if lay is None:
+                out = out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise EagleError(f"ground: out must be a contiguous uint8 array of at least {need} bytes")
+        cov = np.zeros(n, np.uint32)
+        keep = np.zeros(16, np.uint8)
+        self._check(self.L.eagle_ground_frames(self._h, _ptr(frames, keep), n, int(max_staging_bytes), _ptr(Hs, keep), _ptr(valid, keep), _ptr(shapes, keep), _ptr(off, keep),
+                                               C.byref(p), _out_pix(fmt), None if lay is None else C.byref(lay), _ptr(out, keep), _ptr(cov, keep)), "ground_frames")
+        return out, cov
 
     # --- annotated output (include/eagle.h, eagle_annotate_*) --------------------------------------------------
     def annotate_device(self, d_bgr, n, recs, d_out, team_mapping=None, fmt="bgr", layout=None):
@@ -2493,6 +2550,69 @@ def op_topview(frames, Hs, valid, params, boxes=None, mode=TOPVIEW_VIDEO, fmt="b
     if (mode & TOPVIEW_VIDEO) and lay is None:
         res["video"] = out.reshape((n, Hc, W, 3) if _out_pix(fmt) == 0 else (n, Hc * 3 // 2, W))
     return res
+
+
+def ground_params(key_min=48, key_lead=16, no_cull=False):
+    """EagleGroundParams; 48 and 16 are the shots stage's grass rule, conventional choices that are not fitted to footage."""
+    return EagleGroundParams(int(key_min), int(key_lead), int(bool(no_cull)), 0)
+
+
+def ground_band(x0, x1, y0, y1, colour, alpha, keyed=False):
+    """one GROUND_SHAPE_DTYPE record: the band x0 <= qx < x1, y0 <= qy < y1 (1 / 1024 m)"""
+    s = np.zeros((), GROUND_SHAPE_DTYPE)
+    s["kind"], s["a"][:4], s["colour"], s["alpha"], s["flags"] = GROUND_BAND, (x0, x1, y0, y1), colour, alpha, GROUND_KEYED if keyed else 0
+    return s
+
+
+def ground_ring(cx, cy, r0, r1, colour, alpha, keyed=False):
+    """one GROUND_SHAPE_DTYPE record: the ring r0^2 <= (qx - cx)^2 + (qy - cy)^2 < r1^2 (1 / 1024 m)"""
+    s = np.zeros((), GROUND_SHAPE_DTYPE)
+    s["kind"], s["a"][:4], s["colour"], s["alpha"], s["flags"] = GROUND_RING, (cx, cy, r0, r1), colour, alpha, GROUND_KEYED if keyed else 0
+    return s
+
+
+def ground_shape_lists(lists):
+    """a list of per-frame lists of GROUND_SHAPE_DTYPE records -> (shapes [off[n]], off int32 [n + 1])"""
+    off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
+    flat = [np.asarray(s, GROUND_SHAPE_DTYPE).reshape(()) for x in lists for s in x]
+    return (np.stack(flat) if flat else np.zeros(0, GROUND_SHAPE_DTYPE)), off
+
+
+def _ground_lists(what, shapes, off, n):
+    shapes = np.ascontiguousarray(shapes, GROUND_SHAPE_DTYPE).reshape(-1)
+    off = np.ascontiguousarray(off, np.int32).reshape(-1)
+    if len(off) != n + 1 or int(off[-1]) > len(shapes):
+        raise EagleError(f"{what}: off must have n + 1 = {n + 1} entries that end inside the {len(shapes)} shapes (got {len(off)} entries)")
+    return shapes, off
+
+
+def op_ground(frames, Hs, valid, shapes, off, params=None, fmt="bgr", layout=None, out=None, device=0):
+    """The ground launch on constructed frames (include/eagle.h eagle_op_ground): frames uint8 [n, h, w, 3] of any size, Hs [n, 9], valid [n], shapes
+    GROUND_SHAPE_DTYPE [off[n]], off [n + 1] -> (the pictures: [n, h, w, 3] / [n, 3h / 2, w] when dense, else the flat buffer ``out`` or a zeroed one
+    written in ``layout``; covered uint32 [n])."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    if frames.ndim != 4 or frames.shape[3] != 3:
+        raise EagleError(f"op_ground: frames must be [n, h, w, 3] (got {frames.shape})")
+    n, h, w, _ = frames.shape
+    Hs, valid = _topview_maps("op_ground", Hs, valid, n)
+    shapes, off = _ground_lists("op_ground", shapes, off, n)
+    p = ground_params() if params is None else params
+    lay = _yuv_layout(layout)
+    need = out_span(fmt, h, w, lay, n)
+    if out is None:
+        out = np.zeros(need, np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+        raise EagleError(f"op_ground: out must be a contiguous uint8 array of at least {need} bytes")
+    cov = np.zeros(n, np.uint32)
+    keep = np.zeros(16, np.uint8)
+    rc = L.eagle_op_ground(device, _ptr(frames, keep), n, h, w, _ptr(Hs, keep), _ptr(valid, keep), _ptr(shapes, keep), _ptr(off, keep), C.byref(p), _out_pix(fmt),
+                           None if lay is None else C.byref(lay), _ptr(out, keep), _ptr(cov, keep))
+    if rc:
+        raise EagleError(f"eagle_op_ground failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if lay is None:
+        out = out.reshape((n, h, w, 3) if _out_pix(fmt) == 0 else (n, h * 3 // 2, w))
+    return out, cov
 
 
 def op_minimap_hulls(values, frames, columns, team_mapping, params, hull, trail=None, sel=(), owner=None, events=None, row0=0, n=None, fmt="bgr", layout=None, out=None,

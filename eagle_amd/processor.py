@@ -141,3 +141,15 @@ class Processor:
         eagle_amd/offside.py."""
         from . import offside as of
         return of.offside(self.model.handle, table, direction, tolerance, assume_keeper, per_row)
+
+    def offside_view(self, frames, coords_or_records, table, team="possession", width=0.25, zone=True, rings=True, keyed=True, pixel_format="bgr", out_format="bgr"):
+        """The annotated video of a processed table with the offside line lying on the grass under the players, after offside above (and possession for
+        team="possession") -> (pictures, the dict offside_view.json holds): see eagle_amd/ground.py."""
+        from . import ground as gr
+        return gr.offside_view(self.model, frames, coords_or_records, table, team, width, zone, rings, keyed, pixel_format, out_format)
+
+    def offside_stills(self, frames, coords_or_records, table, width=0.25, zone=True, keyed=True, pixel_format="bgr"):
+        """One picture per pass with an offside verdict, after possession and offside above: the frame in which the ball was played with the receiver's
+        team's line and a ring under the receiver in the colour of the verdict -> [(event index, picture, dict)]: see eagle_amd/ground.py."""
+        from . import ground as gr
+        return gr.offside_stills(self.model, frames, coords_or_records, table, width, zone, keyed, pixel_format)

@@ -1130,6 +1130,69 @@ int eagle_op_topview(int device, const uint8_t* bgr, int n, int h, int w, const 
                      const EagleTopviewParams* p, int mode, int out_format, const EagleYuvLayout* out_layout, uint8_t* out, uint8_t* mosaic_out, uint32_t* cnt_out,
                      uint64_t* res_sum, uint32_t* res_cnt, uint32_t* covered);
 
+/* ---- ground layer: shapes that lie on the pitch plane, blended into the grass of the camera picture under the players (own specification:
+ * tests/ground_ref.py defines every output byte) ----
+ * What puts an offside line, its zone and a ring under a player's feet into the frame itself, as a broadcaster shows them.  Input: n dense BGR frames
+ * [h][w][3], Hs [n][9] (row-major, image -> pitch, as in the records), valid [n], and per frame the shapes shapes[off[f] .. off[f + 1]) (off [n + 1]
+ * ascends from 0), at most EAGLE_GROUND_MAX_SHAPES per frame.
+ *   MAP      per frame; pixel centres lie at integers, as in the top view.  sb = (h6 (w - 1) / 2 + h7 (h - 1)) + h8 in float64, every operation single:
+ *            the projective weight of the frame's bottom-centre pixel.  The frame has NO MAP when valid is 0, when any h_i or sb is not finite, or
+ *            when sb == 0; it is then passed through: its source pixels in the output format, covered = 0.
+ *   SAMPLES  four per pixel (X, Y), a rotated grid with the offsets (dx, dy) = (-0.375, -0.125), (0.125, -0.375), (0.375, 0.125), (-0.125, 0.375):
+ *            u = X + dx, v = Y + dy; x' = ((h0 u) + (h1 v)) + h2, y' and w' likewise from rows 1 and 2.  A sub-sample is ON THE GROUND iff w' and sb
+ *            have the same strict sign (the same side of the horizon as the bottom of the picture, so H and c H, c != 0, give the same bytes) and
+ *            px = x' / w', py = y' / w' are finite with |px|, |py| <= 1024.  Then qx = floor(px 1024 + 0.5), qy likewise, as int32: the quantisation
+ *            q of the team-shape, space and offside stages.  Everything behind it is integers.
+ *   SHAPES   EAGLE_GROUND_BAND, a = x0, x1, y0, y1: inside iff x0 <= qx < x1 and y0 <= qy < y1 (half-open).  EAGLE_GROUND_RING, a = cx, cy, r0, r1
+ *            with 0 <= r0 < r1 <= 2^20: inside iff r0^2 <= (qx - cx)^2 + (qy - cy)^2 < r1^2 in int64.  Flag EAGLE_GROUND_KEYED: the shape is drawn
+ *            only where the SOURCE pixel is grass, g >= key_min and g - max(r, b) >= key_lead (the shots stage's rule with its 48 and 16, which are
+ *            conventional choices, not fitted to footage).
+ *   BLEND    per pixel over the frame's shapes in list order, starting from the source pixel: c = the number of its four sub-samples that are on the
+ *            ground and inside the shape; the shape is skipped when c == 0, when alpha == 0, or when it is KEYED and the source pixel is not grass;
+ *            else A = alpha c (at most 1024) and every channel becomes (channel (1024 - A) + colour A + 512) >> 10.  covered[f] = the pixels of
+ *            frame f that at least one shape blended into: an integer sum, independent of how the work is split, the same in two runs.
+ *   OUTPUT   BGR, NV12 or I420 in the caller's layout, as eagle_annotate_* (same conversion, same layout rules).
+ * Limits: the key is a colour rule per pixel of the source frame, no matting and no smoothing over time, so green kits and shadows key wrongly; a shape
+ * is only as well placed as the frame's homography; no lens distortion; four sub-samples, so a band narrower than a far-side pixel thins out; bands are
+ * axis-aligned on the pitch; nothing is validated on real footage.  One launch per 65535 frames (ground.hip) on the handle's main stream; the table of
+ * maps, the shapes and the counts are allocated per call and freed; records, staging buffers and graphs of the handle are not involved.  no_cull = 1
+ * switches off the kernel's per-tile rejection of shapes for measurements; the bytes are the same either way.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output alone: NULL pointers (parameters, off; frames, Hs, valid, the output with
+ * n > 0; shapes with off[n] > 0), n < 0, off not ascending from 0 or more than EAGLE_GROUND_MAX_SHAPES shapes in a frame, an unknown kind or flag,
+ * alpha outside 0 .. 256, a colour above 0xffffff, a band with x0 >= x1 or y0 >= y1 or an argument beyond +-2^21, a ring with a centre coordinate
+ * beyond +-2^21 or radii outside 0 <= r0 < r1 <= 2^20, non-zero reserved words (a[4], a[5] and reserved of a shape, reserved of the parameters), key_min
+ * or key_lead outside 0 .. 255, no_cull other than 0 or 1, every layout error eagle_annotate_* refuses (odd h or w with a 4:2:0 format among them), a
+ * negative max_staging_bytes; d_out equal to d_bgr; in the operator entry a frame side outside 1 .. 16384.  n == 0 succeeds and writes nothing.  covered may
+ * be NULL. */
+#define EAGLE_GROUND_MAX_SHAPES 16
+#define EAGLE_GROUND_BAND 0            /* EagleGroundShape::kind */
+#define EAGLE_GROUND_RING 1
+#define EAGLE_GROUND_KEYED 1           /* EagleGroundShape::flags */
+typedef struct EagleGroundShape {
+    int32_t kind;                  /* EAGLE_GROUND_BAND, EAGLE_GROUND_RING */
+    int32_t a[6];                  /* band: x0, x1, y0, y1; ring: cx, cy, r0, r1 (1 / 1024 m); a[4] = a[5] = 0 */
+    uint32_t colour;               /* B | G << 8 | R << 16 */
+    int32_t alpha;                 /* 0 .. 256 per sub-sample */
+    int32_t flags;                 /* EAGLE_GROUND_KEYED */
+    int32_t reserved[2];           /* 0 */
+} EagleGroundShape;                /* 48 bytes */
+typedef struct EagleGroundParams {
+    int32_t key_min, key_lead;     /* 0 .. 255 (conventionally 48 and 16) */
+    int32_t no_cull;               /* 0; 1: measure without the per-tile rejection */
+    int32_t reserved;              /* 0 */
+} EagleGroundParams;               /* 16 bytes */
+/* n frames of the handle's size, dense, resident in HBM -> n pictures at d_out (device, another buffer than d_bgr) in out_format / out_layout, and
+ * covered [n] (host); returns when they are complete.  Hs, valid, shapes and off are host memory. */
+int eagle_ground_device_frames(EagleHandle* h, const uint8_t* d_bgr, int n, const double* Hs, const uint8_t* valid, const EagleGroundShape* shapes, const int32_t* off,
+                               const EagleGroundParams* p, int out_format, const EagleYuvLayout* out_layout, void* d_out, uint32_t* covered);
+/* Same, dense frames in host memory -> pictures in host memory (pinned or pageable, as eagle_minimap_frames), in passes of what max_staging_bytes (0:
+ * 64 MB; always at least one frame) of device staging hold.  The result does not depend on the size of a pass. */
+int eagle_ground_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t max_staging_bytes, const double* Hs, const uint8_t* valid, const EagleGroundShape* shapes,
+                        const int32_t* off, const EagleGroundParams* p, int out_format, const EagleYuvLayout* out_layout, uint8_t* out, uint32_t* covered);
+/* Operator entry (host buffers in / out, no handle) for constructed inputs: dense frames of any h x w within 1 .. 16384 per side. */
+int eagle_op_ground(int device, const uint8_t* bgr, int n, int h, int w, const double* Hs, const uint8_t* valid, const EagleGroundShape* shapes, const int32_t* off,
+                    const EagleGroundParams* p, int out_format, const EagleYuvLayout* out_layout, uint8_t* out, uint32_t* covered);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
