@@ -4,8 +4,14 @@
 // random_state=0)), the cluster that owns the majority of the four crop corners is the background, and the other cluster's pixels are
 // counted per colour range of proc.py:10-23 in cv2's 8-bit HSV (hue 0..180, table-driven fixed point like hue180 in geom.hip).
 // The 2-means is scikit-learn's run restated step by step (k-means++ seeding with RandomState(0)'s first three doubles, Lloyd's iterations with
-// the tol rule, final assignment; oracle/colors.py::kmeans2_labels is the same restatement and is pinned to sklearn's own labels on
-// several hundred crops): colour counts identical to the reference's own outputs on all crops of tests/golden/team_golden.json.
+// the tol rule, final assignment; oracle/colors.py::kmeans2_labels is the same restatement): colour counts identical to the reference's own
+// outputs on all crops of tests/golden/team_golden.json.
+// What is pinned: the labels equal scikit-learn's for every crop WITHOUT an exact distance tie on its Lloyd path (a pixel exactly equidistant from
+// the two centres at some assignment step).  On a tie this kernel, like the restatement, assigns the pixel to cluster 0.  scikit-learn centres
+// the data before it iterates, so its ties break by the rounding of the centred values; that is not reproduced, and the two can end in different
+// local minima.  Of 400 seeded few-level crops (flat graphics, heavily quantised video) 117 have such a tie and 16 of those differ from
+// scikit-learn 1.7.2; all 283 tie-free ones are identical (tests/test_team_cases_cpu.py; tests/team_color_cases.py builds tie-free cases and
+// checks the condition in exact integer arithmetic).
 #include "common.h"
 
 namespace eagle {

@@ -1318,7 +1318,10 @@ int eagle_track_frames_reid(EagleHandle* h, EagleFrameResult* recs, int n, const
 
 /* ---- team colours: Processor.detect_color, eagle/processor.py:466-503, for player crops of a clip resident in HBM -----
  * counts[12 * i + k]: pixels of crop i's player cluster inside colour range k of proc.py:10-23, k = red (red2 merged), orange, yellow,
- * green, cyan, blue, purple, magenta, white, gray, black; slot 11 = pixels of the player cluster.  Crops are frame[y1:y2, x1:x2]. */
+ * green, cyan, blue, purple, magenta, white, gray, black; slot 11 = pixels of the player cluster.  Crops are frame[y1:y2, x1:x2]; a crop that is
+ * empty or leaves the clip gives twelve zeros.  The 2-means equals scikit-learn's KMeans(n_clusters=2, random_state=0) for crops with no exact
+ * distance tie on the Lloyd path.  On a tie (a pixel exactly equidistant from both centres) the library assigns to cluster 0; scikit-learn's
+ * result there depends on the rounding of its centred data and is not reproduced (of 400 seeded few-level crops, 117 tie and 16 of those differ). */
 int eagle_team_colors(EagleHandle* h, const void* d_bgr, int n_frames, const EagleCrop* crops, int n_crops, int32_t* counts);
 
 /* Frame-sharded multi-GPU: rank r owns a contiguous chunk; one RCCL all-gather of records.

@@ -2,8 +2,12 @@
 
 Team colours: ``Processor.get_team_mapping`` / ``detect_color`` of the reference's post-processor (eagle/processor.py:405-503,
 colour table :10-23).  K-means: ``kmeans2_labels`` restates scikit-learn 1.7's ``KMeans(n_clusters=2, random_state=0).fit(X).labels_`` (the
-reference's call) step by step and is pinned to sklearn's own labels (tests/test_oracle_colors.py, several hundred crops; sklearn is in this
-image); cv2's 8-bit BGR2HSV is eo_flow.c's restatement; inRange / bitwise_and / countNonZero are their numpy definitions.
+reference's call) step by step.  It equals sklearn's own labels on every crop that has no exact distance tie on its Lloyd path (a pixel exactly
+equidistant from both centres at some assignment step): tests/test_oracle_colors.py (several hundred crops; sklearn is in this image) and
+tests/test_team_cases_cpu.py, whose cases are checked to be tie-free in exact integer arithmetic.  On a tie the restatement, like the kernel,
+assigns to cluster 0; sklearn centres X before iterating, so its result there depends on the rounding of the centred data and is not reproduced
+(of 400 seeded few-level crops 117 have a tie on the path and 16 of those end in another partition under sklearn 1.7.2; all 283 tie-free ones
+are identical).  cv2's 8-bit BGR2HSV is eo_flow.c's restatement; inRange / bitwise_and / countNonZero are their numpy definitions.
 Pinned to the reference's own functions by tests/golden/team_golden.json (tests/golden/make_golden.py::dump_team runs proc.py itself
 over these primitives)."""
 from collections import Counter
@@ -41,7 +45,8 @@ def kmeans2_labels(X):
       * seeding (_kmeans_plusplus): centre 0 = X[choice(n)] = X[floor(u0 n)]; two candidates (n_local_trials = 2 + int(log 2)) at
         searchsorted(cumsum(d0), (u1, u2) * sum(d0)) with d0 the squared distances to centre 0; the candidate with the smaller potential
         sum(min(d0, d_candidate)) becomes centre 1.  Squared distances between pixels are exact integers;
-      * Lloyd (_kmeans_single_lloyd, float64): label = argmin_k |c_k|^2 - 2 x.c_k (ties to cluster 0), centres = cluster means; stop when the
+      * Lloyd (_kmeans_single_lloyd, float64): label = argmin_k |c_k|^2 - 2 x.c_k (ties to cluster 0: equal to sklearn only where no exact tie
+        occurs, see the module docstring), centres = cluster means; stop when the
         labels repeat, or when the summed squared centre shift is <= mean(var(X, axis=0)) * 1e-4; the returned labels are the assignment to the
         final centres.  Label 0 is the cluster that grew from centre 0."""
     X = np.asarray(X).astype(np.int64)
