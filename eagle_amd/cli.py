@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -193,6 +193,18 @@ def main(argv=None):
                          "the receiver's team's line and a ring under the receiver, green (onside), yellow (close) or red (offside)")
     ap.add_argument("--space-map", action="store_true",
                     help="with --space: also write <out>/space.npy (uint8 [rows, 68 R, 105 R]), per cell the index of its owner among the frame's sites, 255 on a skipped frame")
+    ap.add_argument("--ball-track", action="store_true",
+                    help="with --processed: the table's ball is the detection of every frame that lies on the best physically possible path through the clip "
+                         "instead of the reference's choice (a frame's only detection whatever it is, of several the nearest to the image origin); also write "
+                         "<out>/ball_track.json.  With --shots or --trim-to-shot the cuts break the path (eagle_amd/balltrack.py)")
+    ap.add_argument("--ball-track-speed", type=float, default=None, metavar="PX",
+                    help="with --ball-track: the ball's greatest speed in pixels per frame, > 0 and <= 65535 (default a tenth of the frame's width, a conventional choice)")
+    ap.add_argument("--ball-track-gap", type=int, default=None, metavar="G", help="with --ball-track: the most frames a link may span, 1 .. 64 (default min(64, --fps))")
+    ap.add_argument("--ball-track-reward", type=float, default=None, metavar="PX",
+                    help="with --ball-track: what a sighting of confidence 1 is worth, in pixels of path, > 0 and <= 65535 (default the speed)")
+    ap.add_argument("--ball-track-break", type=float, default=None, metavar="PX",
+                    help="with --ball-track: what it costs to break the path off and start again, in pixels, > 0 and <= 1048576 (default two and a half rewards)")
+    ap.add_argument("--ball-track-rows", action="store_true", help="with --ball-track: also write the record of every frame into ball_track.json")
     ap.add_argument("--shots", action="store_true",
                     help="also write <out>/shots.json: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at "
                          "the pitch, and put the shot count into metadata.json (the thresholds are conventional choices, not fitted to footage)")
@@ -285,6 +297,20 @@ def main(argv=None):
         a.space_set = (1 if a.space_grid is None else a.space_grid, 3.0 if a.space_radius is None else a.space_radius)
         if not (a.space_set[1] == a.space_set[1] and 0.0 < a.space_set[1] <= 1024.0):
             ap.error("--space-radius: M must be > 0 and <= 1024 metres")
+    if a.ball_track and not a.processed:
+        ap.error("--ball-track chooses the ball of the processed table: it needs --processed")
+    bt_set = {"speed": a.ball_track_speed, "gap": a.ball_track_gap, "reward": a.ball_track_reward, "brk": a.ball_track_break}
+    if not a.ball_track and (a.ball_track_rows or any(v is not None for v in bt_set.values())):
+        ap.error("--ball-track-speed, --ball-track-gap, --ball-track-reward, --ball-track-break and --ball-track-rows set up the ball track: they need --ball-track")
+    if a.ball_track:
+        if a.fps < 1:
+            ap.error("--ball-track needs --fps of at least 1")
+        if a.ball_track_gap is not None and not 1 <= a.ball_track_gap <= 64:
+            ap.error("--ball-track-gap takes 1 .. 64 frames")
+        for v, top, flag in ((a.ball_track_speed, 65535.0, "speed"), (a.ball_track_reward, 65535.0, "reward"), (a.ball_track_break, 1048576.0, "break")):
+            if v is not None and not 0.0 < v <= top:                      # (NaN fails too)
+                ap.error(f"--ball-track-{flag}: PX must be > 0 and <= {top:.0f} pixels")
+        a.ball_track_set = {k: v for k, v in bt_set.items() if v is not None}
     if a.offside and not a.processed:
         ap.error("--offside works on the processed table: it needs --processed")
     if not a.offside and (a.offside_rows or a.offside_no_assumed_keeper or a.offside_direction is not None or a.offside_tolerance is not None):
@@ -399,10 +425,11 @@ def main(argv=None):
                             precision=a.precision, detector_precision=a.detector_precision, allow_saturation=a.allow_saturation, device=a.device, seed=a.seed,
                             hrnet_state_dict=hs, detector_state_dict=ys, tracker=a.tracker, camera_motion=a.camera_motion or False,
                             reid=a.reid, reid_state_dict=({("reid." + k): v for k, v in load_state_dict(a.reid_weights).items()} if a.reid_weights else None))
-    shot_meta = {}
+    shot_meta, found_shots, first_frame = {}, None, 0
     if a.shots or a.trim_to_shot is not None:
         from . import shots as _shots
         found = model.shots(frames, a.fps, **shot_set)
+        found_shots = found.shots
         shot_meta["shots"] = len(found.shots)
         if a.shots:
             os.makedirs(a.out, exist_ok=True)
@@ -417,7 +444,7 @@ def main(argv=None):
             first, count = int(found.shots[k]["first"]), int(found.shots[k]["count"])
             shot_meta["trim"] = {"shot": int(k), "first": first, "count": count}
             frames = frames[first:first + count]
-            n = count
+            n, first_frame = count, first
     t0 = time.perf_counter()
     nh, nk = (a.fps, a.fps) if a.every_frame else (a.num_homography, a.num_keypoint_detection)
     from . import lib
@@ -437,7 +464,14 @@ def main(argv=None):
         from . import postprocess
         from .annotate import write_y4m
         from .processor import Processor
-        table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids)
+        if a.ball_track:
+            from . import balltrack as bt
+            cuts = bt.cuts_of_shots(found_shots, first_frame, n) if found_shots is not None else None
+            table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids, ball_track=a.ball_track_set or True, cuts=cuts)
+            with open(os.path.join(a.out, "ball_track.json"), "w") as f:
+                json.dump(bt.to_json(*table.ball_track, rows=a.ball_track_rows), f)
+        else:
+            table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids)
         merges = table.merges
         with open(os.path.join(a.out, "raw_data.json"), "w") as f:
             json.dump(postprocess.json_rows(postprocess.raw_data_rows(table)), f)
@@ -543,6 +577,8 @@ def main(argv=None):
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
         if a.merge_ids:
             meta["merges"] = merges
+        if a.ball_track:
+            meta["ball"] = "ball_track"                                    # the table's ball is the tracked one (ball_track.json)
     elif a.annotated:
         from .annotate import write_y4m
         from .processor import Processor

@@ -460,7 +460,7 @@ static const void* conv_zero_page()
     int dev = 0;
     HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> g(g_page_mutex);
-    if (!z[dev]) { HIP_CHECK(hipMalloc(&z[dev], 256)); HIP_CHECK(hipMemset(z[dev], 0, 256)); }
+    if (!z[dev]) { HIP_CHECK(hipMalloc(&z[dev], 256)); HIP_CHECK(hipMemset(z[dev], 0, 256)); HIP_CHECK(hipStreamSynchronize(nullptr)); }     // (read on non-blocking streams)
     return z[dev];
 }
 static void* conv_trash_page()

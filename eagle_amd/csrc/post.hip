@@ -382,7 +382,8 @@ static void stitch_tracks(std::vector<PostTrack>& tr, const std::vector<int32_t>
     }
 }
 
-static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, EaglePostTable* t)
+// ball_det (may be NULL): the one reported ball detection of every frame that counts, -1: none (eagle_postprocess_ball)
+static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, EaglePostTable* t, const int32_t* ball_det)
 {
     t->h = h;
     if (p->team_ids && p->n_team >= 0) {
@@ -406,6 +407,7 @@ static void postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, con
             for (int k = 0; k < nd; ++k) {
                 const EagleDet& d = rec.det[k];
                 if (d.cls != want || !d.reported) continue;
+                if (want == 2 && ball_det && ball_det[i] != k) continue;
                 const double cx = (double)((d.bx1 & 0xFFFF) + (d.bx2 & 0xFFFF)) / 2.0, cy = (double)(d.by2 & 0xFFFF);      // ((x1 + x2) / 2, y2) of the uint16 "BBox"
                 const bool on_pitch = rec.H_valid && d.in_bounds;
                 if (want < 2) {
@@ -614,6 +616,11 @@ extern "C" {
 
 int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, EaglePostTable** out)
 {
+    return eagle_postprocess_ball(h, recs, n, p, nullptr, out);
+}
+
+int eagle_postprocess_ball(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, const int32_t* ball_det, EaglePostTable** out)
+{
     API_BEGIN_H(h)
     if (!out) fail(EAGLE_E_INVALID, "eagle_postprocess: out is NULL");
     *out = nullptr;
@@ -625,10 +632,16 @@ int eagle_postprocess(EagleHandle* h, const EagleFrameResult* recs, int n, const
     if (p->fps <= 0 || p->frame_w <= 0) fail(EAGLE_E_INVALID, "eagle_postprocess: fps %d and frame_w %d must be positive", p->fps, p->frame_w);
     if (p->n_team < 0 || (p->n_team > 0 && p->team_ids && !p->team_vals)) fail(EAGLE_E_INVALID, "eagle_postprocess: bad team map (%d entries)", p->n_team);
     if (p->max_bytes < 0) fail(EAGLE_E_INVALID, "eagle_postprocess: max_bytes %lld is negative", (long long)p->max_bytes);
+    for (int i = 0; ball_det && i < n; ++i) {
+        const int k = ball_det[i];
+        if (k == -1) continue;
+        if (k < 0 || k >= std::min(recs[i].n_det, EAGLE_MAX_DET) || recs[i].det[k].cls != 2 || !recs[i].det[k].reported)
+            fail(EAGLE_E_INVALID, "eagle_postprocess_ball: ball_det[%d] = %d is not a reported ball detection of its record (%d detections)", i, k, recs[i].n_det);
+    }
     std::unique_ptr<EaglePostTable> t(new EaglePostTable);
     t->max_bytes = p->max_bytes;
     try {
-        postprocess(h, recs, n, p, t.get());
+        postprocess(h, recs, n, p, t.get(), ball_det);
     } catch (...) {
         if (t->d_values) (void)hipFree(t->d_values);
         throw;

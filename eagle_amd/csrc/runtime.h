@@ -142,6 +142,9 @@ struct Net {                      // one launch schedule + the device memory it 
         void* p = nullptr;
         HIP_CHECK(hipMalloc(&p, b));
         HIP_CHECK(hipMemset(p, 0, b));
+        // the fill runs on the null stream and need not have finished when hipMemset returns; the handle's streams are non-blocking and do not wait
+        // for it, so a copy or a kernel that writes the buffer right away could be overwritten by the late zeros: wait here, once per new buffer
+        HIP_CHECK(hipStreamSynchronize(nullptr));
         owned.push_back(p); sizes[p] = b; bytes += b;
         return p;
     }

@@ -153,6 +153,24 @@ assert C.sizeof(EagleOffsideParams) == 32 and (OFFSIDE_ROW_DTYPE.itemsize, OFFSI
                                                OFFSIDE_CLIP_DTYPE.itemsize) == (48, 32, 32, 32)                                                      # offside.hip asserts them too
 
 
+class EagleBallTrackParams(C.Structure):
+    """include/eagle.h EagleBallTrackParams: the clip's fps and frame width, the window in frames, speed / reward / break in pixels (0: the default), the
+    device-memory budget."""
+    _fields_ = [("fps", C.c_int32), ("frame_w", C.c_int32), ("gap", C.c_int32), ("reserved", C.c_int32 * 5), ("speed", C.c_double), ("reward", C.c_double),
+                ("brk", C.c_double), ("max_bytes", C.c_int64)]
+
+
+BALL_MAX_CAND = 8                                                              # include/eagle.h EAGLE_BALL_*
+BALL_TOO_MANY, BALL_SHOT_START, BALL_TRACKLET_START = 1, 2, 4
+BALL_RECOVER_DEFAULT, BALL_RECOVER_DOUBLING, BALL_RECOVER_CHASE = 0, 1, 2
+BALL_FRAME_DTYPE = np.dtype([("cand", "<i4"), ("det", "<i4"), ("tracklet", "<i4"), ("flags", "<i4"), ("qx", "<i4"), ("qy", "<i4"), ("f", "<i8")])     # EagleBallFrame (32 bytes)
+BALL_TRACKLET_DTYPE = np.dtype([("first", "<i4"), ("last", "<i4"), ("shot", "<i4"), ("sightings", "<i4"), ("sum_cq", "<i8"), ("length", "<i8"), ("gain", "<i8"),
+                                ("reserved", "<i4", 2)])                                                                                               # EagleBallTracklet (48 bytes)
+BALL_CLIP_DTYPE = np.dtype([("frames_with", "<i4"), ("frames_chosen", "<i4"), ("rejected", "<i4"), ("frames_multi", "<i4"), ("tracklets", "<i4"), ("shots", "<i4"),
+                            ("ignored", "<i4"), ("reserved", "<i4"), ("score", "<i8"), ("V", "<i4"), ("G", "<i4"), ("R0", "<i4"), ("B", "<i4"), ("reserved2", "<i4", 2)])  # EagleBallClip (64 bytes)
+assert C.sizeof(EagleBallTrackParams) == 64 and (BALL_FRAME_DTYPE.itemsize, BALL_TRACKLET_DTYPE.itemsize, BALL_CLIP_DTYPE.itemsize) == (32, 48, 64)    # balltrack.hip asserts them too
+
+
 class EagleShotParams(C.Structure):
     """include/eagle.h EagleShotParams: cut, low and grass_thr in 1 / 65536, the window W in frames, the least length of a usable shot in frames."""
     _fields_ = [("cut", C.c_int32), ("low", C.c_int32), ("grass_thr", C.c_int32), ("window", C.c_int32), ("min_len", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -444,6 +462,14 @@ def load():
     L.eagle_post_offside_events.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_post_device_offside.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.eagle_op_offside.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, i32, ofp, vp, i32, vp, vp, vp, vp, vp]
+    btp = C.POINTER(EagleBallTrackParams)
+    L.eagle_ball_track.argtypes = [vp, vp, i32, vp, i32, btp, C.POINTER(vp)]
+    L.eagle_ball_track_values.argtypes = [vp, vp, vp]
+    L.eagle_ball_track_tracklets.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_ball_track_free.argtypes = [vp]
+    L.eagle_ball_track_free.restype = None
+    L.eagle_op_ball_track.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, i32, btp, i32, vp, vp, i32, vp, vp]
+    L.eagle_postprocess_ball.argtypes = [vp, vp, i32, C.POINTER(EaglePostParams), vp, C.POINTER(vp)]
     shp = C.POINTER(EagleShotParams)
     L.eagle_shots_device_frames.argtypes = [vp, vp, i32, shp, vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_shots_frames.argtypes = [vp, vp, i32, i64, i64, i64, shp, vp, vp, i32, C.POINTER(C.c_int)]
@@ -507,7 +533,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_physical_totals", "eagle_post_physical_efforts", "eagle_post_device_physical", "eagle_op_physical", "eagle_post_roles",
            "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
            "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_post_offside", "eagle_post_offside_values", "eagle_post_offside_events",
-           "eagle_post_device_offside", "eagle_op_offside", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
+           "eagle_post_device_offside", "eagle_op_offside", "eagle_ball_track", "eagle_ball_track_values", "eagle_ball_track_tracklets", "eagle_ball_track_free",
+           "eagle_op_ball_track", "eagle_postprocess_ball", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
            "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
            "eagle_op_topview", "eagle_ground_device_frames", "eagle_ground_frames", "eagle_op_ground", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
@@ -955,17 +982,46 @@ class Handle:
         return out
 
     # --- the clip post-processor (include/eagle.h, eagle_postprocess) -------------------------------------------
-    def postprocess(self, recs, fps, frame_w, team_mapping=None, smooth=False, filter_ball=False, max_bytes=0, merge_ids=False):
+    def postprocess(self, recs, fps, frame_w, team_mapping=None, smooth=False, filter_ball=False, max_bytes=0, merge_ids=False, ball_det=None):
         """The records of a finished clip -> a PostTable (the reference's Processor.process_data table, built on the GPU and resident there).
         merge_ids: stitch the fragments of one person under several tracker ids into one column (include/eagle.h; False, 0: the reference as written,
-        which never merges); the table's ``merges`` list what was joined and its ``team_mapping`` gains the teams the heads inherit."""
+        which never merges); the table's ``merges`` list what was joined and its ``team_mapping`` gains the teams the heads inherit.
+        ball_det: per record -1 or the index of the one reported ball detection that counts (ball_track's ``det``; include/eagle.h,
+        eagle_postprocess_ball); None: the reference's choice."""
         recs = np.ascontiguousarray(recs, RESULT_DTYPE).reshape(-1)
         ids, vals, nt = _team_arrays(team_mapping)
         p = EaglePostParams(int(fps), int(frame_w), int(bool(smooth)), int(filter_ball), None if ids is None else ids.ctypes.data, None if vals is None else vals.ctypes.data,
                             nt, int(merge_ids), int(max_bytes))                 # (the struct's ``reserved`` field carries merge_ids)
         t = C.c_void_p()
-        self._check(self.L.eagle_postprocess(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), C.byref(p), C.byref(t)), "postprocess")
+        if ball_det is None:
+            self._check(self.L.eagle_postprocess(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), C.byref(p), C.byref(t)), "postprocess")
+        else:
+            ball_det = np.ascontiguousarray(ball_det, np.int32).reshape(-1)
+            if len(ball_det) != len(recs):
+                raise ValueError(f"ball_det has {len(ball_det)} entries for {len(recs)} records")
+            self._check(self.L.eagle_postprocess_ball(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), C.byref(p), ball_det.ctypes.data_as(C.c_void_p), C.byref(t)),
+                        "postprocess_ball")
         return PostTable(self, t, team_mapping)
+
+    # --- the ball track (include/eagle.h, eagle_ball_track) ---------------------------------------------------------------------
+    def ball_track(self, recs, params, cuts=None):
+        """Which reported ball detection of every record lies on the best path through the clip -> (BALL_FRAME_DTYPE [n], BALL_TRACKLET_DTYPE [tracklets],
+        BALL_CLIP_DTYPE [1]); params ball_track_params(...), cuts the sorted frames that start a new shot.  ``frames["det"]`` is postprocess's ball_det."""
+        recs = np.ascontiguousarray(recs, RESULT_DTYPE).reshape(-1)
+        cuts = np.zeros(0, np.int32) if cuts is None else np.ascontiguousarray(cuts, np.int32).reshape(-1)
+        t = C.c_void_p()
+        self._check(self.L.eagle_ball_track(self._h, recs.ctypes.data_as(C.c_void_p), len(recs), cuts.ctypes.data_as(C.c_void_p) if len(cuts) else None, len(cuts),
+                                            C.byref(params), C.byref(t)), "ball_track")
+        try:
+            frames, clip, n = np.zeros(len(recs), BALL_FRAME_DTYPE), np.zeros(1, BALL_CLIP_DTYPE), C.c_int(0)
+            keep = np.zeros(4, np.float64)
+            self._check(self.L.eagle_ball_track_values(t, _ptr(frames, keep), _ptr(clip, keep)), "ball_track_values")
+            self._check(self.L.eagle_ball_track_tracklets(t, None, 0, C.byref(n)), "ball_track_tracklets")
+            tracklets = np.zeros(n.value, BALL_TRACKLET_DTYPE)
+            self._check(self.L.eagle_ball_track_tracklets(t, _ptr(tracklets, keep), n.value, C.byref(n)), "ball_track_tracklets")
+        finally:
+            self.L.eagle_ball_track_free(t)
+        return frames, tracklets, clip
 
     # --- the minimap (include/eagle.h, eagle_minimap_*) ------------------------------------------------------------
     def minimap_device(self, table, d_out, params, row0=0, n=None, fmt="bgr", layout=None):
@@ -2437,6 +2493,39 @@ def op_offside(values, columns, team_mapping, params=None, events=None, frames=N
     if rc:
         raise EagleError(f"eagle_op_offside failed ({rc}): {L.eagle_last_error(None).decode()}")
     return rec, mg, totals, clip, ev
+
+
+def ball_track_params(fps, frame_w, speed=0.0, gap=0, reward=0.0, brk=0.0, max_bytes=0):
+    """EagleBallTrackParams; speed, reward and brk in pixels, gap in frames, 0: the default (a tenth of the frame's width, min(64, fps) frames, the speed, two
+    and a half rewards: conventional choices, not fitted to data)."""
+    p = EagleBallTrackParams()
+    p.fps, p.frame_w, p.gap, p.speed, p.reward, p.brk, p.max_bytes = int(fps), int(frame_w), int(gap), float(speed), float(reward), float(brk), int(max_bytes)
+    return p
+
+
+def op_ball_track(counts, positions, cq, params, cuts=None, conf=None, det=None, recover=BALL_RECOVER_DEFAULT, times=False, device=0):
+    """The ball-track launches on constructed candidates (include/eagle.h eagle_op_ball_track): counts int32 [n], positions int32 [sum, 2] half pixels, cq int32
+    [sum] (or None with conf float32 [sum]), det int32 [sum] or None -> (BALL_FRAME_DTYPE [n], BALL_TRACKLET_DTYPE [tracklets], BALL_CLIP_DTYPE [1]), with
+    times=True also the four device times in milliseconds (recurrence, recovery, rows, all)."""
+    L = load()
+    counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    n, total = len(counts), int(counts.astype(np.int64).sum())
+    positions = np.ascontiguousarray(positions, np.int32).reshape(-1, 2)
+    cq = None if cq is None else np.ascontiguousarray(cq, np.int32).reshape(-1)
+    conf = None if conf is None else np.ascontiguousarray(conf, np.float32).reshape(-1)
+    det = None if det is None else np.ascontiguousarray(det, np.int32).reshape(-1)
+    for a, what in ((positions, "positions"), (cq, "cq"), (conf, "conf"), (det, "det")):
+        if a is not None and len(a) != total:
+            raise ValueError(f"op_ball_track: {what} has {len(a)} entries for {total} candidates")
+    cuts = np.zeros(0, np.int32) if cuts is None else np.ascontiguousarray(cuts, np.int32).reshape(-1)
+    frames, tracklets, clip, ms = np.zeros(n, BALL_FRAME_DTYPE), np.zeros(n, BALL_TRACKLET_DTYPE), np.zeros(1, BALL_CLIP_DTYPE), np.zeros(4, np.float32)
+    keep = np.zeros(16, np.float64)
+    rc = L.eagle_op_ball_track(device, _ptr(counts, keep), n, _ptr(positions, keep), _ptr(cq, keep), _ptr(conf, keep), _ptr(det, keep), _ptr(cuts, keep) if len(cuts) else None,
+                               len(cuts), C.byref(params), int(recover), _ptr(frames, keep), _ptr(tracklets, keep), n, _ptr(clip, keep), _ptr(ms, keep) if times else None)
+    if rc:
+        raise EagleError(f"eagle_op_ball_track failed ({rc}): {L.eagle_last_error(None).decode()}")
+    out = frames, tracklets[:int(clip[0]["tracklets"])].copy(), clip
+    return out + (ms,) if times else out
 
 
 def shot_params(cut=None, low=None, grass_thr=None, window=None, min_len=None, fps=25):

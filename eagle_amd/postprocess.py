@@ -8,15 +8,17 @@ import math
 from . import lib
 
 
-def process_data(handle, records, fps, frame_w, team_mapping, smooth=False, filter_ball_detections=False, merge_ids=False):
+def process_data(handle, records, fps, frame_w, team_mapping, smooth=False, filter_ball_detections=False, merge_ids=False, ball_det=None):
     """records: the EagleFrameResult array of the clip (record i = frame i); team_mapping: {player id: 0 | 1} (Processor.get_team_mapping) or None.
     -> lib.PostTable.  filter_ball_detections=True is refused: it needs cv2's Kalman gain, which this project cannot pin.
     merge_ids=True stitches the fragments of one person under several tracker ids into one column (the merge the reference's ``merge_data`` was
     meant to do, as a rule of this project's own: include/eagle.h, tests/stitch_ref.py); the table's ``merges`` list the joins and its
-    ``team_mapping`` holds the teams the chains' heads inherit.  The default is the reference as written: no id is ever merged."""
+    ``team_mapping`` holds the teams the chains' heads inherit.  The default is the reference as written: no id is ever merged.
+    ball_det: per record -1 or the index of the one reported ball detection that counts (the ``det`` of eagle_amd/balltrack.py's frame records); the
+    table is then the one built from records without any other ball detection.  None: the reference's choice of ball."""
     if filter_ball_detections:
         raise NotImplementedError("filter_ball_detections=True is not supported: the reference's ball filter needs cv2.KalmanFilter.correct (unpinned)")
-    return handle.postprocess(records, fps, frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids)
+    return handle.postprocess(records, fps, frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids, ball_det=ball_det)
 
 
 def _cell(v):

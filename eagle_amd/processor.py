@@ -35,18 +35,29 @@ class Processor:
         finally:
             self.model.handle.free(d)
 
-    def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False):
+    def ball_track(self, records, fps, cuts=None, speed=None, gap=None, reward=None, brk=None):
+        """Which ball detection of every frame lies on the best physically possible path through the clip (cuts: the frames that start a new shot)
+        -> (frame records, tracklets, clip totals): see eagle_amd/balltrack.py."""
+        from . import balltrack as bt
+        return bt.track(self.model.handle, self.model._records_of(records), fps, self.model.handle.cfg.frame_w, cuts, speed, gap, reward, brk)
+
+    def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False, ball_track=False, cuts=None):
         """The reference post-processor's ``process_data`` (eagle/processor.py:73-87) for a clip and its ``get_coordinates`` output (or raw
         records): the team mapping (get_team_mapping above), then the interpolated, goalkeeper-folded, optionally smoothed table, built on the GPU
         (eagle_amd/postprocess.py).  -> (table, team_mapping); postprocess.raw_data_rows / format_data turn the table into main.py's two JSON files.
-        merge_ids: stitch fragmented tracker ids (postprocess.process_data); the returned mapping then includes the teams the merged ids inherit."""
+        merge_ids: stitch fragmented tracker ids (postprocess.process_data); the returned mapping then includes the teams the merged ids inherit.
+        ball_track: True, or a dict of ball_track's settings (speed, gap, reward, brk): the table's ball is the tracked one (ball_track above, with
+        ``cuts``) instead of the reference's choice; the track is kept as ``table.ball_track``."""
         from . import postprocess
         coords = coords_or_records
         if not isinstance(coords, dict):
             coords = {i: records.to_reference_dict(r, i, fps) for i, r in enumerate(np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1))}
         recs = self.model._records_of(coords_or_records)
         team_mapping = self.get_team_mapping(frames, coords, pixel_format) if len(recs) else {}
-        table = postprocess.process_data(self.model.handle, recs, fps, self.model.handle.cfg.frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids)
+        track = self.ball_track(recs, fps, cuts, **(ball_track if isinstance(ball_track, dict) else {})) if ball_track else None
+        table = postprocess.process_data(self.model.handle, recs, fps, self.model.handle.cfg.frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids,
+                                         ball_det=None if track is None else track[0]["det"])
+        table.ball_track = track
         return table, table.team_mapping if merge_ids else team_mapping
 
     def shots(self, frames, fps, pixel_format="bgr", **overrides):

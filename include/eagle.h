@@ -974,6 +974,98 @@ int eagle_op_offside(int device, const double* values, const int32_t* frames, co
                      const int32_t* team_vals, int n_team, const EagleOffsideParams* p, const EaglePossessionEvent* events, int n_events,
                      EagleOffsideRow* rows_out, int32_t* margins, EagleOffsideTotals* totals_out, EagleOffsideClip* clip_out, EagleOffsideEvent* events_out);
 
+/* ---- ball track: which ball detection of every frame lies on the best physically possible path through the clip (own specification:
+ * tests/balltrack_ref.py defines every output bit) ----
+ * eagle_postprocess takes a frame's only ball detection whatever it is and, of several, the one nearest the image origin (above: the reference's
+ * parse_ball_detections_with_kalman(filter=False)).  This stage is the library's own, opt-in answer: over the whole clip it takes the sequence of
+ * candidates that forms the best path; isolated false positives drop out (the table then interpolates over them), a frame with several candidates is
+ * decided by the frames around it, a camera cut (eagle_shots_frames) breaks the path.  Integers only: no order of accumulation exists.
+ *   NODES      frame i of the n records: its reported ball detections (cls == 2, reported) in eagle_postprocess's order (one per id, the later record of
+ *              an id in the earlier one's place, then stably by descending conf).  The first EAGLE_BALL_MAX_CAND are nodes (i, 0 ..); the others are
+ *              ignored and the frame is flagged.  Position in half pixels, exact: qx = (bx1 & 0xFFFF) + (bx2 & 0xFFFF), qy = 2 (by2 & 0xFFFF), the image
+ *              point of eagle_postprocess.  cq = floor(conf * 1024); conf must be finite and within [0, 1].
+ *   PARAMETERS resolved to integers, pixels as floor(2 v + 0.5) half pixels; 0 stands for the default: V half pixels per frame (speed; 0.1 frame_w
+ *              pixels, the reference filter's threshold), G frames (gap, 1 .. 64; min(64, fps)), R0 (reward; V) and B (brk; (5 R0) >> 1).  Conventional
+ *              choices, not fitted to data: a sighting of confidence 1 pays for any admissible one-frame step, and a track needs about three sightings
+ *              to pay for itself.
+ *   SCORE      R(i, a) = (cq R0) >> 10.  A link (i, a) -> (j, b) is admissible when i < j <= i + G, both frames lie in one shot (cuts: the sorted
+ *              frames that start a new shot) and d2 = dx dx + dy dy <= (V (j - i))^2 (int64); it costs isqrt(d2), the exact floor.  Per shot, with
+ *              P(-1) = 0:  f(j, b) = R(j, b) + max(P(j - 1) - B, max over admissible links of f(i, a) - cost),  P(j) = max(P(j - 1), max_b f(j, b)).
+ *   TIES       a link is taken when it is at least as good as the break; among links the larger i wins, then the smaller a; P's arg-max moves only on a
+ *              strictly greater f, within a frame to the lowest b; a break's predecessor is that arg-max when P(j - 1) > 0, otherwise it has none.
+ *   CHOSEN     per shot with P(end) > 0 the predecessors back from the arg-max.  A tracklet is a maximal run of chosen nodes joined by links, numbered
+ *              from 0 in frame order; its gain is its rewards minus its links' costs minus B, and the gains add up to the clip's score, the sum of the
+ *              shots' P(end).
+ * Launches (balltrack.hip): the recurrence with one wave per piece of the timeline (a shot, cut further at its runs of at least G frames without a
+ * candidate, which no link crosses), the pieces chained per shot, the chosen nodes marked by pointer doubling, then rows, a prefix sum of the tracklet
+ * starts, the tracklets and the totals.  Host C++ stages the candidates.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output and an earlier result alone: NULL pointers (parameters, the result; recs,
+ * counts, positions with n > 0; cuts with n_cuts > 0; neither cq nor conf), n < 0 or n > 2^20, an n_det outside 0 .. EAGLE_MAX_DET (a count outside
+ * it), cuts that are unsorted, repeated or outside 1 .. n - 1, fps or frame_w not positive, gap outside 0 .. 64, a speed, reward or brk that is not
+ * finite, is negative or exceeds 65535 / 65535 / 2^20 pixels, a frame_w whose default speed exceeds 65535 pixels, non-zero reserved words, a conf
+ * outside [0, 1] or not finite, a position outside 0 .. 131070, a cq outside 0 .. 1024, a device-memory need beyond the budget (max_bytes; 0: nine tenths of what is
+ * free).  n == 0 succeeds and writes nothing. */
+#define EAGLE_BALL_MAX_CAND 8
+#define EAGLE_BALL_TOO_MANY 1          /* EagleBallFrame::flags: the frame had more candidates than EAGLE_BALL_MAX_CAND */
+#define EAGLE_BALL_SHOT_START 2        /* frame 0 and every cut */
+#define EAGLE_BALL_TRACKLET_START 4    /* the chosen node was reached by a break, or by nothing */
+#define EAGLE_BALL_RECOVER_DEFAULT 0   /* eagle_op_ball_track's `recover`: how the chosen nodes are found; the default is the faster at 30 000 frames */
+#define EAGLE_BALL_RECOVER_DOUBLING 1  /* jump tables by pointer doubling, marking from the end nodes with the powers high to low */
+#define EAGLE_BALL_RECOVER_CHASE 2     /* one lane per shot follows the predecessors */
+typedef struct EagleBallTrack EagleBallTrack;
+typedef struct EagleBallTrackParams {
+    int32_t fps, frame_w;          /* > 0 */
+    int32_t gap;                   /* G in frames, 1 .. 64; 0: min(64, fps) */
+    int32_t reserved[5];           /* 0 */
+    double speed, reward, brk;     /* pixels (per frame); 0: the default */
+    int64_t max_bytes;             /* device-memory budget of the call, 0 = nine tenths of what is free */
+} EagleBallTrackParams;            /* 64 bytes */
+typedef struct EagleBallFrame {
+    int32_t cand;                  /* the chosen node's index among the frame's candidates, -1: none */
+    int32_t det;                   /* the index in EagleFrameResult::det it came from (eagle_op_ball_track: what `det` holds, -1 without), -1: none */
+    int32_t tracklet;              /* -1: none */
+    int32_t flags;                 /* EAGLE_BALL_TOO_MANY | _SHOT_START | _TRACKLET_START */
+    int32_t qx, qy;                /* half pixels; 0 without a chosen node */
+    int64_t f;                     /* the recurrence's value at the chosen node; 0 without */
+} EagleBallFrame;                  /* 32 bytes */
+typedef struct EagleBallTracklet {
+    int32_t first, last;           /* frames */
+    int32_t shot, sightings;
+    int64_t sum_cq;
+    int64_t length;                /* the links' costs, half pixels */
+    int64_t gain;                  /* rewards - length - B */
+    int32_t reserved[2];
+} EagleBallTracklet;               /* 48 bytes */
+typedef struct EagleBallClip {
+    int32_t frames_with;           /* frames with at least one candidate */
+    int32_t frames_chosen;
+    int32_t rejected;              /* nodes that were not chosen */
+    int32_t frames_multi;          /* frames with several candidates */
+    int32_t tracklets, shots;
+    int32_t ignored;               /* candidates beyond EAGLE_BALL_MAX_CAND of their frame */
+    int32_t reserved;
+    int64_t score;
+    int32_t V, G, R0, B;           /* the resolved parameters */
+    int32_t reserved2[2];
+} EagleBallClip;                   /* 64 bytes */
+/* The result is kept on the host with *out until eagle_ball_track_free; the launches run on the handle's main stream.  cuts may be NULL with n_cuts == 0. */
+int eagle_ball_track(EagleHandle* h, const EagleFrameResult* recs, int n, const int32_t* cuts, int n_cuts, const EagleBallTrackParams* p, EagleBallTrack** out);
+int eagle_ball_track_values(const EagleBallTrack* t, EagleBallFrame* frames_out /* [n] */, EagleBallClip* clip_out);        /* either may be NULL */
+int eagle_ball_track_tracklets(const EagleBallTrack* t, EagleBallTracklet* out, int cap, int* n);                           /* *n = their number; at most cap are written */
+void eagle_ball_track_free(EagleBallTrack* t);
+/* Operator entry (host buffers in / out, no handle): counts [n] candidates per frame (0 .. EAGLE_MAX_DET), positions [sum of counts][2] half pixels and
+ * cq [sum] (or, with cq NULL, conf [sum] float32) frame after frame in descending confidence, det [sum] or NULL.  Every output may be NULL; at most cap
+ * tracklets are written (EagleBallClip::tracklets is their number).  times_ms (may be NULL): device events around the recurrence with its chaining, the
+ * recovery of the chosen nodes, the row / prefix-sum / tracklet launches, and all of them. */
+int eagle_op_ball_track(int device, const int32_t* counts, int n, const int32_t* positions, const int32_t* cq, const float* conf, const int32_t* det,
+                        const int32_t* cuts, int n_cuts, const EagleBallTrackParams* p, int recover, EagleBallFrame* frames_out, EagleBallTracklet* tracklets_out,
+                        int cap, EagleBallClip* clip_out, float* times_ms /* [4] */);
+/* eagle_postprocess with the ball of frame i given: ball_det[i] is -1 (no ball) or the index of a reported ball detection of record i (EagleBallFrame::det).
+ * The table is the one eagle_postprocess builds from records in which every other reported ball detection is dropped, so fewer than two sightings still
+ * give EAGLE_POST_NO_BALL, and Ball and Ball_video of a row come from the same detection.  ball_det == NULL is eagle_postprocess exactly.  A ball_det
+ * entry that is not a reported ball detection of its record is EAGLE_E_INVALID, before anything is built. */
+int eagle_postprocess_ball(EagleHandle* h, const EagleFrameResult* recs, int n, const EaglePostParams* p, const int32_t* ball_det, EaglePostTable** out);
+
 /* ---- shots: the camera cuts, gradual transitions and photo flashes of a clip, and which of its shots look at the pitch (own specification:
  * tests/shots_ref.py defines every output bit) ----
  * The stage in front of the networks: every other stage assumes one continuous shot of the main camera.  Input: n dense BGR frames [h][w][3], P = h w.
