@@ -415,6 +415,57 @@ int eagle_op_flow(int device, const uint8_t* bgr, int n, int h, int w, int src_f
     API_END(hh)
 }
 
+// ---- the ECC camera-motion kernels (ecc.hip, K17) without a handle (tests/test_gpu_ecc_ops.py) ---------------------------------------------
+int eagle_op_ecc_small(int device, const uint8_t* gray, int n, int h, int w, double scale, uint8_t* small_out, int* dh_out, int* dw_out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (!gray || !dh_out || !dw_out || n < 1 || h < 1 || w < 1 || !(scale > 0.0) || !(scale <= 1.0))
+        fail(EAGLE_E_INVALID, "eagle_op_ecc_small: n >= 1 gray frames and 0 < scale <= 1 required (n %d, %d x %d, scale %g)", n, h, w, scale);
+    const int dh = (int)lrint(h * scale), dw = (int)lrint(w * scale);      // as eagle_clip_motion_ecc
+    if (dh < 4 || dw < 4) fail(EAGLE_E_INVALID, "eagle_op_ecc_small: frame too small for the %g-scale alignment (%d x %d -> %d x %d)", scale, h, w, dh, dw);
+    *dh_out = dh; *dw_out = dw;
+    if (!small_out) return EAGLE_OK;                      // the size query
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const uint8_t* d = (const uint8_t*)net.upload(gray, (size_t)n * h * w);
+    uint8_t* s = (uint8_t*)net.get((size_t)n * dh * dw);
+    ecc_small_launch(d, s, n, h, w, dh, dw, 1.0 / scale, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(small_out, s, (size_t)n * dh * dw, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
+int eagle_op_ecc(int device, const uint8_t* small, int n, int h, int w, const uint8_t* carry, const int32_t* pairs, int n_pairs, int max_iter, double eps,
+                 EagleEccResult* out)
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    static_assert(sizeof(EagleEccResult) == sizeof(EccResult) && offsetof(EagleEccResult, rho) == offsetof(EccResult, rho) &&
+                  offsetof(EagleEccResult, M) == offsetof(EccResult, M), "EagleEccResult mirrors EccResult");
+    if (!small || n < 1 || h < 4 || w < 4) fail(EAGLE_E_INVALID, "eagle_op_ecc: n >= 1 images of at least 4 x 4 pixels required (n %d, %d x %d)", n, h, w);
+    if (max_iter < 0 || max_iter > 100 || n_pairs < 0 || n_pairs > 4096 || !(eps == eps))
+        fail(EAGLE_E_INVALID, "eagle_op_ecc: 0 <= max_iter <= 100 and 0 <= n_pairs <= 4096 required (max_iter %d, n_pairs %d)", max_iter, n_pairs);
+    if (n_pairs == 0) return EAGLE_OK;
+    if (!pairs || !out) fail(EAGLE_E_INVALID, "eagle_op_ecc: null argument");
+    for (int k = 0; k < n_pairs; ++k) {
+        const int t = pairs[2 * k], i = pairs[2 * k + 1];
+        if (i < 0 || i >= n || t < -1 || t >= n || (t == -1 && !carry))
+            fail(EAGLE_E_INVALID, "eagle_op_ecc: pair %d = (%d, %d): images inside [0, %d), the template -1 only with a carried image", k, t, i, n);
+    }
+    HIP_CHECK(hipSetDevice(device));
+    Net net;
+    const size_t npx = (size_t)h * w;
+    const uint8_t* d = (const uint8_t*)net.upload(small, (size_t)n * npx);
+    const uint8_t* dc = carry ? (const uint8_t*)net.upload(carry, npx) : nullptr;
+    const int2* dp = (const int2*)net.upload(pairs, sizeof(int2) * (size_t)n_pairs);
+    EccResult* dr = (EccResult*)net.get(sizeof(EccResult) * (size_t)n_pairs);
+    ecc_launch(d, dc, dp, n_pairs, dr, h, w, max_iter, eps, nullptr);     // one launch for all pairs
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, dr, sizeof(EccResult) * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    API_END(hh)
+}
+
 // ---- the OSNet (ReID) kernels of reid.hip one launch at a time (tests/test_gpu_reid_ops.py) ------------------------------------------------
 // Every activation operand is a slice view: `c` channels at channel `off` of a buffer with `cs` floats per pixel.  Whatever lies outside the
 // slice holds EAGLE_OP_SENTINEL_BITS (a quiet NaN) when the kernel starts, and output buffers come back whole: a read outside an input slice

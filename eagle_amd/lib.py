@@ -508,6 +508,8 @@ def load():
     L.eagle_op_split_to_f32.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, i32, i32, fp]
     L.eagle_op_gray_pyramid.argtypes = [i32, u8p, i32, i32, i32, u8p, u8p, u8p, C.POINTER(i32)]
     L.eagle_op_flow.argtypes = [i32, u8p, i32, i32, i32, i32, i32, i32, vp, i32, vp, C.POINTER(i32), fp, u8p]
+    L.eagle_op_ecc_small.argtypes = [i32, u8p, i32, i32, i32, C.c_double, u8p, C.POINTER(i32), C.POINTER(i32)]
+    L.eagle_op_ecc.argtypes = [i32, u8p, i32, i32, i32, u8p, C.POINTER(i32), i32, i32, C.c_double, vp]
     _lib = L
     return L
 
@@ -538,9 +540,10 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
            "eagle_op_topview", "eagle_ground_device_frames", "eagle_ground_frames", "eagle_op_ground", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
-           "eagle_op_flow"]
+           "eagle_op_flow", "eagle_op_ecc_small", "eagle_op_ecc"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
+ECC_DTYPE = np.dtype([("ok", "<i4"), ("iters", "<i4"), ("rho", "<f8"), ("M", "<f4", (6,))], align=True)      # EagleEccResult
 E_REFERENCE_RAISES = -7
 E_RANGE = -8
 
@@ -2373,6 +2376,41 @@ def op_flow(frames, src_frame, dst_frame, hue_frame, kps, device=0):
     if rc:
         raise EagleError(f"eagle_op_flow failed ({rc}): {L.eagle_last_error(None).decode()}")
     return out[: n_out.value].copy(), nxt[: len(kps)], st[: len(kps)]
+
+
+# --- the ECC camera-motion kernels without a handle (include/eagle.h eagle_op_ecc_small / eagle_op_ecc) --------------------------
+def op_ecc_small(gray, scale=0.15, device=0):
+    """ecc_small_kernel (csrc/ecc.hip, K17) on gray u8 frames [n, h, w] -> u8 [n, dh, dw], the scale-sized images of eagle_clip_motion_ecc
+    (dh = round(h * scale), dw = round(w * scale)); an EagleError below 4 x 4."""
+    L = load()
+    gray = np.ascontiguousarray(gray, np.uint8)
+    n, h, w = gray.shape
+    dh, dw = C.c_int(0), C.c_int(0)
+    rc = L.eagle_op_ecc_small(device, _u8p(gray), n, h, w, float(scale), None, C.byref(dh), C.byref(dw))
+    out = np.zeros((n, dh.value, dw.value), np.uint8)
+    if not rc:
+        rc = L.eagle_op_ecc_small(device, _u8p(gray), n, h, w, float(scale), _u8p(out), C.byref(dh), C.byref(dw))
+    if rc:
+        raise EagleError(f"eagle_op_ecc_small failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
+
+
+def op_ecc(small, pairs, carry=None, max_iter=100, eps=1e-5, device=0):
+    """ecc_kernel (csrc/ecc.hip, K17), one launch: small u8 [n, h, w], pairs int32 [n_pairs, 2] of (template, image) indices, the template -1
+    being `carry` u8 [h, w] -> ECC_DTYPE [n_pairs], the kernel's raw results (M in the pixels of `small`)."""
+    L = load()
+    small = np.ascontiguousarray(small, np.uint8)
+    n, h, w = small.shape
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    if carry is not None:
+        carry = np.ascontiguousarray(carry, np.uint8)
+        assert carry.shape == (h, w)
+    out = np.zeros(len(pairs), ECC_DTYPE)
+    rc = L.eagle_op_ecc(device, _u8p(small), n, h, w, None if carry is None else _u8p(carry), pairs.ctypes.data_as(C.POINTER(C.c_int32)), len(pairs),
+                        int(max_iter), float(eps), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EagleError(f"eagle_op_ecc failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
 
 
 # --- trails, pass arrows and the owner ring; the trajectory and the pass still -------------------------------------------------

@@ -1544,6 +1544,21 @@ int eagle_op_gray_pyramid(int device, const uint8_t* bgr, int n, int h, int w, u
 int eagle_op_flow(int device, const uint8_t* bgr, int n, int h, int w, int src_frame, int dst_frame, int hue_frame, const EagleFlowKp* in, int n_in,
                   EagleFlowKp* out /* EAGLE_N_LANDMARKS */, int* n_out, float* next_pts /* 2*n_in or NULL */, uint8_t* status /* n_in or NULL */);
 
+/* The ECC camera-motion kernels (ecc.hip, K17) without a handle: the two launches of eagle_clip_motion_ecc, each alone.
+ * eagle_op_ecc_small: n gray frames [h][w] (the clip session's gray level 0) -> the scale-sized images [n][dh][dw] that cv2.resize((0, 0), fx = fy = scale)
+ * gives, dh = lrint(h * scale), dw = lrint(w * scale), the taps taken from 1 / scale.  *dh_out, *dw_out are always written; small_out = NULL only asks for
+ * them.  EAGLE_E_INVALID for dh < 4 or dw < 4, as eagle_clip_motion_ecc, and for a scale outside (0, 1].
+ * eagle_op_ecc: findTransformECC(template, image, eye(2, 3), MOTION_EUCLIDEAN, (EPS | COUNT, max_iter, eps)) of n_pairs (template, image) index pairs into
+ * small [n][h][w], all in ONE launch; the template index -1 is the image `carry` [h][w].  out[k] is the kernel's raw result: ok = 0 where cv2 raises (no pixel
+ * inside the mask, a NaN correlation, lambda_d <= 0) and then iters counts the iteration that failed and rho, M are not meaningful; otherwise iters is the
+ * number of iterations run, rho the last correlation (-1 with max_iter = 0) and M the 2 x 3 warp in the pixels of `small` (the translation NOT divided by
+ * the scale).  EAGLE_E_INVALID for h < 4, w < 4, n < 1, an index outside [0, n), -1 without carry, max_iter outside [0, 100] and n_pairs outside [0, 4096];
+ * n_pairs = 0 returns at once. */
+typedef struct EagleEccResult { int32_t ok, iters; double rho; float M[6]; } EagleEccResult;
+int eagle_op_ecc_small(int device, const uint8_t* gray, int n, int h, int w, double scale, uint8_t* small_out /* n*dh*dw or NULL */, int* dh_out, int* dw_out);
+int eagle_op_ecc(int device, const uint8_t* small, int n, int h, int w, const uint8_t* carry /* h*w or NULL */, const int32_t* pairs /* 2*n_pairs */, int n_pairs,
+                 int max_iter, double eps, EagleEccResult* out /* n_pairs */);
+
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
  * Keys: "lk_threads" (64 | 256), "lk_dbg" (1 trace, 2 LDS guard words, 4 end-of-level verification, 8 L1-bypassing loads), "lk_excl_lds" (bytes), "lk_trace", "lk_counters". */
