@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--team-method cluster`` (with ``--processed`` or ``--annotated``) finds the team mapping as the two clusters of the ids' kit colours over the clip instead of by the reference's named colour ranges, and writes ``teams.json`` (eagle_amd/kits.py; ``--team-min-pixels``, ``--team-min-crops``, ``--team-outlier`` set the rule).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -205,6 +205,15 @@ def main(argv=None):
     ap.add_argument("--ball-track-break", type=float, default=None, metavar="PX",
                     help="with --ball-track: what it costs to break the path off and start again, in pixels, > 0 and <= 1048576 (default two and a half rewards)")
     ap.add_argument("--ball-track-rows", action="store_true", help="with --ball-track: also write the record of every frame into ball_track.json")
+    ap.add_argument("--team-method", choices=("colours", "cluster"), default="colours",
+                    help="with --processed or --annotated: how the team mapping is found.  colours (the default): the reference's rule, named colour ranges and the two "
+                         "most common names.  cluster: the two clusters of the ids' kit colours over the clip, which separates two kits of one colour name and leaves "
+                         "a referee in neither team; also write <out>/teams.json (eagle_amd/kits.py)")
+    ap.add_argument("--team-min-pixels", type=int, default=None, metavar="N", help="with --team-method cluster: the least counted pixels of a crop's shirt window, 1 .. 1048576 (default 32)")
+    ap.add_argument("--team-min-crops", type=int, default=None, metavar="N", help="with --team-method cluster: the least used crops of an id that votes, 1 .. 65536 (default 3)")
+    ap.add_argument("--team-outlier", type=float, default=None, metavar="R",
+                    help="with --team-method cluster: an id farther from its team's medoid than R times the distance between the medoids is in neither team, "
+                         "0 .. 1024, 0 = off (default 0.5)")
     ap.add_argument("--shots", action="store_true",
                     help="also write <out>/shots.json: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at "
                          "the pitch, and put the shot count into metadata.json (the thresholds are conventional choices, not fitted to footage)")
@@ -311,6 +320,20 @@ def main(argv=None):
             if v is not None and not 0.0 < v <= top:                      # (NaN fails too)
                 ap.error(f"--ball-track-{flag}: PX must be > 0 and <= {top:.0f} pixels")
         a.ball_track_set = {k: v for k, v in bt_set.items() if v is not None}
+    team_set = {"min_pixels": a.team_min_pixels, "min_crops": a.team_min_crops, "outlier": a.team_outlier}
+    if a.team_method != "cluster" and any(v is not None for v in team_set.values()):
+        ap.error("--team-min-pixels, --team-min-crops and --team-outlier set up the team clustering: they need --team-method cluster")
+    a.team_set = {}
+    if a.team_method == "cluster":
+        if not (a.processed or a.annotated):
+            ap.error("--team-method cluster chooses how the team mapping is found: it needs --processed or --annotated")
+        if a.team_min_pixels is not None and not 1 <= a.team_min_pixels <= 1048576:
+            ap.error("--team-min-pixels takes 1 .. 1048576 pixels")
+        if a.team_min_crops is not None and not 1 <= a.team_min_crops <= 65536:
+            ap.error("--team-min-crops takes 1 .. 65536 crops")
+        if a.team_outlier is not None and not 0.0 <= a.team_outlier <= 1024.0:                      # (NaN fails too)
+            ap.error("--team-outlier: R must be >= 0 and <= 1024 (--team-method cluster)")
+        a.team_set = {k: v for k, v in team_set.items() if v is not None}
     if a.offside and not a.processed:
         ap.error("--offside works on the processed table: it needs --processed")
     if not a.offside and (a.offside_rows or a.offside_no_assumed_keeper or a.offside_direction is not None or a.offside_tolerance is not None):
@@ -464,14 +487,21 @@ def main(argv=None):
         from . import postprocess
         from .annotate import write_y4m
         from .processor import Processor
+        team_kw = dict(team_method="cluster", team_params=a.team_set) if a.team_method == "cluster" else {}
         if a.ball_track:
             from . import balltrack as bt
             cuts = bt.cuts_of_shots(found_shots, first_frame, n) if found_shots is not None else None
-            table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids, ball_track=a.ball_track_set or True, cuts=cuts)
+            table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids, ball_track=a.ball_track_set or True, cuts=cuts,
+                                                                **team_kw)
             with open(os.path.join(a.out, "ball_track.json"), "w") as f:
                 json.dump(bt.to_json(*table.ball_track, rows=a.ball_track_rows), f)
         else:
-            table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids)
+            table, team_mapping = Processor(model).process_data(frames, coordinates, a.fps, smooth=a.smooth, merge_ids=a.merge_ids, **team_kw)
+        team_report = table.team_report                                    # None: the colours' rule, or a clip without records (no teams.json then)
+        if team_report is not None:
+            from . import kits
+            with open(os.path.join(a.out, "teams.json"), "w") as f:
+                json.dump(kits.to_json(team_report), f)
         merges = table.merges
         with open(os.path.join(a.out, "raw_data.json"), "w") as f:
             json.dump(postprocess.json_rows(postprocess.raw_data_rows(table)), f)
@@ -579,12 +609,23 @@ def main(argv=None):
             meta["merges"] = merges
         if a.ball_track:
             meta["ball"] = "ball_track"                                    # the table's ball is the tracked one (ball_track.json)
+        if team_report is not None:
+            meta["teams"] = "cluster"                                      # the mapping is the clustering's (teams.json)
     elif a.annotated:
         from .annotate import write_y4m
         from .processor import Processor
-        team_mapping = Processor(model).get_team_mapping(frames, coordinates)
+        if a.team_method == "cluster":
+            from . import kits
+            pr = Processor(model)
+            team_mapping = pr.get_team_mapping(frames, coordinates, method="cluster", **a.team_set)
+            with open(os.path.join(a.out, "teams.json"), "w") as f:
+                json.dump(kits.to_json(pr.team_report), f)
+        else:
+            team_mapping = Processor(model).get_team_mapping(frames, coordinates)
         write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420"), a.fps)
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
+        if a.team_method == "cluster":
+            meta["teams"] = "cluster"
     if a.topview:
         from . import topview as tv
         from .annotate import write_y4m

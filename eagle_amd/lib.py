@@ -171,6 +171,23 @@ BALL_CLIP_DTYPE = np.dtype([("frames_with", "<i4"), ("frames_chosen", "<i4"), ("
 assert C.sizeof(EagleBallTrackParams) == 64 and (BALL_FRAME_DTYPE.itemsize, BALL_TRACKLET_DTYPE.itemsize, BALL_CLIP_DTYPE.itemsize) == (32, 48, 64)    # balltrack.hip asserts them too
 
 
+class EagleKitParams(C.Structure):
+    """include/eagle.h EagleKitParams: the least counted pixels of a used crop, the least used crops of a voter, the outlier bound in 1/1024 of the
+    distance between the medoids (0: off)."""
+    _fields_ = [("min_pixels", C.c_int32), ("min_crops", C.c_int32), ("outlier", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+KIT_BINS, KIT_MAX_IDS = 34, 1024                                               # include/eagle.h EAGLE_KIT_*
+KIT_CROP_OUTSIDE, KIT_CROP_EMPTY, KIT_CROP_FEW = 1, 2, 4
+KIT_ID_WEAK, KIT_ID_NEITHER, KIT_ID_SINGLE = 1, 2, 4
+KIT_MODEL_SINGLE, KIT_MODEL_SWAPPED = 1, 2
+KIT_CROP_DTYPE = np.dtype([("units", "<u4", KIT_BINS), ("n", "<i4"), ("flags", "<i4")])                                                           # EagleKitCrop (144 bytes)
+KIT_ID_DTYPE = np.dtype([("used", "<i4"), ("skipped", "<i4"), ("team", "<i4"), ("flags", "<i4"), ("d", "<u4", 2), ("p", "<u4", KIT_BINS)])        # EagleKitId (160 bytes)
+KIT_MODEL_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("dab", "<u4"), ("voters", "<i4"), ("cost", "<i8"), ("w", "<i8", 2), ("neither", "<i4"), ("flags", "<i4"),
+                            ("team_of_a", "<i4"), ("reserved", "<i4", 3)])                                                                        # EagleKitModel (64 bytes)
+assert C.sizeof(EagleKitParams) == 32 and (KIT_CROP_DTYPE.itemsize, KIT_ID_DTYPE.itemsize, KIT_MODEL_DTYPE.itemsize) == (144, 160, 64)             # kits.hip asserts them too
+
+
 class EagleShotParams(C.Structure):
     """include/eagle.h EagleShotParams: cut, low and grass_thr in 1 / 65536, the window W in frames, the least length of a usable shot in frames."""
     _fields_ = [("cut", C.c_int32), ("low", C.c_int32), ("grass_thr", C.c_int32), ("window", C.c_int32), ("min_len", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -470,6 +487,11 @@ def load():
     L.eagle_ball_track_free.restype = None
     L.eagle_op_ball_track.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, i32, btp, i32, vp, vp, i32, vp, vp]
     L.eagle_postprocess_ball.argtypes = [vp, vp, i32, C.POINTER(EaglePostParams), vp, C.POINTER(vp)]
+    ktp = C.POINTER(EagleKitParams)
+    L.eagle_kit_params_default.argtypes = [ktp]
+    L.eagle_team_cluster.argtypes = [vp, vp, i32, vp, vp, i32, i32, ktp, vp, vp, vp]
+    L.eagle_op_team_cluster.argtypes = [i32, vp, i32, i32, i32, vp, vp, i32, i32, ktp, vp, vp, vp, vp]
+    L.eagle_op_team_cluster_ids.argtypes = [i32, vp, vp, i32, ktp, vp, vp, vp]
     shp = C.POINTER(EagleShotParams)
     L.eagle_shots_device_frames.argtypes = [vp, vp, i32, shp, vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_shots_frames.argtypes = [vp, vp, i32, i64, i64, i64, shp, vp, vp, i32, C.POINTER(C.c_int)]
@@ -536,7 +558,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_roles_values", "eagle_post_device_roles", "eagle_op_roles", "eagle_post_space", "eagle_post_space_values", "eagle_post_device_space",
            "eagle_space_device_grids", "eagle_space_grids", "eagle_op_space", "eagle_post_offside", "eagle_post_offside_values", "eagle_post_offside_events",
            "eagle_post_device_offside", "eagle_op_offside", "eagle_ball_track", "eagle_ball_track_values", "eagle_ball_track_tracklets", "eagle_ball_track_free",
-           "eagle_op_ball_track", "eagle_postprocess_ball", "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
+           "eagle_op_ball_track", "eagle_postprocess_ball", "eagle_kit_params_default", "eagle_team_cluster", "eagle_op_team_cluster", "eagle_op_team_cluster_ids",
+           "eagle_shots_device_frames", "eagle_shots_frames", "eagle_op_shots", "eagle_topview_size", "eagle_topview_device_frames", "eagle_topview_frames",
            "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
            "eagle_op_topview", "eagle_ground_device_frames", "eagle_ground_frames", "eagle_op_ground", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
@@ -1392,6 +1415,20 @@ class Handle:
         out = np.zeros((len(crops), 12), np.int32)
         self._check(self.L.eagle_team_colors(self._h, dptr, n_frames, crops.ctypes.data_as(C.c_void_p), len(crops), out.ctypes.data_as(C.c_void_p)), "team_colors")
         return out
+
+    def team_cluster(self, dptr, n_frames, crops, slots, n_ids, params=None):
+        """The team clustering on a clip resident in HBM (include/eagle.h, eagle_team_cluster): crops int32 [k, 5] (frame, x1, y1, x2, y2), slots int32 [k]
+        (0 .. n_ids - 1) -> (KIT_CROP_DTYPE [k], KIT_ID_DTYPE [n_ids], KIT_MODEL_DTYPE [1]); params kit_params(...)."""
+        crops = np.ascontiguousarray(crops, np.int32).reshape(-1, 5)
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        if len(slots) != len(crops):
+            raise ValueError(f"team_cluster: {len(slots)} slots for {len(crops)} crops")
+        params = params or kit_params()
+        recs, ids, model = np.zeros(len(crops), KIT_CROP_DTYPE), np.zeros(int(n_ids), KIT_ID_DTYPE), np.zeros(1, KIT_MODEL_DTYPE)
+        keep = np.zeros(64, np.float64)
+        self._check(self.L.eagle_team_cluster(self._h, dptr, int(n_frames), _ptr(crops, keep), _ptr(slots, keep), len(crops), int(n_ids), C.byref(params),
+                                              _ptr(recs, keep), _ptr(ids, keep), _ptr(model, keep)), "team_cluster")
+        return recs, ids, model
 
     # --- track identities (include/eagle.h, eagle_track_*) -------------------------------------------------
     def track_open(self, **params):
@@ -2564,6 +2601,54 @@ def op_ball_track(counts, positions, cq, params, cuts=None, conf=None, det=None,
         raise EagleError(f"eagle_op_ball_track failed ({rc}): {L.eagle_last_error(None).decode()}")
     out = frames, tracklets[:int(clip[0]["tracklets"])].copy(), clip
     return out + (ms,) if times else out
+
+
+def kit_params(min_pixels=None, min_crops=None, outlier=None):
+    """EagleKitParams; None: the library's default (32 counted pixels, 3 used crops, 512 / 1024 of the distance between the medoids: conventional
+    choices, not fitted to data).  outlier 0: nobody is neither."""
+    p = EagleKitParams()
+    load().eagle_kit_params_default(C.byref(p))
+    for k, v in (("min_pixels", min_pixels), ("min_crops", min_crops), ("outlier", outlier)):
+        if v is not None:
+            setattr(p, k, int(v))
+    return p
+
+
+def op_team_cluster(frames, crops, slots, n_ids, params=None, times=False, device=0):
+    """The team clustering on host frames uint8 [n, h, w, 3] (include/eagle.h eagle_op_team_cluster) -> (KIT_CROP_DTYPE [k], KIT_ID_DTYPE [n_ids],
+    KIT_MODEL_DTYPE [1]), with times=True also the two device times in milliseconds (histograms, clustering)."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, h, w = frames.shape[:3]
+    crops = np.ascontiguousarray(crops, np.int32).reshape(-1, 5)
+    slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+    if len(slots) != len(crops):
+        raise ValueError(f"op_team_cluster: {len(slots)} slots for {len(crops)} crops")
+    params = params or kit_params()
+    recs, ids, model, ms = np.zeros(len(crops), KIT_CROP_DTYPE), np.zeros(int(n_ids), KIT_ID_DTYPE), np.zeros(1, KIT_MODEL_DTYPE), np.zeros(2, np.float32)
+    keep = np.zeros(64, np.float64)
+    rc = L.eagle_op_team_cluster(device, _ptr(frames, keep), n, h, w, _ptr(crops, keep), _ptr(slots, keep), len(crops), int(n_ids), C.byref(params), _ptr(recs, keep),
+                                 _ptr(ids, keep), _ptr(model, keep), _ptr(ms, keep) if times else None)
+    if rc:
+        raise EagleError(f"eagle_op_team_cluster failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return (recs, ids, model, ms) if times else (recs, ids, model)
+
+
+def op_team_cluster_ids(sums, used, params=None, times=False, device=0):
+    """Steps 5 to 11 of the team clustering from given sums int64 [n_ids, 34] and used int32 [n_ids] (include/eagle.h eagle_op_team_cluster_ids)
+    -> (KIT_ID_DTYPE [n_ids], KIT_MODEL_DTYPE [1]), with times=True also the device times."""
+    L = load()
+    sums = np.ascontiguousarray(sums, np.int64).reshape(-1, KIT_BINS)
+    used = np.ascontiguousarray(used, np.int32).reshape(-1)
+    if len(sums) != len(used):
+        raise ValueError(f"op_team_cluster_ids: {len(sums)} rows of sums for {len(used)} ids")
+    params = params or kit_params()
+    ids, model, ms = np.zeros(len(used), KIT_ID_DTYPE), np.zeros(1, KIT_MODEL_DTYPE), np.zeros(2, np.float32)
+    keep = np.zeros(64, np.float64)
+    rc = L.eagle_op_team_cluster_ids(device, _ptr(sums, keep), _ptr(used, keep), len(used), C.byref(params), _ptr(ids, keep), _ptr(model, keep), _ptr(ms, keep) if times else None)
+    if rc:
+        raise EagleError(f"eagle_op_team_cluster_ids failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return (ids, model, ms) if times else (ids, model)
 
 
 def shot_params(cut=None, low=None, grass_thr=None, window=None, min_len=None, fps=25):

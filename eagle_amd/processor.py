@@ -14,6 +14,7 @@ from .coordinate_model import CoordinateModel
 class Processor:
     def __init__(self, model: CoordinateModel = None, **model_kwargs):
         self.model = model or CoordinateModel(**model_kwargs)
+        self.team_report = None                                   # the report of the last get_team_mapping(method="cluster")
 
     def process(self, frame, pixel_format="bgr"):
         """frame: uint8 HWC BGR, or a decoder's 4:2:0 frame [3h/2, w] with pixel_format "nv12" / "i420".
@@ -24,13 +25,22 @@ class Processor:
     def process_clip(self, frames, pixel_format="bgr"):
         return [records.to_process_dict(r) for r in self.model.process_records(frames, pixel_format)]
 
-    def get_team_mapping(self, frames, coords, pixel_format="bgr"):
+    def get_team_mapping(self, frames, coords, pixel_format="bgr", method="colours", **params):
         """The reference post-processor's ``get_team_mapping`` (eagle/processor.py:405-464; its "pretty slow" step) for a clip and the
         ``get_coordinates`` output of that clip: colour segmentation and counting of every player crop on the GPU (eagle_amd/teams.py).
-        -> {player_id: 0 | 1}.  Player ids are track ids when the model was built with ``tracker=True``."""
-        from . import teams
+        -> {player_id: 0 | 1}.  Player ids are track ids when the model was built with ``tracker=True``.
+        method="cluster": the project's own rule instead, the two clusters of the ids' kit colours over the clip (eagle_amd/kits.py; params
+        min_pixels, min_crops, outlier); an id in neither team has no entry, and the report is kept as ``self.team_report``."""
+        if method not in ("colours", "cluster"):
+            raise ValueError(f"get_team_mapping: method {method!r} is neither 'colours' nor 'cluster'")
+        if method == "colours" and params:
+            raise ValueError(f"get_team_mapping: {sorted(params)} belong to method='cluster'")
+        from . import kits, teams
         d = self.model._upload(frames, pixel_format)
         try:
+            if method == "cluster":
+                mapping, self.team_report = kits.cluster_team_mapping(self.model.handle, d, coords, n_frames=len(frames), **params)
+                return mapping
             return teams.get_team_mapping(self.model.handle, d, coords, n_frames=len(frames))
         finally:
             self.model.handle.free(d)
@@ -41,23 +51,33 @@ class Processor:
         from . import balltrack as bt
         return bt.track(self.model.handle, self.model._records_of(records), fps, self.model.handle.cfg.frame_w, cuts, speed, gap, reward, brk)
 
-    def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False, ball_track=False, cuts=None):
+    def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False, ball_track=False, cuts=None, team_method="colours",
+                     team_params=None):
         """The reference post-processor's ``process_data`` (eagle/processor.py:73-87) for a clip and its ``get_coordinates`` output (or raw
         records): the team mapping (get_team_mapping above), then the interpolated, goalkeeper-folded, optionally smoothed table, built on the GPU
         (eagle_amd/postprocess.py).  -> (table, team_mapping); postprocess.raw_data_rows / format_data turn the table into main.py's two JSON files.
         merge_ids: stitch fragmented tracker ids (postprocess.process_data); the returned mapping then includes the teams the merged ids inherit.
         ball_track: True, or a dict of ball_track's settings (speed, gap, reward, brk): the table's ball is the tracked one (ball_track above, with
-        ``cuts``) instead of the reference's choice; the track is kept as ``table.ball_track``."""
+        ``cuts``) instead of the reference's choice; the track is kept as ``table.ball_track``.
+        team_method: "colours" (the reference's rule) or "cluster" (get_team_mapping above, with the dict ``team_params``); the cluster report is kept
+        as ``table.team_report`` (None otherwise)."""
         from . import postprocess
         coords = coords_or_records
         if not isinstance(coords, dict):
             coords = {i: records.to_reference_dict(r, i, fps) for i, r in enumerate(np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1))}
         recs = self.model._records_of(coords_or_records)
-        team_mapping = self.get_team_mapping(frames, coords, pixel_format) if len(recs) else {}
+        if team_method not in ("colours", "cluster") or (team_method == "colours" and team_params):
+            raise ValueError(f"process_data: team_method {team_method!r} with team_params {team_params!r}")
+        self.team_report = None
+        if team_method == "cluster":
+            team_mapping = self.get_team_mapping(frames, coords, pixel_format, method="cluster", **(team_params or {})) if len(recs) else {}
+        else:
+            team_mapping = self.get_team_mapping(frames, coords, pixel_format) if len(recs) else {}
         track = self.ball_track(recs, fps, cuts, **(ball_track if isinstance(ball_track, dict) else {})) if ball_track else None
         table = postprocess.process_data(self.model.handle, recs, fps, self.model.handle.cfg.frame_w, team_mapping, smooth=smooth, merge_ids=merge_ids,
                                          ball_det=None if track is None else track[0]["det"])
         table.ball_track = track
+        table.team_report = self.team_report
         return table, table.team_mapping if merge_ids else team_mapping
 
     def shots(self, frames, fps, pixel_format="bgr", **overrides):

@@ -31,12 +31,11 @@ def crop_colors(handle, dptr, n_frames, crops):
     return out
 
 
-def get_team_mapping(handle, dptr, coords, n_frames=None):
-    """coords: ``{i: {"Coordinates": {"Player": {id: {"BBox": [x1,y1,x2,y2], ...}}}}}`` as ``get_coordinates`` returns it, frame i of the
-    clip at ``dptr`` -> {player_id: 0 | 1}.  ``n_frames``: frames resident at ``dptr``; like the reference's ``zip(frames, coords)``
-    (proc.py:408) the walk stops at the shorter of the two, and the kernel never indexes beyond the uploaded clip."""
+def eligible_crops(coords, n_frames=None):
+    """The walk of proc.py:408-436 over ``coords``: yields (frame, player id, [x1, y1, x2, y2], overlap) for every Player box with integer
+    coordinates that is not empty and that no other player box of the frame covers by more than 35 %.  ``n_frames``: frames resident; the walk
+    stops at the shorter of the two."""
     n_frames = len(coords) if n_frames is None else min(int(n_frames), len(coords))
-    items, crops = [], []
     for i, key in enumerate(coords):
         if i >= n_frames:
             break
@@ -51,8 +50,18 @@ def get_team_mapping(handle, dptr, coords, n_frames=None):
             prop = _overlap(bbox, boxes)
             if prop > 0.35:
                 continue
-            items.append((int(pid), prop))
-            crops.append((i, *bbox))
+            yield i, int(pid), bbox, prop
+
+
+def get_team_mapping(handle, dptr, coords, n_frames=None):
+    """coords: ``{i: {"Coordinates": {"Player": {id: {"BBox": [x1,y1,x2,y2], ...}}}}}`` as ``get_coordinates`` returns it, frame i of the
+    clip at ``dptr`` -> {player_id: 0 | 1}.  ``n_frames``: frames resident at ``dptr``; like the reference's ``zip(frames, coords)``
+    (proc.py:408) the walk stops at the shorter of the two, and the kernel never indexes beyond the uploaded clip."""
+    n_frames = len(coords) if n_frames is None else min(int(n_frames), len(coords))
+    items, crops = [], []
+    for i, pid, bbox, prop in eligible_crops(coords, n_frames):
+        items.append((pid, prop))
+        crops.append((i, *bbox))
     if not crops:
         return {}
     colors = crop_colors(handle, dptr, n_frames, crops)

@@ -1416,6 +1416,75 @@ int eagle_track_frames_reid(EagleHandle* h, EagleFrameResult* recs, int n, const
  * result there depends on the rounding of its centred data and is not reproduced (of 400 seeded few-level crops, 117 tie and 16 of those differ). */
 int eagle_team_colors(EagleHandle* h, const void* d_bgr, int n_frames, const EagleCrop* crops, int n_crops, int32_t* counts);
 
+/* ---- team clustering: the two teams as the two clusters of the ids' kit colours over the clip (own specification: tests/kits_ref.py defines every
+ * output bit) ----
+ * eagle_team_colors above feeds the reference's rule: named colour ranges and the two most common names, which cannot separate two kits inside one
+ * named range (navy and sky blue are both "blue").  This stage is the library's own, opt-in answer.  Crop i belongs to the id of slot slots[i]
+ * (0 .. n_ids - 1).  With w = x2 - x1, h = y2 - y1 its shirt window is rows [y1 + h/5, y1 + h/2) and columns [x1 + w/4, x2 - w/4) (integer
+ * divisions).  A pixel with g >= 48 and g - max(r, b) >= 16 is grass and does not count; every other pixel gets cv2's 8-bit HSV; with s >= 64 and
+ * v >= 48 it puts 12 units into the two nearest of 15 circular hue bins of width 12 (t = (h + 174) % 180: 12 - t % 12 units to bin t / 12, t % 12
+ * units to the next), in the lower 15 bins for v < 144, in the upper 15 otherwise; any other pixel puts 12 units into bin 30 + v / 64.  A crop of n
+ * counted pixels gives q[b] = units[b] * 4096 / (12 n); per id sum[b] adds the q[b] of its used crops and p[b] = sum[b] * 65536 / T with T the sum of
+ * sum[b].  D(i, j) = sum_b |p_i[b] - p_j[b]|.  The voters are the ids with at least min_crops used crops, of weight w_i = used.  For every pair of
+ * voters a < b, cost(a, b) = sum over the voters of w_i min(D(i, a), D(i, b)); the least cost wins, ties go to the earlier pair.  Every id with a used
+ * crop goes to the nearer medoid (equal distances: a); it is "neither" (team -1) when outlier > 0 and d_near * 1024 > outlier * D(a, b).  Team 0 is
+ * the cluster with the larger sum of w over its voters that are not neither (a tie: the cluster of a).  With fewer than two voters every id with
+ * crops is team 0.  Integers throughout: the result does not depend on any order of accumulation, and two runs give identical bytes.  The constants
+ * are conventional choices, not fitted to data. */
+#define EAGLE_KIT_BINS 34
+#define EAGLE_KIT_MAX_IDS 1024
+#define EAGLE_KIT_CROP_OUTSIDE 1   /* the crop leaves the frame or names a frame outside the clip: zeros */
+#define EAGLE_KIT_CROP_EMPTY 2     /* the crop or its shirt window is empty: zeros */
+#define EAGLE_KIT_CROP_FEW 4       /* fewer than min_pixels counted pixels: units and n are reported, the crop is not used */
+#define EAGLE_KIT_ID_WEAK 1        /* fewer than min_crops used crops: assigned, but no voter */
+#define EAGLE_KIT_ID_NEITHER 2     /* farther from the nearer medoid than outlier / 1024 of the distance between the medoids: team -1 */
+#define EAGLE_KIT_ID_SINGLE 4      /* fewer than two voters: team 0 */
+#define EAGLE_KIT_MODEL_SINGLE 1
+#define EAGLE_KIT_MODEL_SWAPPED 2  /* team 0 is the cluster of b */
+typedef struct {
+    int32_t min_pixels;            /* 1 .. 2^20: the least counted pixels of a used crop (default 32) */
+    int32_t min_crops;             /* 1 .. 2^16: the least used crops of a voter (default 3) */
+    int32_t outlier;               /* 0 .. 2^20, in 1/1024 of D(a, b); 0: nobody is neither (default 512, half the distance between the medoids) */
+    int32_t reserved[5];           /* 0 */
+} EagleKitParams;                  /* 32 bytes */
+typedef struct {
+    uint32_t units[EAGLE_KIT_BINS];
+    int32_t n, flags;              /* counted pixels; EAGLE_KIT_CROP_* */
+} EagleKitCrop;                    /* 144 bytes */
+typedef struct {
+    int32_t used, skipped;         /* crops of the id that count / that were skipped */
+    int32_t team;                  /* 0, 1, or -1: no used crop, or neither */
+    int32_t flags;                 /* EAGLE_KIT_ID_* */
+    uint32_t d[2];                 /* D to the medoid of team 0 and of team 1 (0 without medoids) */
+    uint32_t p[EAGLE_KIT_BINS];    /* the signature (0 without a used crop) */
+} EagleKitId;                      /* 160 bytes */
+typedef struct {
+    int32_t a, b;                  /* the medoids' slots, a < b; -1 with fewer than two voters */
+    uint32_t dab;                  /* D(a, b) */
+    int32_t voters;
+    int64_t cost;                  /* cost(a, b) */
+    int64_t w[2];                  /* sum of w over the voters of team 0 and of team 1 that are not neither */
+    int32_t neither;               /* ids that are neither */
+    int32_t flags;                 /* EAGLE_KIT_MODEL_* */
+    int32_t team_of_a;             /* 0 or 1 */
+    int32_t reserved[3];
+} EagleKitModel;                   /* 64 bytes */
+int eagle_kit_params_default(EagleKitParams* p);
+/* On a clip of n_frames BGR frames of the handle's size resident at d_bgr (as eagle_team_colors).  Each output may be NULL: crops_out [n_crops],
+ * ids_out [n_ids], model_out [1].  EAGLE_E_INVALID, with a message naming the count and the limit and before anything is read or written: more than
+ * 1024 ids, more than 2^22 crops, a slot outside 0 .. n_ids - 1, a parameter outside its range.  n_ids == 0 writes the model of no voters only. */
+int eagle_team_cluster(EagleHandle* h, const void* d_bgr, int n_frames, const EagleCrop* crops, const int32_t* slots, int n_crops, int n_ids, const EagleKitParams* p,
+                       EagleKitCrop* crops_out, EagleKitId* ids_out, EagleKitModel* model_out);
+/* Operator entries (host buffers in / out, no handle: parity tests and tools).  The same from n host frames [n, h, w, 3]; times_ms NULL or two device
+ * times in milliseconds, from events recorded directly around kit_hist_kernel's launch (0 without crops) and around the four clustering launches;
+ * allocations and copies lie outside both. */
+int eagle_op_team_cluster(int device, const uint8_t* bgr, int n, int h, int w, const EagleCrop* crops, const int32_t* slots, int n_crops, int n_ids, const EagleKitParams* p,
+                          EagleKitCrop* crops_out, EagleKitId* ids_out, EagleKitModel* model_out, float* times_ms);
+/* The clustering alone from given sums [n_ids][34] (each 0 .. 2^34) and used [n_ids] (0 .. 2^22 each and in all; an id with used > 0 needs a sum above 0): ties and
+ * degenerate distances that pixels cannot reach.  "skipped" of the records is 0. */
+int eagle_op_team_cluster_ids(int device, const int64_t* sums, const int32_t* used, int n_ids, const EagleKitParams* p, EagleKitId* ids_out, EagleKitModel* model_out,
+                              float* times_ms);
+
 /* Frame-sharded multi-GPU: rank r owns a contiguous chunk; one RCCL all-gather of records.
  * eagle_comm_id fills a 128-byte ncclUniqueId on rank 0; the caller broadcasts it (any channel). */
 int eagle_comm_id(void* id128);
