@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--team-method cluster`` (with ``--processed`` or ``--annotated``) finds the team mapping as the two clusters of the ids' kit colours over the clip instead of by the reference's named colour ranges, and writes ``teams.json`` (eagle_amd/kits.py; ``--team-min-pixels``, ``--team-min-crops``, ``--team-outlier`` set the rule).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope.  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--smooth-tracks`` (with ``--processed``) replaces the pitch positions of every Player and Goalkeeper by windowed least-squares fits directly after the table is built, trims jumps, hands the fits' velocities to ``kinematics.json``, the physical report, pass options and the control grid, and writes ``smooth.json`` (eagle_amd/smooth.py; ``--smooth-window``, ``--smooth-degree``, ``--smooth-outlier``, ``--smooth-floor`` and ``--smooth-ball`` set the rule, conventional choices that are not fitted to data, ``--smooth-rows`` adds the per-cell records); ``metadata.json`` then says ``"positions": "smoothed"``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--team-method cluster`` (with ``--processed`` or ``--annotated``) finds the team mapping as the two clusters of the ids' kit colours over the clip instead of by the reference's named colour ranges, and writes ``teams.json`` (eagle_amd/kits.py; ``--team-min-pixels``, ``--team-min-crops``, ``--team-outlier`` set the rule).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope (SURVEY §8f rows 3-4).  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -99,6 +99,16 @@ def main(argv=None):
     ap.add_argument("--merge-ids", action="store_true",
                     help="with --processed: stitch the fragments of one person under several tracker ids into one id (off: the reference as written, which never "
                          "merges); metadata.json then lists the joins as \"merges\" and its team_mapping holds the teams the merged ids inherit")
+    ap.add_argument("--smooth-tracks", action="store_true",
+                    help="with --processed: replace the pitch positions of every Player and Goalkeeper by windowed least-squares fits right after the table is built, "
+                         "trim jumps, and hand the fits' velocities to every later stage; writes <out>/smooth.json (the half-width, degree, threshold and floor are "
+                         "conventional choices, not fitted to data)")
+    ap.add_argument("--smooth-window", type=int, default=None, metavar="F", help="with --smooth-tracks: the half-width in frames, 1 .. 64 (default max(2, round(0.4 fps)))")
+    ap.add_argument("--smooth-degree", type=int, default=None, choices=[1, 2], metavar="D", help="with --smooth-tracks: the polynomial degree (default 2)")
+    ap.add_argument("--smooth-outlier", type=float, default=None, metavar="K", help="with --smooth-tracks: reject a sample beyond K medians of its window's residuals; 0: none (default 4)")
+    ap.add_argument("--smooth-floor", type=float, default=None, metavar="M", help="with --smooth-tracks: never reject a sample closer than M metres to its fit (default 0.25)")
+    ap.add_argument("--smooth-ball", type=int, default=None, metavar="F", help="with --smooth-tracks: smooth the ball too, with this half-width in frames (default: the ball stays)")
+    ap.add_argument("--smooth-rows", action="store_true", help="with --smooth-tracks: also write the per-cell records into smooth.json")
     ap.add_argument("--minimap", action="store_true", help="with --processed: also write <out>/minimap.y4m, the processed table as a top-down video of the pitch")
     ap.add_argument("--minimap-voronoi", action="store_true", help="with --minimap: tint the pitch by the team whose player is nearest")
     ap.add_argument("--minimap-scale", type=int, default=8, help="with --minimap: pixels per metre (even, 2 .. 32)")
@@ -422,6 +432,18 @@ def main(argv=None):
         ap.error("--minimap draws the processed table: it needs --processed")
     if (a.kinematics or a.minimap_control or a.control_grid) and not a.processed:
         ap.error("--kinematics, --minimap-control and --control-grid work on the processed table: they need --processed")
+    a.smooth_set = {k: v for k, v in (("window", a.smooth_window), ("degree", a.smooth_degree), ("outlier_k", a.smooth_outlier), ("outlier_floor", a.smooth_floor),
+                                      ("ball_window", a.smooth_ball)) if v is not None}
+    if a.smooth_tracks and not a.processed:
+        ap.error("--smooth-tracks works on the processed table: it needs --processed")
+    if (a.smooth_set or a.smooth_rows) and not a.smooth_tracks:
+        ap.error("--smooth-window, --smooth-degree, --smooth-outlier, --smooth-floor, --smooth-ball and --smooth-rows set the track smoothing: they need --smooth-tracks")
+    if a.smooth_tracks:
+        from . import smooth as sm
+        try:
+            sm.resolve(a.fps, **a.smooth_set)
+        except ValueError as e:
+            ap.error(str(e))
     if a.merge_ids and not a.processed:
         ap.error("--merge-ids works on the processed table: it needs --processed")
     if a.minimap_control and a.minimap_voronoi:
@@ -488,6 +510,8 @@ def main(argv=None):
         from .annotate import write_y4m
         from .processor import Processor
         team_kw = dict(team_method="cluster", team_params=a.team_set) if a.team_method == "cluster" else {}
+        if a.smooth_tracks:                                                # directly after the table is built, before every other stage
+            team_kw.update(smooth_tracks=True, smooth_params=a.smooth_set)
         if a.ball_track:
             from . import balltrack as bt
             cuts = bt.cuts_of_shots(found_shots, first_frame, n) if found_shots is not None else None
@@ -503,6 +527,10 @@ def main(argv=None):
             with open(os.path.join(a.out, "teams.json"), "w") as f:
                 json.dump(kits.to_json(team_report), f)
         merges = table.merges
+        if a.smooth_tracks:
+            from . import smooth as sm
+            with open(os.path.join(a.out, "smooth.json"), "w") as f:
+                json.dump(sm.to_json(table.smooth_report, rows=a.smooth_rows), f)
         with open(os.path.join(a.out, "raw_data.json"), "w") as f:
             json.dump(postprocess.json_rows(postprocess.raw_data_rows(table)), f)
         with open(os.path.join(a.out, "processed_data.json"), "w") as f:
@@ -511,7 +539,7 @@ def main(argv=None):
             write_y4m(os.path.join(a.out, "annotated.y4m"), model.annotate(frames, coordinates, team_mapping, out_format="i420", table=table), a.fps)
         if a.kinematics or a.minimap_control or a.control_grid:
             from . import control as ct
-            kin = ct.kinematics(model.handle, table, a.fps)
+            kin = ct.kinematics(model.handle, table, a.fps, keep=a.smooth_tracks)      # after --smooth-tracks: the fits' velocities
             if a.kinematics:
                 with open(os.path.join(a.out, "kinematics.json"), "w") as f:
                     json.dump({"fps": a.fps, "players": kin["players"]}, f)
@@ -520,7 +548,7 @@ def main(argv=None):
                 np.save(os.path.join(a.out, "control.npy"), grids)
                 with open(os.path.join(a.out, "control_share.json"), "w") as f:
                     json.dump({"cells_per_metre": a.control_grid, "frames": [int(r) for r in table.rows], "team0_share": [float(v) for v in share]}, f)
-        have_vel = bool(a.kinematics or a.minimap_control or a.control_grid)
+        have_vel = bool(a.kinematics or a.minimap_control or a.control_grid or a.smooth_tracks)
         if (a.physical or a.pass_options) and not have_vel:
             model.handle.velocities(table, a.fps)
         if a.physical:
@@ -607,6 +635,8 @@ def main(argv=None):
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
         if a.merge_ids:
             meta["merges"] = merges
+        if a.smooth_tracks:
+            meta["positions"] = "smoothed"                                 # the table's pitch positions are the fits' (smooth.json)
         if a.ball_track:
             meta["ball"] = "ball_track"                                    # the table's ball is the tracked one (ball_track.json)
         if team_report is not None:

@@ -10,11 +10,12 @@ import numpy as np
 from . import lib
 
 
-def kinematics(handle, table, fps, max_gap=None, speed_cap=12.0):
+def kinematics(handle, table, fps, max_gap=None, speed_cap=12.0, keep=False):
     """A lib.PostTable of ``handle`` -> {"velocities": float64 [columns][rows][2], "players": [{"id", "type", "distance", "top_speed"}]}: one entry per
     Player / Goalkeeper pitch column in table order, distance in metres (the trapezoid sum of speed x dt over the steps between rows that are both
-    present and at most max_gap frames apart) and top speed in m/s."""
-    vel = handle.velocities(table, fps, max_gap, speed_cap)
+    present and at most max_gap frames apart) and top speed in m/s.  keep=True: the velocities the table already carries (those of the fits after
+    eagle_amd.smooth.smooth_tracks) are summed instead of being replaced by differences."""
+    vel = handle.velocity_values(table) if keep else handle.velocities(table, fps, max_gap, speed_cap)
     gap = int(fps if max_gap is None else max_gap)
     f = np.asarray(table.rows, np.int64)
     players = []

@@ -256,14 +256,14 @@ __global__ __launch_bounds__(PS_THREADS) void post_velocity_kernel(const double2
     }
 }
 
-static void velocity_check(const EagleKinematicsParams* p)
+void velocity_check(const EagleKinematicsParams* p)
 {
     if (!p) fail(EAGLE_E_INVALID, "velocities: params is NULL");
     if (p->fps <= 0 || p->max_gap <= 0 || !(p->speed_cap > 0) || !std::isfinite(p->speed_cap))
         fail(EAGLE_E_INVALID, "velocities: fps %d, max_gap %d and speed_cap %g must be positive (and finite)", p->fps, p->max_gap, p->speed_cap);
 }
 
-static void velocity_launch(const double2* values, const int32_t* frames, double2* out, int rows, int cols, const EagleKinematicsParams* p, hipStream_t s)
+void velocity_launch(const double2* values, const int32_t* frames, double2* out, int rows, int cols, const EagleKinematicsParams* p, hipStream_t s)
 {
     const dim3 grid((unsigned)((rows + PS_THREADS - 1) / PS_THREADS), (unsigned)std::min(cols, 65535));
     hipLaunchKernelGGL(post_velocity_kernel, grid, dim3(PS_THREADS), 0, s, values, frames, out, rows, cols, (double)p->fps, p->max_gap, p->speed_cap);
@@ -656,6 +656,8 @@ void eagle_post_free(EaglePostTable* t)
     if (t->d_values || t->d_vel || t->d_poss || t->d_occ || t->d_shape || t->d_phys || t->d_roles || t->d_space || t->d_offside) (void)hipSetDevice(t->h->cfg.device);
     if (t->d_values) (void)hipFree(t->d_values);
     if (t->d_vel) (void)hipFree(t->d_vel);
+    if (t->d_raw) (void)hipFree(t->d_raw);
+    if (t->d_smooth) (void)hipFree(t->d_smooth);
     if (t->d_poss) (void)hipFree(t->d_poss);
     if (t->d_occ) (void)hipFree(t->d_occ);
     if (t->d_shape) (void)hipFree(t->d_shape);

@@ -315,6 +315,10 @@ struct EaglePostTable {
     void* d_offside = nullptr;           // offside (eagle_post_offside): EagleOffsideRow [rows][2] | margins i32 [offside_members][rows] | EagleOffsideTotals
     int offside_members = 0;             // [offside_members] | EagleOffsideClip | EagleOffsideEvent [offside_events], each from a 256-byte boundary; nullptr
     int offside_events = 0;              // before the first call, resident until eagle_post_free
+    double* d_raw = nullptr;             // track smoothing (eagle_post_smooth_tracks): the positions from before it, the layout of d_values
+    void* d_smooth = nullptr;            // acc f64 [cols][rows][2] | residual_q i32 | flags u8 | count u8 [cols][rows] | suspect u8 [rows] | EagleSmoothTotals [cols],
+    bool has_smooth = false;             // each from a 256-byte boundary; both nullptr before the call, resident until eagle_post_free
+    std::vector<EagleSmoothTotals> smooth_totals;
 };
 
 namespace eagle {
@@ -347,6 +351,9 @@ AnnotArgs annot_args(const YuvGeom& g, const uint8_t* src, uint8_t* dst, const E
 void frames_to_host(EagleHandle* h, int n, int fh, int fw, int batch, int out_format, const EagleYuvLayout* out_layout, uint8_t* out,
                     const std::function<void(int, int, const YuvGeom&, uint8_t*)>& draw);
 void clip_close(EagleHandle* h);                                                // clip.hip
+// post.hip: post_velocity_kernel over a whole table on stream s (smooth.hip keeps its result for the columns it does not smooth)
+void velocity_check(const EagleKinematicsParams* p);
+void velocity_launch(const double2* values, const int32_t* frames, double2* out, int rows, int cols, const EagleKinematicsParams* p, hipStream_t s);
 // control.hip: what the minimap's control layer needs from it
 struct CtCol { int32_t col; int32_t team0; };              // a site column of the table: a mapped Player pitch column, and whether its team is 0
 struct ControlArgs {

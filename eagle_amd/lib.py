@@ -262,6 +262,19 @@ LOAD_EFFORT_DTYPE = np.dtype([("col", "<i4"), ("kind", "<i4"), ("first_row", "<i
 assert C.sizeof(EagleLoadParams) == 88 and LOAD_TOTALS_DTYPE.itemsize == 128 and LOAD_EFFORT_DTYPE.itemsize == 48  # the sizes physical.hip asserts of the C structs
 
 
+class EagleSmoothParams(C.Structure):
+    """include/eagle.h EagleSmoothParams: frames per second, the half-width in frames, the degree (1, 2), the ball's half-width (0: the ball stays),
+    the velocity rule's gap, the multiple of the median residual (0: no trimming), the floor (m) and the speed cap (m/s)."""
+    _fields_ = [("fps", C.c_int32), ("window", C.c_int32), ("degree", C.c_int32), ("ball_window", C.c_int32), ("max_gap", C.c_int32), ("reserved0", C.c_int32),
+                ("outlier_k", C.c_double), ("outlier_floor", C.c_double), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
+
+
+SMOOTH_FITTED, SMOOTH_OUTLIER, SMOOTH_DEGREE_SHIFT, SMOOTH_RAW, SMOOTH_Q = 1, 2, 2, 16, 1024     # the bits of a cell's flags; residual_q is in 1 / (16 SMOOTH_Q) metres
+SMOOTH_TOTALS_DTYPE = np.dtype([("sum_sq", "<i8"), ("present", "<i4"), ("outliers", "<i4"), ("low_degree", "<i4"), ("max_residual_q", "<i4"), ("window", "<i4"),
+                                ("reserved", "<i4")])                                                             # EagleSmoothTotals (32 bytes)
+assert C.sizeof(EagleSmoothParams) == 56 and SMOOTH_TOTALS_DTYPE.itemsize == 32                                  # the sizes smooth.hip asserts of the C structs
+
+
 class EaglePassOptionParams(C.Structure):
     """include/eagle.h EaglePassOptionParams: cells per metre (1, 2, 4), lane samples K (1 .. 64), reaction time (s), top speed (m/s), sharpness (1/s),
     ball speed (m/s)."""
@@ -511,6 +524,12 @@ def load():
     L.eagle_ground_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, grp, i32, lay, vp, vp]
     L.eagle_op_ground.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, grp, i32, lay, vp, vp]
     lp = C.POINTER(EagleLoadParams)
+    sp = C.POINTER(EagleSmoothParams)
+    L.eagle_post_smooth_tracks.argtypes = [vp, vp, sp]
+    L.eagle_post_smooth_values.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.eagle_post_device_smooth.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.eagle_post_raw_values.argtypes = [vp, vp]
+    L.eagle_op_smooth_tracks.argtypes = [i32, vp, vp, vp, i32, i32, sp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
     L.eagle_post_physical_totals.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
@@ -563,7 +582,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_topview_mosaic_device", "eagle_topview_mosaic_finish", "eagle_topview_residual_device", "eagle_topview_mosaic_frames", "eagle_topview_residual_frames",
            "eagle_op_topview", "eagle_ground_device_frames", "eagle_ground_frames", "eagle_op_ground", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
-           "eagle_op_flow", "eagle_op_ecc_small", "eagle_op_ecc"]
+           "eagle_op_flow", "eagle_op_ecc_small", "eagle_op_ecc", "eagle_post_smooth_tracks", "eagle_post_smooth_values", "eagle_post_device_smooth",
+           "eagle_post_raw_values", "eagle_op_smooth_tracks"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 ECC_DTYPE = np.dtype([("ok", "<i4"), ("iters", "<i4"), ("rho", "<f8"), ("M", "<f4", (6,))], align=True)      # EagleEccResult
@@ -1086,6 +1106,12 @@ class Handle:
         table.kinematics_params = p
         return v
 
+    def velocity_values(self, table):
+        """The velocities the table carries (velocities above, or smooth_tracks' fits) -> float64 [columns][rows][2]; an EagleError without any."""
+        v = np.zeros((len(table.columns), len(table.rows), 2), np.float64)
+        self._check(self.L.eagle_post_velocity_values(table._t, _ptr(v, np.zeros(4, np.float64))), "post_velocity_values")
+        return v
+
     def control_device(self, table, d_out, params, row0=0, n=None, d_share=None):
         """Rows row0 .. row0 + n - 1 -> n control grids [n][gh][gw] at ``d_out`` (device memory) and, with ``d_share``, n int64 byte sums."""
         n = len(table.rows) - row0 if n is None else n
@@ -1158,6 +1184,37 @@ class Handle:
         keep = np.zeros(8, np.float64)
         self._check(self.L.eagle_pass_options(self._h, table._t, int(row0), int(n), C.byref(params), _ptr(g, keep), _ptr(recs, keep), _ptr(opt, keep)), "pass_options")
         return g, recs, opt
+
+    # --- track smoothing (include/eagle.h, eagle_post_smooth_tracks) ------------------------------------------------------------
+    def smooth_tracks(self, table, params):
+        """Replaces the pitch positions of the person columns (and the ball, with params.ball_window > 0) of a PostTable of this handle by windowed
+        least-squares fits, in HBM, sets the table's velocities to the fits' derivatives and keeps the rest with the table; it comes before every
+        other result and once -> {"velocities", "acc": float64 [columns][rows][2]; "flags", "count": uint8 and "residual_q": int32 [columns][rows];
+        "suspect": uint8 [rows]; "totals": SMOOTH_TOTALS_DTYPE [columns]}.  table.values is the smoothed table afterwards, raw_values(table) the old one."""
+        self._check(self.L.eagle_post_smooth_tracks(self._h, table._t, C.byref(params)), "post_smooth_tracks")
+        table._values = None
+        table.kinematics_params = kinematics_params(params.fps, params.max_gap, params.speed_cap)
+        cols, rows = len(table.columns), len(table.rows)
+        out = {"velocities": np.zeros((cols, rows, 2), np.float64), "acc": np.zeros((cols, rows, 2), np.float64), "flags": np.zeros((cols, rows), np.uint8),
+               "count": np.zeros((cols, rows), np.uint8), "residual_q": np.zeros((cols, rows), np.int32), "suspect": np.zeros(rows, np.uint8),
+               "totals": np.zeros(cols, SMOOTH_TOTALS_DTYPE)}
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_post_smooth_values(table._t, _ptr(out["acc"], keep), _ptr(out["flags"], keep), _ptr(out["count"], keep), _ptr(out["residual_q"], keep),
+                                                    _ptr(out["suspect"], keep), _ptr(out["totals"], keep)), "post_smooth_values")
+        self._check(self.L.eagle_post_velocity_values(table._t, _ptr(out["velocities"], keep)), "post_velocity_values")
+        return out
+
+    def raw_values(self, table):
+        """The positions of the table from before smooth_tracks (the table's own without one) -> float64 [columns][rows][2]."""
+        v = np.zeros((len(table.columns), len(table.rows), 2), np.float64)
+        self._check(self.L.eagle_post_raw_values(table._t, _ptr(v, np.zeros(4, np.float64))), "post_raw_values")
+        return v
+
+    def smooth_device(self, table):
+        """(acc float64 [columns][rows][2], flags uint8 [columns][rows], suspect uint8 [rows]) in HBM (None each before smooth_tracks)."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.eagle_post_device_smooth(table._t, C.byref(a), C.byref(b), C.byref(c)), "post_device_smooth")
+        return a.value, b.value, c.value
 
     # --- physical report (include/eagle.h, eagle_post_physical) ------------------------------------------------------------
     def physical(self, table, params):
@@ -2124,6 +2181,34 @@ def op_pass_options(values, velocities, columns, team_mapping, cand, owner, para
     if rc:
         raise EagleError(f"eagle_op_pass_options failed ({rc}): {L.eagle_last_error(None).decode()}")
     return g, recs, opt
+
+
+def smooth_params(fps, window=None, degree=2, outlier_k=4.0, outlier_floor=0.25, ball_window=0, max_gap=None, speed_cap=12.0):
+    """EagleSmoothParams; window None: max(2, round(0.4 fps)) frames; max_gap None: fps frames."""
+    fps = int(fps)
+    return EagleSmoothParams(fps, max(2, int(round(0.4 * fps))) if window is None else int(window), int(degree), int(ball_window), int(fps if max_gap is None else max_gap),
+                             0, float(outlier_k), float(outlier_floor), float(speed_cap), 0)
+
+
+def op_smooth_tracks(values, frames, columns, params, device=0):
+    """The smoothing launches on a constructed table (include/eagle.h eagle_op_smooth_tracks): values float64 [cols][rows][2], frames int32 [rows]
+    strictly ascending, columns POSTCOL_DTYPE (or (kind, id, video) tuples) -> {"values", "vel", "acc": float64 [cols][rows][2]; "flags", "count": uint8 and
+    "residual_q": int32 [cols][rows]; "suspect": uint8 [rows]; "totals": SMOOTH_TOTALS_DTYPE [cols]}."""
+    L = load()
+    values, columns = _table_args("op_smooth_tracks", values, columns)
+    frames = np.ascontiguousarray(frames, np.int32)
+    cols, rows = values.shape[:2]
+    if len(frames) != rows:
+        raise EagleError("op_smooth_tracks: one frame number per row")
+    out = {"values": np.zeros((cols, rows, 2), np.float64), "vel": np.zeros((cols, rows, 2), np.float64), "acc": np.zeros((cols, rows, 2), np.float64),
+           "flags": np.zeros((cols, rows), np.uint8), "count": np.zeros((cols, rows), np.uint8), "residual_q": np.zeros((cols, rows), np.int32),
+           "suspect": np.zeros(rows, np.uint8), "totals": np.zeros(cols, SMOOTH_TOTALS_DTYPE)}
+    keep = np.zeros(8, np.float64)
+    rc = L.eagle_op_smooth_tracks(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, C.byref(params),
+                                  *(_ptr(out[k], keep) for k in ("values", "vel", "acc", "flags", "count", "residual_q", "suspect", "totals")))
+    if rc:
+        raise EagleError(f"eagle_op_smooth_tracks failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
 
 
 def op_physical(velocities, frames, columns, params, cap=None, device=0):

@@ -52,7 +52,7 @@ class Processor:
         return bt.track(self.model.handle, self.model._records_of(records), fps, self.model.handle.cfg.frame_w, cuts, speed, gap, reward, brk)
 
     def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False, ball_track=False, cuts=None, team_method="colours",
-                     team_params=None):
+                     team_params=None, smooth_tracks=False, smooth_params=None):
         """The reference post-processor's ``process_data`` (eagle/processor.py:73-87) for a clip and its ``get_coordinates`` output (or raw
         records): the team mapping (get_team_mapping above), then the interpolated, goalkeeper-folded, optionally smoothed table, built on the GPU
         (eagle_amd/postprocess.py).  -> (table, team_mapping); postprocess.raw_data_rows / format_data turn the table into main.py's two JSON files.
@@ -60,7 +60,9 @@ class Processor:
         ball_track: True, or a dict of ball_track's settings (speed, gap, reward, brk): the table's ball is the tracked one (ball_track above, with
         ``cuts``) instead of the reference's choice; the track is kept as ``table.ball_track``.
         team_method: "colours" (the reference's rule) or "cluster" (get_team_mapping above, with the dict ``team_params``); the cluster report is kept
-        as ``table.team_report`` (None otherwise)."""
+        as ``table.team_report`` (None otherwise).
+        smooth_tracks: replace the pitch positions of the person columns by windowed least-squares fits right after the table is built (smooth_tracks
+        below, with the dict ``smooth_params``); the report is kept as ``table.smooth_report`` (None otherwise)."""
         from . import postprocess
         coords = coords_or_records
         if not isinstance(coords, dict):
@@ -78,6 +80,9 @@ class Processor:
                                          ball_det=None if track is None else track[0]["det"])
         table.ball_track = track
         table.team_report = self.team_report
+        if smooth_params and not smooth_tracks:
+            raise ValueError("process_data: smooth_params without smooth_tracks")
+        table.smooth_report = self.smooth_tracks(table, fps, **(smooth_params or {})) if smooth_tracks else None
         return table, table.team_mapping if merge_ids else team_mapping
 
     def shots(self, frames, fps, pixel_format="bgr", **overrides):
@@ -115,10 +120,17 @@ class Processor:
         events = self.model.handle.events(table)
         return [(k, mm.pass_picture(self.model.handle, table, k, scale, margin, half_width)) for k, e in enumerate(events) if int(e["kind"]) in kinds]
 
-    def kinematics(self, table, fps, max_gap=None, speed_cap=12.0):
-        """Velocities of a processed table (computed on the GPU, kept with the table) plus per id distance covered and top speed: see eagle_amd/control.py."""
+    def smooth_tracks(self, table, fps, **kw):
+        """Smooth the player paths of a processed table that carries no derived result yet (window, degree, outlier_k, outlier_floor, ball_window,
+        max_gap, speed_cap): positions, velocities and accelerations from windowed fits, rejected samples and suspect rows: see eagle_amd/smooth.py."""
+        from . import smooth as sm
+        return sm.smooth_tracks(self.model.handle, table, fps, **kw)
+
+    def kinematics(self, table, fps, max_gap=None, speed_cap=12.0, keep=False):
+        """Velocities of a processed table (computed on the GPU, kept with the table; keep=True: the ones it carries, as after smooth_tracks) plus per
+        id distance covered and top speed: see eagle_amd/control.py."""
         from . import control as ct
-        return ct.kinematics(self.model.handle, table, fps, max_gap, speed_cap)
+        return ct.kinematics(self.model.handle, table, fps, max_gap, speed_cap, keep)
 
     def control(self, table, cells_per_metre=1, t_react=0.7, v_max=5.0, beta=4.0, rows=None):
         """The pitch-control grids of a processed table with velocities (kinematics above) and team 0's area share per row: see eagle_amd/control.py."""

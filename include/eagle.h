@@ -635,6 +635,70 @@ int eagle_op_physical(int device, const double* velocities, const int32_t* frame
                       double* speed, double* accel, uint8_t* zone, EagleLoadTotals* totals, int totals_cap, int* n_persons, EagleLoadEffort* efforts,
                       int efforts_cap, int* n_efforts);
 
+/* ---- track smoothing: windowed least-squares fits of the pitch positions (own specification: tests/smooth_ref.py defines every output bit) ------------
+ * Opt-in; a table never smoothed is byte for byte what eagle_postprocess built.  Integers wherever a sum is formed, float64 with single operations in
+ * the order written everywhere else (no contraction).
+ * COLUMNS.  The Player and Goalkeeper pitch columns (video == 0) are smoothed with half-width W = window; the Ball pitch column with W = ball_window
+ * when that is > 0.  Every other column (video columns, boundaries, the ball by default) keeps its bytes, gets post_velocity_kernel's velocity for
+ * (fps, max_gap, speed_cap) bit for bit, acceleration (NaN, NaN), and 0 in flags, count and residual_q.
+ * PRESENCE.  A cell of a smoothed column is present when x and y are finite and |x|, |y| <= 1024 (the minimap's rule); q = rint(x * 1024) as int64, ties
+ * to even, once.  An absent cell is absent in every output: NaN value, velocity and acceleration, 0 in flags, count and residual_q.
+ * WINDOW of row r: the used rows r' of the column with |f[r'] - f[r]| <= W (frames ascend strictly: within W rows), t = f[r'] - f[r].
+ * SUMS, exact int64: S_k = sum t^k (k = 0 .. 4); per axis B_k = sum t^k q (k = 0 .. 2).  n = S_0.
+ * DEGREE used: n >= 4: degree; n == 3: min(degree, 1); n == 2: 1; n == 1: 0; n == 0 (the refit only): the cell keeps its raw value, velocity and
+ * acceleration (0, 0), flags bit 4, count 0, residual_q 0.
+ * SOLVE, Cramer's rule on the sums converted to double.  Degree 2: C00 = S2 S4 - S3 S3, C01 = S2 S3 - S1 S4, C02 = S1 S3 - S2 S2, C11 = S0 S4 - S2 S2,
+ * C12 = S1 S2 - S0 S3, C22 = S0 S2 - S1 S1, det = (S0 C00 + S1 C01) + S2 C02, a_i = ((C0i B0 + C1i B1) + C2i B2) / det (C10 = C01, C20 = C02, C21 = C12).
+ * Degree 1: det = S0 S2 - S1 S1, a0 = (S2 B0 - S1 B1) / det, a1 = (S0 B1 - S1 B0) / det, a2 = 0.  Degree 0: a0 = B0 / S0, a1 = a2 = 0.
+ * PASS 1: used = present; e[r] = max(|q_x - a0_x|, |q_y - a0_y|).
+ * PASS 2: med[r] = the element of rank (n - 1) // 2 of the window's e ordered by (value, row); the sample is an outlier when outlier_k > 0 and
+ * e[r] > max(outlier_floor * 1024, outlier_k * med[r]).
+ * PASS 3: used = present and not an outlier (a cell's own sample included).  Position a0 / 1024; velocity (a1 * fps) / 1024, a speed above speed_cap scaled
+ * back as post_velocity_kernel does; acceleration (((2 a2) * fps) * fps) / 1024.
+ * PER CELL: flags bit 0 fitted, bit 1 outlier, bits 2-3 the degree used, bit 4 kept raw; count = the refit's n; residual_q = rint(min(16 e', 2^24)) with
+ * e' the raw sample's residual against the final fit.  PER COLUMN: EagleSmoothTotals (all zero for a column not smoothed).  PER ROW: suspect = 1 when at
+ * least 4 smoothed person cells (Player, Goalkeeper) are present and at least half of them are outliers: the frame's homography probably jumped.
+ * Four launches (csrc/smooth.hip): fit, flag, refit, totals.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output and the table alone: NULL pointers, fps, max_gap or speed_cap not positive
+ * (speed_cap not finite), window outside 1 .. 64, degree outside {1, 2}, outlier_k negative or not finite, outlier_floor negative or not finite,
+ * ball_window outside 0 .. 64, a column of unknown kind, frames of the operator entry that do not ascend; through a handle also a table that already
+ * carries a result derived from its positions (velocities, possession, occupancy, shape, physical, roles, space, offside, control parameters) and a
+ * second call.
+ * The constants (0.4 s, degree 2, k = 4, 0.25 m) are conventional choices, not fitted to data; gap-filled cells count as samples; a homography jump is
+ * detected and trimmed per person, not corrected as a common motion; one trimming round. */
+typedef struct EagleSmoothParams {
+    int32_t fps;                   /* > 0 */
+    int32_t window;                /* 1 .. 64: half-width W in frames (a usual choice: max(2, round(0.4 fps))) */
+    int32_t degree;                /* 1 or 2 */
+    int32_t ball_window;           /* 0 .. 64: the ball's half-width; 0 leaves the ball alone */
+    int32_t max_gap;               /* > 0: the velocity rule of the columns not smoothed, as EagleKinematicsParams */
+    int32_t reserved0;
+    double outlier_k;              /* 0: no trimming, else finite and positive: multiple of the window's median residual */
+    double outlier_floor;          /* metres, finite, >= 0: no sample closer to its fit than this is rejected */
+    double speed_cap;              /* > 0, finite: m/s */
+    int64_t reserved;
+} EagleSmoothParams;               /* 56 bytes */
+typedef struct EagleSmoothTotals {
+    int64_t sum_sq;                /* sum of residual_q^2 over the column's cells */
+    int32_t present, outliers;
+    int32_t low_degree;            /* present cells fitted with a degree below `degree` (kept-raw cells included) */
+    int32_t max_residual_q;
+    int32_t window;                /* the half-width the column was smoothed with; 0: not smoothed */
+    int32_t reserved;
+} EagleSmoothTotals;               /* 32 bytes */
+/* Replaces the smoothed columns of the table in HBM, sets the table's velocities (as eagle_post_velocities with fps, max_gap, speed_cap; a later
+ * eagle_post_velocities replaces them) and keeps acceleration, flags, count, residual_q, suspect and totals with the table until eagle_post_free.
+ * It comes before every result derived from the table and once. */
+int eagle_post_smooth_tracks(EagleHandle* h, EaglePostTable* t, const EagleSmoothParams* p);
+/* copies to the host; any pointer may be NULL: acc [cols][rows][2], flags, count, residual_q [cols][rows], suspect [rows], totals [cols] */
+int eagle_post_smooth_values(EaglePostTable* t, double* acc, uint8_t* flags, uint8_t* count, int32_t* residual_q, uint8_t* suspect, EagleSmoothTotals* totals);
+int eagle_post_device_smooth(const EaglePostTable* t, const double** d_acc, const uint8_t** d_flags, const uint8_t** d_suspect);  /* NULL before the call */
+int eagle_post_raw_values(EaglePostTable* t, double* values /* [cols][rows][2] */);   /* the positions from before eagle_post_smooth_tracks (the table's, without one) */
+/* Operator entry (host buffers in / out, no handle): values [cols][rows][2], frames [rows] strictly ascending; every output may be NULL. */
+int eagle_op_smooth_tracks(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const EagleSmoothParams* p,
+                           double* out_values, double* out_vel, double* out_acc, uint8_t* flags, uint8_t* count, int32_t* residual_q, uint8_t* suspect,
+                           EagleSmoothTotals* totals);
+
 /* ---- pass options: where the ball owner can play, per row (own specification: tests/options_ref.py defines every output bit) ----------------------------
  * float32 without contraction, correctly rounded sqrtf and division, the library's own expf (csrc/dmath.h).  Cell centres, the reaction point
  * q = p + v t_react with its clamp to +-2^20, the fp32 rounding of positions and velocities and the non-finite-velocity rule are the control grid's.
