@@ -25,7 +25,7 @@ team and one for the ball); the maps follow a person only with ``--merge-ids``. 
 frame each team's centroid, length, width, hull area, stretch, lines and convex hull, and the clip's means (eagle_amd/shape.py); ``--minimap-hulls [W]``
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
-(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--smooth-tracks`` (with ``--processed``) replaces the pitch positions of every Player and Goalkeeper by windowed least-squares fits directly after the table is built, trims jumps, hands the fits' velocities to ``kinematics.json``, the physical report, pass options and the control grid, and writes ``smooth.json`` (eagle_amd/smooth.py; ``--smooth-window``, ``--smooth-degree``, ``--smooth-outlier``, ``--smooth-floor`` and ``--smooth-ball`` set the rule, conventional choices that are not fitted to data, ``--smooth-rows`` adds the per-cell records); ``metadata.json`` then says ``"positions": "smoothed"``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--team-method cluster`` (with ``--processed`` or ``--annotated``) finds the team mapping as the two clusters of the ids' kit colours over the clip instead of by the reference's named colour ranges, and writes ``teams.json`` (eagle_amd/kits.py; ``--team-min-pixels``, ``--team-min-crops``, ``--team-outlier`` set the rule).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope (SURVEY §8f rows 3-4).  The cadence is main.py:27's by default (homography once per second, key-point model three times per
+(eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--stabilise`` (with ``--processed``) estimates, per kept frame, the motion that every player and the ball share (the small translation, stretch and shear of the pitch plane that a slightly wrong homography gives them at once) from what the players' own paths predict, removes it directly after the table is built and before ``--smooth-tracks``, and writes ``stabilise.json`` (eagle_amd/stabilise.py; ``--stabilise-window``, ``--stabilise-degree``, ``--stabilise-model``, ``--stabilise-min-voters``, ``--stabilise-iterations``, ``--stabilise-trim`` and ``--stabilise-floor`` set the rule, conventional choices that are not fitted to data, ``--stabilise-rows`` adds a record per kept frame); ``metadata.json`` then says ``"stabilised": true``.  ``--smooth-tracks`` (with ``--processed``) replaces the pitch positions of every Player and Goalkeeper by windowed least-squares fits directly after the table is built, trims jumps, hands the fits' velocities to ``kinematics.json``, the physical report, pass options and the control grid, and writes ``smooth.json`` (eagle_amd/smooth.py; ``--smooth-window``, ``--smooth-degree``, ``--smooth-outlier``, ``--smooth-floor`` and ``--smooth-ball`` set the rule, conventional choices that are not fitted to data, ``--smooth-rows`` adds the per-cell records); ``metadata.json`` then says ``"positions": "smoothed"``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--team-method cluster`` (with ``--processed`` or ``--annotated``) finds the team mapping as the two clusters of the ids' kit colours over the clip instead of by the reference's named colour ranges, and writes ``teams.json`` (eagle_amd/kits.py; ``--team-min-pixels``, ``--team-min-crops``, ``--team-outlier`` set the rule).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope (SURVEY §8f rows 3-4).  The cadence is main.py:27's by default (homography once per second, key-point model three times per
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
 import argparse
 import json
@@ -99,6 +99,18 @@ def main(argv=None):
     ap.add_argument("--merge-ids", action="store_true",
                     help="with --processed: stitch the fragments of one person under several tracker ids into one id (off: the reference as written, which never "
                          "merges); metadata.json then lists the joins as \"merges\" and its team_mapping holds the teams the merged ids inherit")
+    ap.add_argument("--stabilise", action="store_true",
+                    help="with --processed: estimate each kept frame's common motion (the small translation, stretch and shear a slightly wrong homography gives "
+                         "every player and the ball at once) from what the players' own paths predict, and remove it, directly after the table is built and before "
+                         "--smooth-tracks; writes <out>/stabilise.json (the constants are conventional choices, not fitted to data)")
+    ap.add_argument("--stabilise-window", type=int, default=None, metavar="F", help="with --stabilise: the half-width in frames, 1 .. 64 (default min(64, max(2, round(fps))))")
+    ap.add_argument("--stabilise-degree", type=int, default=None, choices=[1, 2], metavar="D", help="with --stabilise: the degree of the predicting polynomial (default 2)")
+    ap.add_argument("--stabilise-model", default=None, choices=["translation", "affine"], help="with --stabilise: the common motion's model (default affine)")
+    ap.add_argument("--stabilise-min-voters", type=int, default=None, metavar="N", help="with --stabilise: rows with fewer voting players keep their positions, 3 .. 64 (default 6)")
+    ap.add_argument("--stabilise-iterations", type=int, default=None, metavar="T", help="with --stabilise: rounds, 1 .. 4 (default 2)")
+    ap.add_argument("--stabilise-trim", type=float, default=None, metavar="K", help="with --stabilise: trim a voter beyond K medians of the row's deviations; 0: none (default 3)")
+    ap.add_argument("--stabilise-floor", type=float, default=None, metavar="M", help="with --stabilise: never trim a voter closer than M metres to the median (default 0.1)")
+    ap.add_argument("--stabilise-rows", action="store_true", help="with --stabilise: also write a record per kept frame into stabilise.json")
     ap.add_argument("--smooth-tracks", action="store_true",
                     help="with --processed: replace the pitch positions of every Player and Goalkeeper by windowed least-squares fits right after the table is built, "
                          "trim jumps, and hand the fits' velocities to every later stage; writes <out>/smooth.json (the half-width, degree, threshold and floor are "
@@ -434,6 +446,19 @@ def main(argv=None):
         ap.error("--kinematics, --minimap-control and --control-grid work on the processed table: they need --processed")
     a.smooth_set = {k: v for k, v in (("window", a.smooth_window), ("degree", a.smooth_degree), ("outlier_k", a.smooth_outlier), ("outlier_floor", a.smooth_floor),
                                       ("ball_window", a.smooth_ball)) if v is not None}
+    a.stabilise_set = {k: v for k, v in (("window", a.stabilise_window), ("degree", a.stabilise_degree), ("model", a.stabilise_model), ("min_voters", a.stabilise_min_voters),
+                                         ("iterations", a.stabilise_iterations), ("trim_k", a.stabilise_trim), ("floor", a.stabilise_floor)) if v is not None}
+    if a.stabilise and not a.processed:
+        ap.error("--stabilise works on the processed table: it needs --processed")
+    if (a.stabilise_set or a.stabilise_rows) and not a.stabilise:
+        ap.error("--stabilise-window, --stabilise-degree, --stabilise-model, --stabilise-min-voters, --stabilise-iterations, --stabilise-trim, --stabilise-floor and "
+                 "--stabilise-rows set the stabilisation: they need --stabilise")
+    if a.stabilise:
+        from . import stabilise as stb
+        try:
+            stb.resolve(a.fps, **a.stabilise_set)
+        except ValueError as e:
+            ap.error(str(e))
     if a.smooth_tracks and not a.processed:
         ap.error("--smooth-tracks works on the processed table: it needs --processed")
     if (a.smooth_set or a.smooth_rows) and not a.smooth_tracks:
@@ -510,6 +535,8 @@ def main(argv=None):
         from .annotate import write_y4m
         from .processor import Processor
         team_kw = dict(team_method="cluster", team_params=a.team_set) if a.team_method == "cluster" else {}
+        if a.stabilise:                                                    # directly after the table is built, before --smooth-tracks and every other stage
+            team_kw.update(stabilise=True, stabilise_params=a.stabilise_set)
         if a.smooth_tracks:                                                # directly after the table is built, before every other stage
             team_kw.update(smooth_tracks=True, smooth_params=a.smooth_set)
         if a.ball_track:
@@ -527,6 +554,10 @@ def main(argv=None):
             with open(os.path.join(a.out, "teams.json"), "w") as f:
                 json.dump(kits.to_json(team_report), f)
         merges = table.merges
+        if a.stabilise:
+            from . import stabilise as stb
+            with open(os.path.join(a.out, "stabilise.json"), "w") as f:
+                json.dump(stb.to_json(table.stabilise_report, rows=a.stabilise_rows), f)
         if a.smooth_tracks:
             from . import smooth as sm
             with open(os.path.join(a.out, "smooth.json"), "w") as f:
@@ -635,6 +666,8 @@ def main(argv=None):
         meta = {"fps": a.fps, "frames": n, "seconds": dt, "team_mapping": team_mapping}
         if a.merge_ids:
             meta["merges"] = merges
+        if a.stabilise:
+            meta["stabilised"] = True                                      # each kept frame's common motion was removed (stabilise.json)
         if a.smooth_tracks:
             meta["positions"] = "smoothed"                                 # the table's pitch positions are the fits' (smooth.json)
         if a.ball_track:

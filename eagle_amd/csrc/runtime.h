@@ -319,6 +319,10 @@ struct EaglePostTable {
     void* d_smooth = nullptr;            // acc f64 [cols][rows][2] | residual_q i32 | flags u8 | count u8 [cols][rows] | suspect u8 [rows] | EagleSmoothTotals [cols],
     bool has_smooth = false;             // each from a 256-byte boundary; both nullptr before the call, resident until eagle_post_free
     std::vector<EagleSmoothTotals> smooth_totals;
+    double* d_orig = nullptr;            // stabilisation (eagle_post_stabilise): the positions from before it, the layout of d_values
+    void* d_stab = nullptr;              // EagleStabRow [rows] | votes i32 [cols][rows][2] | EagleStabTotals, each from a 256-byte boundary; both nullptr before
+    bool has_stab = false;               // the call, resident until eagle_post_free
+    EagleStabTotals stab_totals{};
 };
 
 namespace eagle {

@@ -275,6 +275,24 @@ SMOOTH_TOTALS_DTYPE = np.dtype([("sum_sq", "<i8"), ("present", "<i4"), ("outlier
 assert C.sizeof(EagleSmoothParams) == 56 and SMOOTH_TOTALS_DTYPE.itemsize == 32                                  # the sizes smooth.hip asserts of the C structs
 
 
+class EagleStabParams(C.Structure):
+    """include/eagle.h EagleStabParams: frames per second, the half-width in frames, the degree (1, 2), the model (0 translation, 1 affine), the fewest
+    voters of a row, the rounds, the trimming multiple (0: none), its floor (m), the least spread
+    of the inliers (m) and the largest gain of the affine map, and the shift (m) above which a row is flagged as a jump."""
+    _fields_ = [("fps", C.c_int32), ("window", C.c_int32), ("degree", C.c_int32), ("model", C.c_int32), ("min_voters", C.c_int32), ("iterations", C.c_int32),
+                ("reserved0", C.c_int32 * 2), ("trim_k", C.c_double), ("floor", C.c_double), ("min_spread", C.c_double),
+                ("max_gain", C.c_double), ("jump", C.c_double), ("reserved", C.c_int64)]
+
+
+STAB_OVER_CAP, STAB_FEW, STAB_SPREAD, STAB_CORR, STAB_GAIN, STAB_JUMP, STAB_Q = 1, 2, 4, 8, 16, 32, 1024     # the bits of a row's flags; shift_q is in 1 / STAB_Q metres
+STAB_ROW_DTYPE = np.dtype([("voters", "<i4"), ("inliers", "<i4"), ("model", "<i4"), ("flags", "<i4"), ("shift_q", "<i4", (2,)), ("centre_q", "<i4", (2,)),
+                           ("offset", "<f8", (2,)), ("gain", "<f8", (4,)), ("ss_before", "<i8"), ("ss_after", "<i8"), ("moved", "<i4"), ("reserved", "<i4")])   # EagleStabRow
+STAB_TOTALS_DTYPE = np.dtype([("ss_before", "<i8"), ("ss_after", "<i8"), ("inliers", "<i8"), ("moved", "<i8"), ("rows", "<i4"), ("none", "<i4"), ("translation", "<i4"),
+                              ("affine", "<i4"), ("few_inliers", "<i4"), ("low_spread", "<i4"), ("correlated", "<i4"), ("high_gain", "<i4"), ("jumps", "<i4"),
+                              ("over_cap", "<i4"), ("iterations", "<i4"), ("window", "<i4")])                      # EagleStabTotals
+assert C.sizeof(EagleStabParams) == 80 and STAB_ROW_DTYPE.itemsize == 104 and STAB_TOTALS_DTYPE.itemsize == 80      # the sizes stab.hip asserts of the C structs
+
+
 class EaglePassOptionParams(C.Structure):
     """include/eagle.h EaglePassOptionParams: cells per metre (1, 2, 4), lane samples K (1 .. 64), reaction time (s), top speed (m/s), sharpness (1/s),
     ball speed (m/s)."""
@@ -530,6 +548,12 @@ def load():
     L.eagle_post_device_smooth.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.eagle_post_raw_values.argtypes = [vp, vp]
     L.eagle_op_smooth_tracks.argtypes = [i32, vp, vp, vp, i32, i32, sp, vp, vp, vp, vp, vp, vp, vp, vp]
+    stp = C.POINTER(EagleStabParams)
+    L.eagle_post_stabilise.argtypes = [vp, vp, stp]
+    L.eagle_post_stabilise_values.argtypes = [vp, vp, vp, vp]
+    L.eagle_post_original_values.argtypes = [vp, vp]
+    L.eagle_post_device_stabilise.argtypes = [vp, C.POINTER(vp)]
+    L.eagle_op_stabilise.argtypes = [i32, vp, vp, vp, i32, i32, stp, vp, vp, vp, vp]
     L.eagle_post_physical.argtypes = [vp, vp, lp]
     L.eagle_post_physical_values.argtypes = [vp, vp, vp, vp]
     L.eagle_post_physical_totals.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
@@ -583,7 +607,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_topview", "eagle_ground_device_frames", "eagle_ground_frames", "eagle_op_ground", "eagle_op_reid_crop", "eagle_op_reid_conv7", "eagle_op_reid_maxpool3s2", "eagle_op_reid_avgpool2", "eagle_op_reid_dw3",
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
            "eagle_op_flow", "eagle_op_ecc_small", "eagle_op_ecc", "eagle_post_smooth_tracks", "eagle_post_smooth_values", "eagle_post_device_smooth",
-           "eagle_post_raw_values", "eagle_op_smooth_tracks"]
+           "eagle_post_raw_values", "eagle_op_smooth_tracks", "eagle_post_stabilise", "eagle_post_stabilise_values", "eagle_post_original_values",
+           "eagle_post_device_stabilise", "eagle_op_stabilise"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 ECC_DTYPE = np.dtype([("ok", "<i4"), ("iters", "<i4"), ("rho", "<f8"), ("M", "<f4", (6,))], align=True)      # EagleEccResult
@@ -1215,6 +1240,31 @@ class Handle:
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._check(self.L.eagle_post_device_smooth(table._t, C.byref(a), C.byref(b), C.byref(c)), "post_device_smooth")
         return a.value, b.value, c.value
+
+    # --- stabilisation (include/eagle.h, eagle_post_stabilise) ------------------------------------------------------------
+    def stabilise(self, table, params):
+        """Estimates and removes each row's common motion from the Player, Goalkeeper and Ball pitch columns of a PostTable of this handle, in HBM; it
+        comes before smooth_tracks and every other result, and once -> {"rows": STAB_ROW_DTYPE [rows], "totals": STAB_TOTALS_DTYPE [1], "votes": int32
+        [columns][rows][2]}.  table.values is the stabilised table afterwards, original_values(table) the old one."""
+        self._check(self.L.eagle_post_stabilise(self._h, table._t, C.byref(params)), "post_stabilise")
+        table._values = None
+        cols, rows = len(table.columns), len(table.rows)
+        out = {"rows": np.zeros(rows, STAB_ROW_DTYPE), "totals": np.zeros(1, STAB_TOTALS_DTYPE), "votes": np.zeros((cols, rows, 2), np.int32)}
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_post_stabilise_values(table._t, _ptr(out["rows"], keep), _ptr(out["totals"], keep), _ptr(out["votes"], keep)), "post_stabilise_values")
+        return out
+
+    def original_values(self, table):
+        """The positions of the table from before stabilise (the table's own without one) -> float64 [columns][rows][2]."""
+        v = np.zeros((len(table.columns), len(table.rows), 2), np.float64)
+        self._check(self.L.eagle_post_original_values(table._t, _ptr(v, np.zeros(4, np.float64))), "post_original_values")
+        return v
+
+    def stabilise_device(self, table):
+        """The row records (STAB_ROW_DTYPE [rows]) in HBM; None before stabilise."""
+        a = C.c_void_p()
+        self._check(self.L.eagle_post_device_stabilise(table._t, C.byref(a)), "post_device_stabilise")
+        return a.value
 
     # --- physical report (include/eagle.h, eagle_post_physical) ------------------------------------------------------------
     def physical(self, table, params):
@@ -2208,6 +2258,34 @@ def op_smooth_tracks(values, frames, columns, params, device=0):
                                   *(_ptr(out[k], keep) for k in ("values", "vel", "acc", "flags", "count", "residual_q", "suspect", "totals")))
     if rc:
         raise EagleError(f"eagle_op_smooth_tracks failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
+
+
+def stab_params(fps, window=None, degree=2, model=1, min_voters=6, iterations=2, trim_k=3.0, floor=0.1, min_spread=5.0, max_gain=0.05, jump=1.0):
+    """EagleStabParams; window None: min(64, max(2, round(1.0 fps))) frames; model 0 / 1 or "translation" / "affine"."""
+    fps = int(fps)
+    model = {"translation": 0, "affine": 1}.get(model, model)
+    return EagleStabParams(fps, min(64, max(2, int(round(1.0 * fps)))) if window is None else int(window), int(degree), int(model), int(min_voters), int(iterations),
+                           (C.c_int32 * 2)(0, 0), float(trim_k), float(floor), float(min_spread), float(max_gain), float(jump), 0)
+
+
+def op_stabilise(values, frames, columns, params, device=0):
+    """The stabilisation launches on a constructed table (include/eagle.h eagle_op_stabilise): values float64 [cols][rows][2], frames int32 [rows]
+    strictly ascending, columns POSTCOL_DTYPE (or (kind, id, video) tuples) -> {"values": float64 [cols][rows][2]; "rows": STAB_ROW_DTYPE [rows];
+    "votes": int32 [cols][rows][2]; "totals": STAB_TOTALS_DTYPE [1]}."""
+    L = load()
+    values, columns = _table_args("op_stabilise", values, columns)
+    frames = np.ascontiguousarray(frames, np.int32)
+    cols, rows = values.shape[:2]
+    if len(frames) != rows:
+        raise EagleError("op_stabilise: one frame number per row")
+    out = {"values": np.zeros((cols, rows, 2), np.float64), "rows": np.zeros(rows, STAB_ROW_DTYPE), "votes": np.zeros((cols, rows, 2), np.int32),
+           "totals": np.zeros(1, STAB_TOTALS_DTYPE)}
+    keep = np.zeros(8, np.float64)
+    rc = L.eagle_op_stabilise(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, C.byref(params),
+                              *(_ptr(out[k], keep) for k in ("values", "rows", "votes", "totals")))
+    if rc:
+        raise EagleError(f"eagle_op_stabilise failed ({rc}): {L.eagle_last_error(None).decode()}")
     return out
 
 

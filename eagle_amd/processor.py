@@ -52,7 +52,7 @@ class Processor:
         return bt.track(self.model.handle, self.model._records_of(records), fps, self.model.handle.cfg.frame_w, cuts, speed, gap, reward, brk)
 
     def process_data(self, frames, coords_or_records, fps, smooth=False, pixel_format="bgr", merge_ids=False, ball_track=False, cuts=None, team_method="colours",
-                     team_params=None, smooth_tracks=False, smooth_params=None):
+                     team_params=None, smooth_tracks=False, smooth_params=None, stabilise=False, stabilise_params=None):
         """The reference post-processor's ``process_data`` (eagle/processor.py:73-87) for a clip and its ``get_coordinates`` output (or raw
         records): the team mapping (get_team_mapping above), then the interpolated, goalkeeper-folded, optionally smoothed table, built on the GPU
         (eagle_amd/postprocess.py).  -> (table, team_mapping); postprocess.raw_data_rows / format_data turn the table into main.py's two JSON files.
@@ -62,8 +62,13 @@ class Processor:
         team_method: "colours" (the reference's rule) or "cluster" (get_team_mapping above, with the dict ``team_params``); the cluster report is kept
         as ``table.team_report`` (None otherwise).
         smooth_tracks: replace the pitch positions of the person columns by windowed least-squares fits right after the table is built (smooth_tracks
-        below, with the dict ``smooth_params``); the report is kept as ``table.smooth_report`` (None otherwise)."""
+        below, with the dict ``smooth_params``); the report is kept as ``table.smooth_report`` (None otherwise).
+        stabilise: estimate and remove each kept frame's common motion from the Player, Goalkeeper and Ball pitch positions directly after the table is
+        built, before smooth_tracks (stabilise below, with the dict ``stabilise_params``); the report is kept as ``table.stabilise_report`` (None
+        otherwise)."""
         from . import postprocess
+        if stabilise_params and not stabilise:
+            raise ValueError("process_data: stabilise_params without stabilise")
         coords = coords_or_records
         if not isinstance(coords, dict):
             coords = {i: records.to_reference_dict(r, i, fps) for i, r in enumerate(np.ascontiguousarray(coords_or_records, lib.RESULT_DTYPE).reshape(-1))}
@@ -80,6 +85,7 @@ class Processor:
                                          ball_det=None if track is None else track[0]["det"])
         table.ball_track = track
         table.team_report = self.team_report
+        table.stabilise_report = self.stabilise(table, fps, **(stabilise_params or {})) if stabilise else None
         if smooth_params and not smooth_tracks:
             raise ValueError("process_data: smooth_params without smooth_tracks")
         table.smooth_report = self.smooth_tracks(table, fps, **(smooth_params or {})) if smooth_tracks else None
@@ -119,6 +125,12 @@ class Processor:
         from . import minimap as mm
         events = self.model.handle.events(table)
         return [(k, mm.pass_picture(self.model.handle, table, k, scale, margin, half_width)) for k, e in enumerate(events) if int(e["kind"]) in kinds]
+
+    def stabilise(self, table, fps, **kw):
+        """Estimate and remove each kept frame's common motion (the error of its homography) from a processed table that carries no derived result yet
+        (window, degree, model, min_voters, iterations, trim_k, floor, min_spread, max_gain, jump): see eagle_amd/stabilise.py."""
+        from . import stabilise as st
+        return st.stabilise(self.model.handle, table, fps, **kw)
 
     def smooth_tracks(self, table, fps, **kw):
         """Smooth the player paths of a processed table that carries no derived result yet (window, degree, outlier_k, outlier_floor, ball_window,

@@ -5,8 +5,9 @@ The fits run on the GPU where the post-processor left the table in HBM (include/
 defines every bit).  This module holds the defaults, the call and the host arithmetic of smooth.json: a column's RMS and largest residual in metres are
 its integer totals over 16 * 1024.  It is opt-in and comes first: every later stage (kinematics, physical report, pass options, control, possession ...)
 then reads the smoothed table and the fits' velocities.  The half-width (0.4 s), the degree (2), the threshold (4 medians) and its floor (0.25 m) are
-conventional choices, not fitted to data; gap-filled cells count as samples; a homography jump is detected (suspect rows) and trimmed per person, not
-corrected; a quadratic over 0.8 s blunts a cut that is faster than that; the ball stays as it is by default, because a kick is not smooth."""
+conventional choices, not fitted to data; gap-filled cells count as samples; a homography jump is detected (suspect rows) and trimmed per person
+(correcting it as a common motion is eagle_amd.stabilise's part, which runs before this stage); a quadratic over 0.8 s blunts a cut that is faster
+than that; the ball stays as it is by default, because a kick is not smooth."""
 import math
 
 import numpy as np

@@ -665,7 +665,8 @@ int eagle_op_physical(int device, const double* velocities, const int32_t* frame
  * carries a result derived from its positions (velocities, possession, occupancy, shape, physical, roles, space, offside, control parameters) and a
  * second call.
  * The constants (0.4 s, degree 2, k = 4, 0.25 m) are conventional choices, not fitted to data; gap-filled cells count as samples; a homography jump is
- * detected and trimmed per person, not corrected as a common motion; one trimming round. */
+ * detected and trimmed per person; correcting it as a common motion is eagle_post_stabilise's part (below), which runs before this stage; one trimming
+ * round. */
 typedef struct EagleSmoothParams {
     int32_t fps;                   /* > 0 */
     int32_t window;                /* 1 .. 64: half-width W in frames (a usual choice: max(2, round(0.4 fps))) */
@@ -698,6 +699,100 @@ int eagle_post_raw_values(EaglePostTable* t, double* values /* [cols][rows][2] *
 int eagle_op_smooth_tracks(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const EagleSmoothParams* p,
                            double* out_values, double* out_vel, double* out_acc, uint8_t* flags, uint8_t* count, int32_t* residual_q, uint8_t* suspect,
                            EagleSmoothTotals* totals);
+
+/* ---- stabilisation: each frame's common motion is estimated and removed (own specification: tests/stab_ref.py defines every output bit) ----------------
+ * Opt-in; directly after eagle_postprocess, before eagle_post_smooth_tracks and every derived result.  A homography that is a little off moves every
+ * player and the ball of that frame together by a small translation, stretch and shear of the pitch plane; the persons' own paths over a window of
+ * frames predict where each of them should be, and the common part of what they miss is an affine map that is estimated robustly and subtracted.
+ * Integers wherever a sum is formed, float64 with single operations in the order written everywhere else (no contraction).
+ * COLUMNS.  Voters: the Player and Goalkeeper pitch columns (video == 0).  Moved: the voters and the Ball pitch column.  Every other column (video
+ * columns, boundaries) keeps its bytes.
+ * PRESENCE of a cell of a moved column and q = rint(x * 1024): eagle_post_smooth_tracks' rule.  C, the corrected integers, start as q.
+ * ROUNDS.  `iterations` rounds; each is computed from C of the round before for the neighbours and from q for the row itself; a row's map is estimated
+ * afresh each round, never composed.
+ * PREDICT, per present voter cell (c, r): the window is the present rows r' != r of the column with |f[r'] - f[r]| <= window; the cell can vote when
+ * the window has a row before r, a row after r and n >= 2 rows.  eagle_post_smooth_tracks' SUMS over C[r'] with t = f[r'] - f[r], its DEGREE rule
+ * (n >= 4: degree; else 1) and its SOLVE give a0 per axis.  The cell votes when |a0| <= 2^40 on both axes and, with p = llrint(a0) (ties to even),
+ * d = q - p has |d| <= 2^24 on both axes (a vote fits its int32 and every sum below its int64).
+ * ESTIMATE, per row.  The voters in column order, at most the first 64 (more: flag bit 0).  Fewer than min_voters: no estimate (model 0), the row keeps
+ * its bytes.  b = per-axis lower median of d (the element of rank (n - 1) / 2); dev_i = max(|d_x - b_x|, |d_y - b_y|); m = lower median of dev; a voter
+ * is an inlier when trim_k == 0 or (double)dev_i <= max(floor * 1024, trim_k * (double)m).  Over the n_in inliers, floor division throughout:
+ * translation s = floor((2 sum d + n_in) / (2 n_in)) per axis; centre c = floor(sum q / n_in) per axis; u = q_x - c_x, v = q_y - c_y; exact int64 sums
+ * n, Su, Sv, Suu, Suv, Svv and per axis D0 = sum d, Du = sum u d, Dv = sum v d; Cuu = n Suu - Su Su, Cvv = n Svv - Sv Sv, Cuv = n Suv - Su Sv.
+ * With model 1 the affine map is used when n_in >= 6 (else flag bit 1), (double)Cuu and (double)Cvv >= (double)(n n) * (smin * smin) with
+ * smin = min_spread * 1024 (else bit 2), and (double)Cuv * (double)Cuv <= 0.75 * ((double)Cuu * (double)Cvv) (else bit 3), tested in this order.
+ * Its solve on the sums converted to double: C00 = Suu Svv - Suv Suv, C01 = Suv Sv - Su Svv, C02 = Su Suv - Suu Sv, C11 = n Svv - Sv Sv,
+ * C12 = Su Sv - n Suv, C22 = n Suu - Su Su, det = (n C00 + Su C01) + Sv C02, coefficient j = ((C0j D0 + C1j Du) + C2j Dv) / det, giving
+ * (b0, g_u, g_v) per axis.  A gain above max_gain in magnitude (or |b0| > 2^40) falls back to the translation too (bit 4).
+ * T(q) per axis = llrint((b0 + g_u u) + g_v v); for the translation T(q) = s and offset = (double)s.  shift_q = T(c); bit 5 (jump) when |shift_q|
+ * exceeds jump * 1024 on either axis: reported only.
+ * APPLY.  Every present cell of a moved column in a row with an estimate: C = q - T(q); in a row without: C = q.  After the last round the table's
+ * value of such a cell is (double)C / 1024.0; rows without an estimate, absent cells and all other columns keep their input bytes.
+ * Launches (csrc/stab.hip): quantise; per round predict, estimate, apply; totals.
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output and the table alone: NULL pointers, fps <= 0, window outside 1 .. 64,
+ * degree outside {1, 2}, model outside {0, 1}, min_voters outside 3 .. 64, iterations outside 1 .. 4, trim_k neither 0
+ * nor in 1 .. 1000, floor outside 0 .. 1024, min_spread outside (0, 1024], max_gain outside (0, 1], jump not positive, anything not finite, a column of
+ * unknown kind, frames of the operator entry that do not ascend; through a handle also another handle's table, a second call, and a table that already
+ * carries a result derived from its positions, eagle_post_smooth_tracks' included: stabilising comes first.
+ * LIMITS.  What differs from the window's trend is removed: an error that lasts (a homography wrong for a second, the drift between two key-point
+ * frames) is a path like any other and stays.  Gap-filled cells cannot be told from seen ones: they lie on a line, vote for "no motion" and bias a
+ * row in which many cells are filled.  A real common jerk (the whole team stopping in one frame) is taken for camera error.  The affine map is a
+ * first-order stand-in for a projective error, valid where the players stand: boundaries are not moved.  The ball is moved although it may be in the
+ * air.  At most 64 voters per row.  The constants are conventional choices, not fitted to data; nothing was validated on real footage. */
+typedef struct EagleStabParams {
+    int32_t fps;                   /* > 0 */
+    int32_t window;                /* 1 .. 64: half-width W in frames (a usual choice: min(64, max(2, round(1.0 fps)))) */
+    int32_t degree;                /* 1 or 2 */
+    int32_t model;                 /* 0 translation, 1 affine (with the translation as its fall-back) */
+    int32_t min_voters;            /* 3 .. 64 */
+    int32_t iterations;            /* 1 .. 4 */
+    int32_t reserved0[2];
+    double trim_k;                 /* 0: no trimming, else 1 .. 1000: multiple of the median deviation */
+    double floor;                  /* metres, 0 .. 1024: no voter closer to the median than this is trimmed */
+    double min_spread;             /* metres, (0, 1024]: the least standard deviation of the inliers along x and y for the affine map */
+    double max_gain;               /* (0, 1]: the largest |gain| of the affine map */
+    double jump;                   /* metres, > 0: |shift| above it sets the jump flag */
+    int64_t reserved;
+} EagleStabParams;                 /* 80 bytes */
+#define EAGLE_STAB_OVER_CAP 1      /* EagleStabRow.flags: more than 64 voters, the first 64 were used */
+#define EAGLE_STAB_FEW 2           /*   fall-back to the translation: fewer than 6 inliers */
+#define EAGLE_STAB_SPREAD 4        /*   ... the inliers' spread is below min_spread */
+#define EAGLE_STAB_CORR 8          /*   ... the inliers lie too close to a line */
+#define EAGLE_STAB_GAIN 16         /*   ... a gain above max_gain */
+#define EAGLE_STAB_JUMP 32         /*   |shift_q| above jump */
+typedef struct EagleStabRow {
+    int32_t voters, inliers;
+    int32_t model;                 /* 0 none (the row kept its bytes), 1 translation, 2 affine */
+    int32_t flags;
+    int32_t shift_q[2];            /* T(centre), 1/1024 m */
+    int32_t centre_q[2];
+    double offset[2];              /* b0 per axis (the translation as a double for model 1) */
+    double gain[4];                /* x by u, x by v, y by u, y by v */
+    int64_t ss_before;             /* sum over the inliers of |d|^2 */
+    int64_t ss_after;              /* sum over the inliers of |d - T(q)|^2 */
+    int32_t moved;                 /* cells of the row that were moved */
+    int32_t reserved;
+} EagleStabRow;                    /* 104 bytes */
+typedef struct EagleStabTotals {
+    int64_t ss_before, ss_after;   /* summed over the rows (modulo 2^64) */
+    int64_t inliers, moved;
+    int32_t rows;
+    int32_t none, translation, affine;                          /* rows per model */
+    int32_t few_inliers, low_spread, correlated, high_gain;     /* fall-backs by cause */
+    int32_t jumps, over_cap;
+    int32_t iterations, window;
+} EagleStabTotals;                 /* 80 bytes */
+/* Replaces the moved cells of the table in HBM and keeps the row records, the last round's votes, the totals and the positions from before with the
+ * table until eagle_post_free.  Called once and before everything else; eagle_post_smooth_tracks accepts a stabilised table, and
+ * eagle_post_raw_values then gives the stabilised positions. */
+int eagle_post_stabilise(EagleHandle* h, EaglePostTable* t, const EagleStabParams* p);
+/* copies to the host; any pointer may be NULL: rows [rows], totals, votes [cols][rows][2] ((0, 0) where a cell did not vote); EAGLE_E_INVALID before the stage ran */
+int eagle_post_stabilise_values(EaglePostTable* t, EagleStabRow* rows, EagleStabTotals* totals, int32_t* votes);
+int eagle_post_original_values(EaglePostTable* t, double* values /* [cols][rows][2] */);   /* the positions from before eagle_post_stabilise (the table's own, without one) */
+int eagle_post_device_stabilise(const EaglePostTable* t, const EagleStabRow** d_rows);     /* the row records in HBM; NULL before the call */
+/* Operator entry (host buffers in / out, no handle): values [cols][rows][2], frames [rows] strictly ascending; every output may be NULL. */
+int eagle_op_stabilise(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const EagleStabParams* p,
+                       double* out_values, EagleStabRow* rows_out, int32_t* votes, EagleStabTotals* totals);
 
 /* ---- pass options: where the ball owner can play, per row (own specification: tests/options_ref.py defines every output bit) ----------------------------
  * float32 without contraction, correctly rounded sqrtf and division, the library's own expf (csrc/dmath.h).  Cell centres, the reaction point
