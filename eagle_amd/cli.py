@@ -251,6 +251,19 @@ def main(argv=None):
     ap.add_argument("--trim-to-shot", default=None, metavar="{auto,K}",
                     help="keep only the frames of shot K of the clip (auto: the longest usable shot, the earliest on a tie) for everything that follows, the "
                          "trimming the reference asks its users to do by hand; metadata.json records the shot's first frame and count")
+    ap.add_argument("--refine-lines", action="store_true",
+                    help="refine each frame's homography on the frame's painted lines directly after the coordinates are computed (and after --trim-to-shot): "
+                         "raw_coordinates.json and everything behind it carry the refined result; writes <out>/lines.json (eagle_amd/linefit.py; the constants are "
+                         "conventional choices, not fitted to data)")
+    ap.add_argument("--refine-lines-rounds", type=int, default=None, metavar="T", help="with --refine-lines: rounds, 0 .. 16 (default 5)")
+    ap.add_argument("--refine-lines-radius", type=float, default=None, metavar="M", help="with --refine-lines: the first round's inlier radius in metres, at most 8 (default 2.5)")
+    ap.add_argument("--refine-lines-min-radius", type=float, default=None, metavar="M", help="with --refine-lines: the last and the deciding inlier radius in metres (default 0.5)")
+    ap.add_argument("--refine-lines-max-shift", type=float, default=None, metavar="M",
+                    help="with --refine-lines: a refined homography that moves the view by more than M metres is not taken (default 3)")
+    ap.add_argument("--refine-lines-contrast", type=int, default=None, metavar="TAU",
+                    help="with --refine-lines: a line pixel's b + 2 g + r exceeds both neighbours' by TAU, 1 .. 1020 (default 200, i.e. 50 grey levels)")
+    ap.add_argument("--refine-lines-model", default=None, choices=["projective", "affine", "translation"], help="with --refine-lines: the largest correction (default projective)")
+    ap.add_argument("--refine-lines-rows", action="store_true", help="with --refine-lines: also write a record per frame into lines.json")
     ap.add_argument("--topview", action="store_true",
                     help="also write <out>/topview.y4m: every frame warped onto the pitch plane with its homography (the picture that shows whether the homography "
                          "puts the painted lines where the pitch model has them); needs neither --processed nor a tracker")
@@ -459,6 +472,21 @@ def main(argv=None):
             stb.resolve(a.fps, **a.stabilise_set)
         except ValueError as e:
             ap.error(str(e))
+    a.lines_set = {k: v for k, v in (("rounds", a.refine_lines_rounds), ("radius", a.refine_lines_radius), ("radius_min", a.refine_lines_min_radius),
+                                     ("max_shift", a.refine_lines_max_shift), ("tau", a.refine_lines_contrast), ("model", a.refine_lines_model)) if v is not None}
+    if (a.lines_set or a.refine_lines_rows) and not a.refine_lines:
+        ap.error("--refine-lines-rounds, --refine-lines-radius, --refine-lines-min-radius, --refine-lines-max-shift, --refine-lines-contrast, --refine-lines-model and "
+                 "--refine-lines-rows set the line registration: they need --refine-lines")
+    if a.refine_lines:
+        r0, r1 = a.lines_set.get("radius", 2.5), a.lines_set.get("radius_min", 0.5)
+        if not 0 <= a.lines_set.get("rounds", 5) <= 16:
+            ap.error("--refine-lines-rounds takes 0 .. 16")
+        if not (1.0 / 2048 <= r1 <= r0 <= 8.0):
+            ap.error("--refine-lines-radius and --refine-lines-min-radius take metres with 1 / 2048 <= min radius <= radius <= 8")
+        if not 0.0 <= a.lines_set.get("max_shift", 3.0) <= 1024.0:
+            ap.error("--refine-lines-max-shift takes 0 .. 1024 metres")
+        if not 1 <= a.lines_set.get("tau", 200) <= 1020:
+            ap.error("--refine-lines-contrast takes 1 .. 1020")
     if a.smooth_tracks and not a.processed:
         ap.error("--smooth-tracks works on the processed table: it needs --processed")
     if (a.smooth_set or a.smooth_rows) and not a.smooth_tracks:
@@ -522,6 +550,8 @@ def main(argv=None):
         coordinates = model.get_coordinates(frames, a.fps, num_homography=nh, num_keypoint_detection=nk, verbose=False, calibration=a.calibration)
     except lib.EagleRangeError as e:
         raise SystemExit(f"error: {e}\n(re-run with --precision f32, or with --allow-saturation to accept clipped activations)")
+    if a.refine_lines:
+        coordinates, lines = model.refine_lines(frames, coordinates, **a.lines_set)
     dt = time.perf_counter() - t0
     sat = model.handle.timings()
     if sat.sat_events:
@@ -529,6 +559,10 @@ def main(argv=None):
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "raw_coordinates.json"), "w") as f:
         json.dump(coordinates, f, default=float)
+    if a.refine_lines:
+        from . import linefit
+        with open(os.path.join(a.out, "lines.json"), "w") as f:
+            json.dump(linefit.to_json(lines, rows=a.refine_lines_rows), f)
     meta = {"fps": a.fps, "frames": n, "seconds": dt, "note": "team_mapping needs the post-processor (out of scope)"}
     if a.processed:
         from . import postprocess
@@ -700,6 +734,8 @@ def main(argv=None):
             with open(os.path.join(a.out, "topview.json"), "w") as f:
                 json.dump(tv.to_json(res, carry=a.topview_carry, suspect=tv.SUSPECT if a.topview_suspect is None else a.topview_suspect), f)
     meta.update(shot_meta)
+    if a.refine_lines:
+        meta["homography"] = "refined"                                     # the accepted frames were projected with the refined matrix (lines.json)
     with open(os.path.join(a.out, "metadata.json"), "w") as f:
         json.dump(meta, f, default=str)
     print(f"{n} frames in {dt:.3f} s -> {os.path.join(a.out, 'raw_coordinates.json')}")

@@ -85,6 +85,7 @@ class CoordinateModel:
         frames cv2.cvtColor(..., COLOR_YUV2BGR_NV12 / _I420) gives."""
         homography_interval = max(1, int(fps / max(1, num_homography)))
         keypoint_interval = max(1, int(fps / max(1, num_keypoint_detection)))
+        self._last_fps = fps
         if self.tracker:
             # before ANY motion estimate: eagle_track_open forgets the ECC estimator's carried template, so opening the tracker lazily after the
             # clip's camera motion (as until round 3) threw away the template this clip had just stored and mis-aligned the next clip's frame 0
@@ -123,6 +124,7 @@ class CoordinateModel:
 
     # ---- annotated output ----------------------------------------------------------------------------
     _last = None
+    _last_fps = 25
 
     def _remember(self, coords, recs, own):
         """the records behind the last get_coordinates output (and which frames solved their own homography): annotate() draws from them, the dict is
@@ -160,6 +162,26 @@ class CoordinateModel:
         """The mean of the warped frames, its count map and every frame's distance from it (eagle_amd/topview.py mosaic)."""
         from . import topview as tv
         return tv.mosaic(self.handle, frames, self._records_of(coords_or_records, carried_as_plain=True), carry, **kw)
+
+    def refine_lines(self, frames, coords_or_records, fps=None, **params):
+        """Line registration (eagle_amd/linefit.py, include/eagle.h eagle_linefit_frames): the homography each frame's pitch coordinates were projected
+        with, its own or the carried one (the cadence writes the carried matrix into the record when it re-projects), is refined on the frame's painted
+        lines; a frame that was projected with none has no map and stays as it is; the detections of the records hide the players.  The accepted
+        frames are re-projected by the library (Handle.reproject), so foot points, pitch cells, in_bounds and boundaries follow, and their records hold
+        the refined matrix; every other frame keeps its record byte for byte.  ``frames`` uint8 BGR [n, h, w, 3]; ``coords_or_records`` as annotate
+        takes them; ``fps`` for the rebuilt dict's Time (default: the last get_coordinates call's).  The new dict takes the place of the old one for
+        annotate, topview, ground and Processor.process_data -> (coordinates, report: linefit.Result)."""
+        from . import linefit as lf, topview as tv
+        of_dict = isinstance(coords_or_records, dict)
+        recs = np.ascontiguousarray(self._records_of(coords_or_records)).copy()
+        own = self._last[2].copy() if of_dict else np.ones(len(recs), bool)
+        if len(recs) != len(frames):
+            raise ValueError(f"{len(frames)} frames but {len(recs)} records")
+        Hs, valid, _ = tv.homographies(recs)                # the record's H is the matrix the frame was projected with, also where it was carried
+        report = lf.refine(self.handle, np.asarray(frames), Hs, valid, recs, **params)
+        recs = lf.apply(self.handle, recs, report)
+        fps = self._last_fps if fps is None else fps
+        return self._remember({i: records.to_reference_dict(r, i, fps, own_h=bool(own[i])) for i, r in enumerate(recs)}, recs, own), report
 
     def ground(self, frames, coords_or_records, shapes, off, carry=True, out_format="bgr", params=None):
         """The frames with shapes of the pitch plane blended into their grass (eagle_amd/ground.py, include/eagle.h eagle_ground_frames): shapes

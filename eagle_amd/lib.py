@@ -232,6 +232,23 @@ GROUND_SHAPE_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4", 6), ("colour", "<u4
 assert C.sizeof(EagleGroundShape) == 48 == GROUND_SHAPE_DTYPE.itemsize and C.sizeof(EagleGroundParams) == 16                                           # ground.hip asserts them too
 
 
+class EagleLineFitParams(C.Structure):
+    """include/eagle.h EagleLineFitParams: the line-pixel rule (k, tau, box_pad), the rounds and the ladder's top rung, the inlier radius falling from
+    radius by radius_factor per round to radius_min (metres), and what a refined matrix must meet (min_points, max_shift; max_step per round)."""
+    _fields_ = [("k", C.c_int32), ("tau", C.c_int32), ("rounds", C.c_int32), ("model", C.c_int32), ("min_points", C.c_int32), ("min_per_line", C.c_int32),
+                ("box_pad", C.c_double), ("radius", C.c_double), ("radius_min", C.c_double), ("radius_factor", C.c_double), ("max_shift", C.c_double),
+                ("max_step", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+LINEFIT_NO_MAP, LINEFIT_ACCEPTED, LINEFIT_UNCHANGED, LINEFIT_FEW_POINTS, LINEFIT_NO_GAIN, LINEFIT_SHIFT = range(6)          # include/eagle.h EAGLE_LINEFIT_*
+LINEFIT_STATUS = ("no_map", "accepted", "unchanged", "few_points", "no_gain", "shift")
+LINEFIT_MODEL = ("none", "translation", "affine", "projective")
+LINEFIT_CAUSE = ("lines", "pivot", "cap")
+LINEFIT_FRAME_DTYPE = np.dtype([("status", "<i4"), ("model", "<i4"), ("rounds", "<i4"), ("n_line", "<i4"), ("n_before", "<i4"), ("n_after", "<i4"), ("fall", "<i4"),
+                                ("reserved", "<i4"), ("e2_before", "<i8"), ("e2_after", "<i8"), ("shift2", "<i8")])                    # EagleLineFitFrame (56 bytes)
+assert C.sizeof(EagleLineFitParams) == 88 and LINEFIT_FRAME_DTYPE.itemsize == 56                                                       # linefit.hip asserts them too
+
+
 class EagleKinematicsParams(C.Structure):
     """include/eagle.h EagleKinematicsParams: frames per second, the largest frame gap that is still differenced, the speed cap (m/s)."""
     _fields_ = [("fps", C.c_int32), ("max_gap", C.c_int32), ("speed_cap", C.c_double), ("reserved", C.c_int64)]
@@ -541,6 +558,11 @@ def load():
     L.eagle_ground_device_frames.argtypes = [vp, vp, i32, vp, vp, vp, vp, grp, i32, lay, vp, vp]
     L.eagle_ground_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, grp, i32, lay, vp, vp]
     L.eagle_op_ground.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, grp, i32, lay, vp, vp]
+    lfp = C.POINTER(EagleLineFitParams)
+    L.eagle_linefit_params_default.argtypes = [lfp]
+    L.eagle_linefit_device_frames.argtypes = [vp, vp, i32, vp, vp, vp, lfp, vp, vp, vp]
+    L.eagle_linefit_frames.argtypes = [vp, vp, i32, i64, vp, vp, vp, lfp, vp, vp, vp]
+    L.eagle_op_linefit.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, lfp, vp, vp, vp]
     lp = C.POINTER(EagleLoadParams)
     sp = C.POINTER(EagleSmoothParams)
     L.eagle_post_smooth_tracks.argtypes = [vp, vp, sp]
@@ -608,7 +630,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_reid_gate", "eagle_op_reid_head", "eagle_op_conv2d_sliced", "eagle_op_maxpool5", "eagle_op_upsample2", "eagle_op_split_to_f32", "eagle_op_gray_pyramid",
            "eagle_op_flow", "eagle_op_ecc_small", "eagle_op_ecc", "eagle_post_smooth_tracks", "eagle_post_smooth_values", "eagle_post_device_smooth",
            "eagle_post_raw_values", "eagle_op_smooth_tracks", "eagle_post_stabilise", "eagle_post_stabilise_values", "eagle_post_original_values",
-           "eagle_post_device_stabilise", "eagle_op_stabilise"]
+           "eagle_post_device_stabilise", "eagle_op_stabilise", "eagle_linefit_params_default", "eagle_linefit_device_frames", "eagle_linefit_frames",
+           "eagle_op_linefit"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 ECC_DTYPE = np.dtype([("ok", "<i4"), ("iters", "<i4"), ("rho", "<f8"), ("M", "<f4", (6,))], align=True)      # EagleEccResult
@@ -1003,6 +1026,32 @@ class Handle:
         self._check(self.L.eagle_ground_frames(self._h, _ptr(frames, keep), n, int(max_staging_bytes), _ptr(Hs, keep), _ptr(valid, keep), _ptr(shapes, keep), _ptr(off, keep),
                                                C.byref(p), _out_pix(fmt), None if lay is None else C.byref(lay), _ptr(out, keep), _ptr(cov, keep)), "ground_frames")
         return out, cov
+
+    # --- line registration: each frame's homography refined on the painted lines (include/eagle.h, eagle_linefit_*) ---------------------
+    def linefit_device(self, d_bgr, n, Hs, valid, recs=None, params=None, masks=False):
+        """n dense BGR frames resident in HBM + their homographies (+ the records, whose detections are the boxes) -> (Hs_out float64 [n, 9], frames
+        LINEFIT_FRAME_DTYPE [n], masks uint32 [n, h, (w + 31) // 32] or None)."""
+        return self._linefit("linefit_device", None, d_bgr, n, Hs, valid, recs, params, masks, 0)
+
+    def linefit(self, frames, Hs, valid, recs=None, params=None, masks=False, max_staging_bytes=0):
+        """Same for frames uint8 [n, h, w, 3] in host memory, uploaded in passes of ``max_staging_bytes`` (0: 64 MB)."""
+        return self._linefit("linefit", frames, None, None, Hs, valid, recs, params, masks, max_staging_bytes)
+
+    def _linefit(self, what, frames, d_bgr, n, Hs, valid, recs, params, masks, max_staging_bytes):
+        frames, n, Hs, valid = self._topview_clip(what, frames, Hs, valid, n)
+        recs = _topview_recs(recs, n)
+        p = linefit_params() if params is None else params
+        out, fr = np.zeros((n, 9), np.float64), np.zeros(n, LINEFIT_FRAME_DTYPE)
+        mk = np.zeros((n, self.cfg.frame_h, (self.cfg.frame_w + 31) // 32), np.uint32) if masks else None
+        keep = np.zeros(16, np.uint8)
+        if frames is None:
+            rc = self.L.eagle_linefit_device_frames(self._h, d_bgr, n, _ptr(Hs, keep), _ptr(valid, keep), _ptr(recs, keep), C.byref(p), _ptr(out, keep), _ptr(fr, keep),
+                                                    _ptr(mk, keep))
+        else:
+            rc = self.L.eagle_linefit_frames(self._h, _ptr(frames, keep), n, int(max_staging_bytes), _ptr(Hs, keep), _ptr(valid, keep), _ptr(recs, keep), C.byref(p),
+                                             _ptr(out, keep), _ptr(fr, keep), _ptr(mk, keep))
+        self._check(rc, what)
+        return out, fr, mk
 
     # --- annotated output (include/eagle.h, eagle_annotate_*) --------------------------------------------------
     def annotate_device(self, d_bgr, n, recs, d_out, team_mapping=None, fmt="bgr", layout=None):
@@ -2925,6 +2974,47 @@ def op_topview(frames, Hs, valid, params, boxes=None, mode=TOPVIEW_VIDEO, fmt="b
     if (mode & TOPVIEW_VIDEO) and lay is None:
         res["video"] = out.reshape((n, Hc, W, 3) if _out_pix(fmt) == 0 else (n, Hc * 3 // 2, W))
     return res
+
+
+def linefit_params(**kw):
+    """EagleLineFitParams: the library's defaults (eagle_linefit_params_default: k 4, tau 200, rounds 5, model 3, min_points 200, min_per_line 20, box_pad 3,
+    radius 2.5, radius_min 0.5, radius_factor 0.6, max_shift 3, max_step 4: conventional choices, not fitted to footage) with the given fields replaced."""
+    p = EagleLineFitParams()
+    load().eagle_linefit_params_default(C.byref(p))
+    names = {f[0] for f in EagleLineFitParams._fields_} - {"reserved"}
+    for k, v in kw.items():
+        if k not in names:
+            raise EagleError(f"linefit_params: unknown parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def op_linefit(frames, Hs, valid, params=None, boxes=None, masks=True, device=0):
+    """The line-registration launches on constructed frames (include/eagle.h eagle_op_linefit): frames uint8 [n, h, w, 3] of any size, Hs [n, 9], valid [n],
+    boxes a list of n float32 [k, 4] arrays (or None) -> (Hs_out float64 [n, 9], frames LINEFIT_FRAME_DTYPE [n], masks uint32 [n, h, (w + 31) // 32] or
+    None)."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.uint8)
+    if frames.ndim != 4 or frames.shape[3] != 3:
+        raise EagleError(f"op_linefit: frames must be [n, h, w, 3] (got {frames.shape})")
+    n, h, w, _ = frames.shape
+    Hs, valid = _topview_maps("op_linefit", Hs, valid, n)
+    p = linefit_params() if params is None else params
+    keep = np.zeros(16, np.uint8)
+    flat, off = None, None
+    if boxes is not None:
+        if len(boxes) != n:
+            raise EagleError(f"op_linefit: {n} frames but {len(boxes)} box lists")
+        per = [np.ascontiguousarray(b, np.float32).reshape(-1, 4) for b in boxes]
+        off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(b) for b in per])]), np.int32)
+        flat = np.ascontiguousarray(np.concatenate(per) if per else np.zeros((0, 4)), np.float32)
+    out, fr = np.zeros((n, 9), np.float64), np.zeros(n, LINEFIT_FRAME_DTYPE)
+    mk = np.zeros((n, h, (w + 31) // 32), np.uint32) if masks else None
+    rc = L.eagle_op_linefit(device, _ptr(frames, keep), n, h, w, _ptr(Hs, keep), _ptr(valid, keep), _ptr(flat, keep), _ptr(off, keep), C.byref(p), _ptr(out, keep),
+                            _ptr(fr, keep), _ptr(mk, keep))
+    if rc:
+        raise EagleError(f"eagle_op_linefit failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out, fr, mk
 
 
 def ground_params(key_min=48, key_lead=16, no_cull=False):

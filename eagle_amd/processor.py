@@ -100,6 +100,11 @@ class Processor:
         """The frames warped onto the pitch plane with their homographies: see CoordinateModel.topview and eagle_amd/topview.py."""
         return self.model.topview(frames, coords_or_records, carry, out_format, **kw)
 
+    def refine_lines(self, frames, coords_or_records, fps=None, **params):
+        """Each frame's homography refined on its painted lines, the accepted frames re-projected -> (coordinates, report): see
+        CoordinateModel.refine_lines and eagle_amd/linefit.py.  Run it directly after get_coordinates; process_data takes the new dict."""
+        return self.model.refine_lines(frames, coords_or_records, fps, **params)
+
     def annotate(self, frames, coords_or_records, team_mapping=None, pixel_format="bgr", out_format="bgr", table=None):
         """The annotated frames of a clip (the reference's annotated video, main.py:43-81), drawn on the GPU: see CoordinateModel.annotate.
         ``table``: draw the processed table (process_data above) instead of the raw records."""

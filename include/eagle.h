@@ -1444,6 +1444,92 @@ int eagle_ground_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t max_s
 int eagle_op_ground(int device, const uint8_t* bgr, int n, int h, int w, const double* Hs, const uint8_t* valid, const EagleGroundShape* shapes, const int32_t* off,
                     const EagleGroundParams* p, int out_format, const EagleYuvLayout* out_layout, uint8_t* out, uint32_t* covered);
 
+/* ---- line registration: each frame's homography moved until the frame's painted-line pixels lie on the pitch model's lines (own specification:
+ * tests/linefit_ref.py defines every bit of the masks, the matrices and the records) ----
+ * The one stage that measures a homography against something absolute, before anything is projected with it.  Input: n dense BGR frames [h][w][3],
+ * Hs [n][9] (row-major, image -> pitch), valid [n], optionally the detection boxes of each frame.  Lengths held in integers are in Q = 1 / 1024 m.
+ *   LINE PIXELS  Y = b + 2 g + r; grass: g >= 48 and g - max(r, b) >= 16.  A pixel (x, y) with k <= x <= w - 1 - k and k <= y <= h - 1 - k is a line
+ *            pixel iff for the horizontal or the vertical direction d both p - k d and p + k d are grass and Y(p) - max(Y(p - k d), Y(p + k d)) >= tau,
+ *            and it lies in no detection box widened by box_pad (x1 - box_pad <= x <= x2 + box_pad, likewise y, float64, inclusive).  The mask of a
+ *            frame is u32 [h][(w + 31) / 32], pixel x in bit x & 31 of word x >> 5: the set does not depend on how the work is split.
+ *   TARGETS  the centre lines of the minimap's markings: 17 axis-aligned segments, the centre circle and the two penalty arcs (beyond the penalty area's
+ *            front line), positions and the radius rounded once to Q; the marks are no targets.
+ *   MAP      sb = (h6 ((w - 1) / 2) + h7 (h - 1)) + h8; NO MAP when valid is 0, an h_i or sb is not finite, or sb == 0; G = H when sb > 0, else -H.
+ *   ROUND    every line pixel is mapped with the frame's current matrix (float64, single operations, w' > 0, |X|, |Y| <= 1024, then floor(X 1024 + 0.5)),
+ *            matched to the candidate primitive of least e^2 (segments: the signed distance along the normal, only inside the span; arcs:
+ *            floor((|P - c|^2 - R^2 + R) / (2 R)); ties to the earlier primitive) and is an inlier iff e^2 <= rq^2, rq falling from `radius` by
+ *            `radius_factor` per round to `radius_min`.  Its row is the gradient (1 / 128) times the derivative of the correction
+ *            dx = a0 + a1 x + a2 y - (a6 x + a7 y) x, dy = a3 + a4 x + a5 y - (a6 x + a7 y) y about the centre spot (x, y in 1 / 512 of 64 m), all
+ *            integers below 2^17; the normal matrix, the right-hand side, the inlier count, the sum of e^2 and the inliers per primitive are exact
+ *            64-bit integer sums, which cannot overflow for a frame of at most 2^28 pixels.  The ladder projective (8) -> affine (6) -> translation
+ *            (2) -> none is decided from the number of primitives of each orientation that hold min_per_line inliers, a pivot test (1e-9 of the largest
+ *            diagonal entry) and the cap max_step on every |64 a_i|; Gaussian elimination in float64 with partial pivoting; the new matrix is
+ *            T (D (T^-1 M)).
+ *   DECIDE   the refined matrix is ACCEPTED iff a round changed it, it has min_points inliers at radius_min, its mean e^2 there is below the
+ *            original's, and none of nine image points (corners, edge centres, centre) that the original maps to within 10 m of the pitch moved by
+ *            more than max_shift.  Otherwise the frame keeps its nine doubles bit for bit and the status says why.  Frames are independent.
+ * The constants are conventional choices, not fitted to data, and nothing is validated on real footage.  Limits: straight centre lines and three arcs
+ * only; no lens distortion; a line pixel is a colour-and-contrast rule, so white boots outside a box and advertising on grass-coloured ground are
+ * candidates until the radius shuts them out; a view with fewer than two line directions can only be shifted; a wrong but self-consistent match (the
+ * goal-area line taken for the penalty-area line) is possible and bounded only by radius and max_shift.  Launches (linefit.hip) on the handle's main
+ * stream, chained without host synchronisation between the rounds; device memory is allocated per call and freed; records, staging buffers and graphs
+ * of the handle are not involved.  EAGLE_E_INVALID with a message, before any launch: NULL pointers (parameters, Hs_out, frames_out; frames, Hs, valid
+ * with n > 0), k outside 1 .. 64, tau outside 1 .. 1020, rounds outside 0 .. 16, model outside 1 .. 3, min_points or min_per_line < 1, box_pad negative
+ * or not finite, not 0 < radius_min <= radius <= 8 (radius_min at least 1 / 2048 m), radius_factor outside (0, 1], max_shift outside 0 .. 1024, max_step
+ * outside (0, 64], non-zero reserved words, box offsets not ascending from 0 or more than EAGLE_MAX_DET boxes in a frame (an n_det outside that range),
+ * a negative max_staging_bytes, n < 0; in the operator entry a frame side outside 1 .. 16384.  n == 0 succeeds and writes
+ * nothing.  masks_out may be NULL. */
+#define EAGLE_LINEFIT_NO_MAP 0         /* EagleLineFitFrame::status */
+#define EAGLE_LINEFIT_ACCEPTED 1
+#define EAGLE_LINEFIT_UNCHANGED 2      /* no round could move the matrix (or rounds == 0) */
+#define EAGLE_LINEFIT_FEW_POINTS 3
+#define EAGLE_LINEFIT_NO_GAIN 4
+#define EAGLE_LINEFIT_SHIFT 5
+#define EAGLE_LINEFIT_NONE 0           /* EagleLineFitFrame::model, EagleLineFitParams::model (1 .. 3) */
+#define EAGLE_LINEFIT_TRANSLATION 1
+#define EAGLE_LINEFIT_AFFINE 2
+#define EAGLE_LINEFIT_PROJECTIVE 3
+#define EAGLE_LINEFIT_FALL_LINES 0     /* EagleLineFitFrame::fall: bit 3 (rung - 1) + cause */
+#define EAGLE_LINEFIT_FALL_PIVOT 1
+#define EAGLE_LINEFIT_FALL_CAP 2
+typedef struct EagleLineFitParams {
+    int32_t k, tau;                /* the line-pixel rule (conventionally 4 and 200, i.e. 50 grey levels) */
+    int32_t rounds;                /* conventionally 5 */
+    int32_t model;                 /* the ladder's top rung (conventionally EAGLE_LINEFIT_PROJECTIVE) */
+    int32_t min_points;            /* inliers at radius_min a refined matrix needs (conventionally 200) */
+    int32_t min_per_line;          /* inliers that make a primitive count for the ladder (conventionally 20) */
+    double box_pad;                /* pixels (conventionally 3) */
+    double radius, radius_min;     /* metres (conventionally 2.5 and 0.5) */
+    double radius_factor;          /* per round (conventionally 0.6) */
+    double max_shift;              /* metres (conventionally 3) */
+    double max_step;               /* metres at 64 m from the centre spot, per unknown and round (conventionally 4) */
+    int32_t reserved[4];           /* 0 */
+} EagleLineFitParams;              /* 88 bytes */
+typedef struct EagleLineFitFrame {
+    int32_t status;                /* EAGLE_LINEFIT_NO_MAP .. _SHIFT */
+    int32_t model;                 /* the last round's rung */
+    int32_t rounds;
+    int32_t n_line;                /* line pixels of the frame */
+    int32_t n_before, n_after;     /* inliers at radius_min under the original and under the last matrix */
+    int32_t fall;                  /* every rung that fell in any round, and why */
+    int32_t reserved;
+    int64_t e2_before, e2_after;   /* their sums of e^2 (Q^2) */
+    int64_t shift2;                /* the largest squared shift of the nine image points (Q^2); -1: a point left the map */
+} EagleLineFitFrame;               /* 56 bytes */
+int eagle_linefit_params_default(EagleLineFitParams* p);
+/* n frames of the handle's size, dense, resident in HBM.  Hs, valid, recs (NULL: no boxes; else the detections of each record are the boxes) are host
+ * memory; Hs_out [n][9], frames_out [n] and masks_out (NULL or u32 [n][h][(w + 31) / 32]) are host memory; returns when they are complete. */
+int eagle_linefit_device_frames(EagleHandle* h, const uint8_t* d_bgr, int n, const double* Hs, const uint8_t* valid, const EagleFrameResult* recs,
+                                const EagleLineFitParams* p, double* Hs_out, EagleLineFitFrame* frames_out, uint32_t* masks_out);
+/* Same for a clip in host memory, uploaded in passes of what max_staging_bytes (0: 64 MB; always at least one frame) of device staging hold.  The
+ * result does not depend on the size of a pass. */
+int eagle_linefit_frames(EagleHandle* h, const uint8_t* bgr, int n, int64_t max_staging_bytes, const double* Hs, const uint8_t* valid, const EagleFrameResult* recs,
+                         const EagleLineFitParams* p, double* Hs_out, EagleLineFitFrame* frames_out, uint32_t* masks_out);
+/* Operator entry (host buffers in / out, no handle): dense frames of any h x w within 1 .. 16384 per side.  boxes [box_off[n]][4] =
+ * x1, y1, x2, y2 and box_off [n + 1] stand for the records; both NULL: no boxes. */
+int eagle_op_linefit(int device, const uint8_t* bgr, int n, int h, int w, const double* Hs, const uint8_t* valid, const float* boxes, const int32_t* box_off,
+                     const EagleLineFitParams* p, double* Hs_out, EagleLineFitFrame* frames_out, uint32_t* masks_out);
+
 /* ---- occupancy heat maps: where a player, a team and the ball spent their time (own specification: tests/occupancy_ref.py defines every output bit) ----
  * A call computes n_sel maps.  Selection s is the list sel_cols[sel_off[s] .. sel_off[s + 1] - 1] of table column indices (sel_off[n_sel + 1] ascends from
  * 0).  Members must be pitch columns (video == 0) of kind Player, Goalkeeper or Ball; a column may appear in several selections, not twice in one; an
