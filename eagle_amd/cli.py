@@ -26,7 +26,10 @@ frame each team's centroid, length, width, hull area, stretch, lines and convex 
 draws the two hulls into the minimap.  ``--physical`` (with ``--processed``) writes ``physical.json``: per id the distance and the seconds per speed
 zone, the total distance, the top speed, the high-speed runs, sprints, accelerations and decelerations, and the list of those efforts
 (eagle_amd/physical.py; ``--physical-edges a,b,c,d`` sets the zone edges in m/s, ``--physical-rows`` adds the per-frame speed, acceleration and zone); the figures follow a person only with ``--merge-ids``.  ``--stabilise`` (with ``--processed``) estimates, per kept frame, the motion that every player and the ball share (the small translation, stretch and shear of the pitch plane that a slightly wrong homography gives them at once) from what the players' own paths predict, removes it directly after the table is built and before ``--smooth-tracks``, and writes ``stabilise.json`` (eagle_amd/stabilise.py; ``--stabilise-window``, ``--stabilise-degree``, ``--stabilise-model``, ``--stabilise-min-voters``, ``--stabilise-iterations``, ``--stabilise-trim`` and ``--stabilise-floor`` set the rule, conventional choices that are not fitted to data, ``--stabilise-rows`` adds a record per kept frame); ``metadata.json`` then says ``"stabilised": true``.  ``--smooth-tracks`` (with ``--processed``) replaces the pitch positions of every Player and Goalkeeper by windowed least-squares fits directly after the table is built, trims jumps, hands the fits' velocities to ``kinematics.json``, the physical report, pass options and the control grid, and writes ``smooth.json`` (eagle_amd/smooth.py; ``--smooth-window``, ``--smooth-degree``, ``--smooth-outlier``, ``--smooth-floor`` and ``--smooth-ball`` set the rule, conventional choices that are not fitted to data, ``--smooth-rows`` adds the per-cell records); ``metadata.json`` then says ``"positions": "smoothed"``.  ``--ball-track`` (with ``--processed``) makes the table's ball the detection of every frame that lies on the best physically possible path through the clip, not the reference's choice, and writes ``ball_track.json`` (eagle_amd/balltrack.py; ``--ball-track-speed``, ``-gap``, ``-reward``, ``-break`` set the rule, ``--ball-track-rows`` adds a record per frame).  ``--team-method cluster`` (with ``--processed`` or ``--annotated``) finds the team mapping as the two clusters of the ids' kit colours over the clip instead of by the reference's named colour ranges, and writes ``teams.json`` (eagle_amd/kits.py; ``--team-min-pixels``, ``--team-min-crops``, ``--team-outlier`` set the rule).  ``--pass-options`` (with ``--processed``) writes ``pass_options.json``: per kept frame where the ball's owner could play and per pass event how the pass played ranks among the open ones (eagle_amd/options.py; ``--pass-options-grid R`` adds ``pass_options.npy``, ``--pass-options-pictures`` one PPM per pass event).  ``--roles`` (with ``--processed``) writes ``roles.json``: each team's mean formation, its lines and a label such as 4-4-2, the rows every id played in each role, every change of role and who held each role when (eagle_amd/roles.py; ``--roles-count R``, ``--roles-min-present M``, ``--roles-iterations T`` and ``--roles-lines L`` set the parameters, ``--roles-rows`` adds the ids per role and kept frame); a role follows what a player does, whatever ids the tracker gave.  ``--space`` (with ``--processed``) writes ``space.json``: per id the area of the pitch nearer to him than to anybody else (mean, smallest, largest, by thirds), the mean distance to the nearest opponent, how often an opponent stands within ``--space-radius`` metres and who usually marks him; per team its share of the pitch; with ``--possession`` the owner's room per frame and per pass (eagle_amd/space.py; ``--space-grid R`` cells per metre, ``--space-rows`` adds the per-frame records, ``--space-map`` writes the owner maps as ``space.npy``); an area follows a person only with ``--merge-ids``.  ``--offside`` (with ``--processed``) writes ``offside.json``: per team the offside line of every kept frame (the deepest of the second-last opponent, the halfway line and the ball), per id how often he stood beyond it and by how much at most, and with ``--possession`` per pass whether the receiver was onside, close or offside when the ball was played (eagle_amd/offside.py; ``--offside-direction auto|right|left``, ``--offside-tolerance M``, ``--offside-no-assumed-keeper``, ``--offside-rows`` adds the per-frame lines and margins); only foot points are known and a defender the camera does not see is not counted.  ``--offside-view`` (with ``--processed --offside``) writes ``offside_view.y4m``, the annotated video with that line lying on the grass under the players, and ``offside_view.json``; ``--offside-stills`` (with ``--possession`` too) writes ``offside_<k>.ppm`` per pass with a verdict (eagle_amd/ground.py; the line is only as good as the frame's homography).  ``--shots`` writes ``shots.json``: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at the pitch (eagle_amd/shots.py; ``--shots-cut``, ``--shots-low``, ``--shots-grass``, ``--shots-window`` and ``--shots-min-len`` set the parameters, conventional choices that are not fitted to footage); ``--trim-to-shot auto`` (or a shot's index) keeps only that shot's frames for everything that follows, the trimming the reference's README asks its users to do by hand.  ``--topview`` writes ``topview.y4m``: every frame warped onto the pitch plane with its homography, the check of the one input every analysis stage trusts (eagle_amd/topview.py; ``--topview-scale``, ``--topview-margin``, ``--topview-markings``, ``--topview-carry``); ``--topview-mosaic`` adds ``topview_mosaic.ppm``, ``topview_count.npy`` and ``topview.json``, per frame its coverage and its distance from the mosaic (``--topview-mask-boxes``, ``--topview-step``, ``--topview-min-count``, ``--topview-suspect``; the suspect ratio 2.0 is a conventional choice, not fitted to footage).  Video decode and compressed encode are out of scope (SURVEY §8f rows 3-4).  The cadence is main.py:27's by default (homography once per second, key-point model three times per
-second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame)."""
+second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame).  ``--ball-flights`` (with
+``--processed``) writes ``ball_flights.json``: the ball's path cut into straight flights of constant speed, the kicks between them, the shots and, with
+``--possession``, per pass its kick, kicker and speed (eagle_amd/flights.py; ``--ball-flights-rows``, ``-noise``, ``-penalty``, ``-spike``, ``-kick``,
+``-shot`` set the rule, ``--ball-flights-cells`` adds the per-row arrays)."""
 import argparse
 import json
 import os
@@ -236,6 +239,17 @@ def main(argv=None):
     ap.add_argument("--team-outlier", type=float, default=None, metavar="R",
                     help="with --team-method cluster: an id farther from its team's medoid than R times the distance between the medoids is in neither team, "
                          "0 .. 1024, 0 = off (default 0.5)")
+    ap.add_argument("--ball-flights", action="store_true",
+                    help="with --processed: cut the ball's path into straight flights of constant speed and write <out>/ball_flights.json: the flights (still, carried, "
+                         "free), the kicks between them, the shots and, with --possession, per pass its kick, kicker and speed.  With --shots or --trim-to-shot the "
+                         "shots' first frames break the path (eagle_amd/flights.py; the constants are conventional choices, not fitted to data)")
+    ap.add_argument("--ball-flights-rows", type=int, default=None, metavar="L", help="with --ball-flights: the longest flight in rows, 2 .. 128 (default 64)")
+    ap.add_argument("--ball-flights-noise", type=float, default=None, metavar="M", help="with --ball-flights: the noise of a ball sample in metres (default 0.25)")
+    ap.add_argument("--ball-flights-penalty", type=float, default=None, metavar="P", help="with --ball-flights: the price of a flight in noise variances (default 16)")
+    ap.add_argument("--ball-flights-spike", type=float, default=None, metavar="M", help="with --ball-flights: a sample this far off its neighbours' line is set aside (default 1.0)")
+    ap.add_argument("--ball-flights-kick", type=float, default=None, metavar="V", help="with --ball-flights: the change of velocity of a kick in m/s (default 3)")
+    ap.add_argument("--ball-flights-shot", type=float, default=None, metavar="V", help="with --ball-flights: the least speed of a shot in m/s (default 10)")
+    ap.add_argument("--ball-flights-cells", action="store_true", help="with --ball-flights: also write the per-row arrays into ball_flights.json")
     ap.add_argument("--shots", action="store_true",
                     help="also write <out>/shots.json: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at "
                          "the pitch, and put the shot count into metadata.json (the thresholds are conventional choices, not fitted to footage)")
@@ -487,6 +501,19 @@ def main(argv=None):
             ap.error("--refine-lines-max-shift takes 0 .. 1024 metres")
         if not 1 <= a.lines_set.get("tau", 200) <= 1020:
             ap.error("--refine-lines-contrast takes 1 .. 1020")
+    a.ball_flights_set = {k: v for k, v in (("max_rows", a.ball_flights_rows), ("noise", a.ball_flights_noise), ("penalty", a.ball_flights_penalty),
+                                            ("spike", a.ball_flights_spike), ("kick_dv", a.ball_flights_kick), ("shot_speed", a.ball_flights_shot)) if v is not None}
+    if a.ball_flights and not a.processed:
+        ap.error("--ball-flights works on the processed table: it needs --processed")
+    if (a.ball_flights_set or a.ball_flights_cells) and not a.ball_flights:
+        ap.error("--ball-flights-rows, --ball-flights-noise, --ball-flights-penalty, --ball-flights-spike, --ball-flights-kick, --ball-flights-shot and "
+                 "--ball-flights-cells set the ball flights: they need --ball-flights")
+    if a.ball_flights:
+        from . import flights as _flights
+        try:
+            _flights.resolve(a.fps, **a.ball_flights_set)
+        except ValueError as e:
+            ap.error(str(e))
     if a.smooth_tracks and not a.processed:
         ap.error("--smooth-tracks works on the processed table: it needs --processed")
     if (a.smooth_set or a.smooth_rows) and not a.smooth_tracks:
@@ -625,6 +652,12 @@ def main(argv=None):
             from . import possession as po
             with open(os.path.join(a.out, "possession.json"), "w") as f:
                 json.dump(po.to_json(po.possession(model.handle, table, a.fps)), f)
+        if a.ball_flights:                                                 # reads the table's ball column as it is; changes nothing in the table
+            from . import balltrack as bt, flights as fls
+            cuts = bt.cuts_of_shots(found_shots, first_frame, n) if found_shots is not None else None
+            res = fls.ball_flights(model.handle, table, a.fps, cuts, **a.ball_flights_set)
+            with open(os.path.join(a.out, "ball_flights.json"), "w") as f:
+                json.dump(fls.to_json(res, events=model.handle.events(table) if a.possession else None, cells=a.ball_flights_cells), f)
         if a.occupancy:
             from . import occupancy as oc
             occ = oc.occupancy(model.handle, table, a.fps, a.occupancy_grid, a.occupancy_sigma)
@@ -704,6 +737,8 @@ def main(argv=None):
             meta["stabilised"] = True                                      # each kept frame's common motion was removed (stabilise.json)
         if a.smooth_tracks:
             meta["positions"] = "smoothed"                                 # the table's pitch positions are the fits' (smooth.json)
+        if a.ball_flights:
+            meta["ball_flights"] = True                                    # ball_flights.json
         if a.ball_track:
             meta["ball"] = "ball_track"                                    # the table's ball is the tracked one (ball_track.json)
         if team_report is not None:

@@ -323,6 +323,11 @@ struct EaglePostTable {
     void* d_stab = nullptr;              // EagleStabRow [rows] | votes i32 [cols][rows][2] | EagleStabTotals, each from a 256-byte boundary; both nullptr before
     bool has_stab = false;               // the call, resident until eagle_post_free
     EagleStabTotals stab_totals{};
+    void* d_flights = nullptr;           // ball flights (eagle_post_ball_flights): seg i32 [rows] | flags u8 [rows] | fitted f64 [rows][2] | velocity f64 [rows][2], each
+    bool has_flights = false;            // from a 256-byte boundary; nullptr before the first call (and with no rows), resident until eagle_post_free
+    std::vector<EagleBallFlight> flights;
+    std::vector<EagleBallKick> kicks;
+    EagleFlightTotals flight_totals{};
 };
 
 namespace eagle {

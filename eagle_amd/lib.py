@@ -292,6 +292,31 @@ SMOOTH_TOTALS_DTYPE = np.dtype([("sum_sq", "<i8"), ("present", "<i4"), ("outlier
 assert C.sizeof(EagleSmoothParams) == 56 and SMOOTH_TOTALS_DTYPE.itemsize == 32                                  # the sizes smooth.hip asserts of the C structs
 
 
+class EagleFlightParams(C.Structure):
+    """include/eagle.h EagleFlightParams: frames per second, the largest frame step inside a run, the longest segment in rows (L), the sample noise (m) and
+    the penalty per segment in units of its square, the spike threshold (m), the kick threshold (m/s), possession's radius (m), the speeds (m/s) below
+    which a flight is still and from which it may be a shot, a shot's range and margin (m), and the layout of the cost table (FLIGHT_LAYOUT_*)."""
+    _fields_ = [("fps", C.c_double), ("max_gap", C.c_int32), ("max_rows", C.c_int32), ("noise", C.c_double), ("penalty", C.c_double), ("spike", C.c_double),
+                ("kick_dv", C.c_double), ("radius", C.c_double), ("still_speed", C.c_double), ("shot_speed", C.c_double), ("shot_range", C.c_double),
+                ("shot_margin", C.c_double), ("layout", C.c_int32), ("reserved", C.c_int32)]
+
+
+FLIGHT_STILL, FLIGHT_CARRIED, FLIGHT_FREE = 0, 1, 2                                                              # EagleBallFlight.kind
+FLIGHT_KIND_NAMES = ("still", "carried", "free")
+FLIGHT_ROW_PRESENT, FLIGHT_ROW_USED, FLIGHT_ROW_SPIKE, FLIGHT_ROW_KNOT, FLIGHT_ROW_KICK = 1, 2, 4, 8, 16          # the bits of a row's flags
+FLIGHT_CAPPED, FLIGHT_CONTINUES = 1, 2                                                                           # EagleBallFlight.flags
+FLIGHT_LAYOUT_DEFAULT, FLIGHT_LAYOUT_END_MAJOR, FLIGHT_LAYOUT_K_MAJOR = 0, 1, 2
+FLIGHT_TIMES = ("prepare", "cost", "walk", "path", "fit", "events", "total")                                     # times_ms of eagle_op_ball_flights
+FLIGHT_DTYPE = np.dtype([("row0", "<i4"), ("row1", "<i4"), ("used", "<i4"), ("spikes", "<i4"), ("near", "<i4"), ("kind", "<i4"), ("shot", "<i4"), ("flags", "<i4"),
+                         ("x0", "<f8"), ("y0", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("vx", "<f8"), ("vy", "<f8"), ("speed", "<f8"), ("rms", "<f8"),
+                         ("y_cross", "<f8"), ("c", "<i8")])                                                       # EagleBallFlight (112 bytes)
+KICK_DTYPE = np.dtype([("row", "<i4"), ("seg_in", "<i4"), ("seg_out", "<i4"), ("col", "<i4"), ("speed_in", "<f8"), ("speed_out", "<f8"), ("dv", "<f8"),
+                       ("cos_turn", "<f8")])                                                                      # EagleBallKick (48 bytes)
+FLIGHT_TOTALS_DTYPE = np.dtype([("runs", "<i4"), ("flights", "<i4"), ("kinds", "<i4", 3), ("spikes", "<i4"), ("knots", "<i4"), ("kicks", "<i4"),
+                                ("shots", "<i4", 3), ("capped", "<i4"), ("sum_c", "<i8"), ("reserved", "<i8")])   # EagleFlightTotals (64 bytes)
+assert C.sizeof(EagleFlightParams) == 96 and FLIGHT_DTYPE.itemsize == 112 and KICK_DTYPE.itemsize == 48 and FLIGHT_TOTALS_DTYPE.itemsize == 64
+
+
 class EagleStabParams(C.Structure):
     """include/eagle.h EagleStabParams: frames per second, the half-width in frames, the degree (1, 2), the model (0 translation, 1 affine), the fewest
     voters of a row, the rounds, the trimming multiple (0: none), its floor (m), the least spread
@@ -597,6 +622,14 @@ def load():
     L.eagle_op_flow.argtypes = [i32, u8p, i32, i32, i32, i32, i32, i32, vp, i32, vp, C.POINTER(i32), fp, u8p]
     L.eagle_op_ecc_small.argtypes = [i32, u8p, i32, i32, i32, C.c_double, u8p, C.POINTER(i32), C.POINTER(i32)]
     L.eagle_op_ecc.argtypes = [i32, u8p, i32, i32, i32, u8p, C.POINTER(i32), i32, i32, C.c_double, vp]
+    flp = C.POINTER(EagleFlightParams)
+    L.eagle_flight_params_default.argtypes = [flp, C.c_double, i32]
+    L.eagle_post_ball_flights.argtypes = [vp, vp, flp, vp, i32]
+    L.eagle_post_ball_flight_values.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.eagle_post_ball_flight_records.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_post_ball_kicks.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
+    L.eagle_post_device_ball_flights.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.eagle_op_ball_flights.argtypes = [i32, vp, vp, vp, i32, i32, vp, i32, flp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int), vp, i32, C.POINTER(C.c_int), vp, vp]
     _lib = L
     return L
 
@@ -631,7 +664,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_op_flow", "eagle_op_ecc_small", "eagle_op_ecc", "eagle_post_smooth_tracks", "eagle_post_smooth_values", "eagle_post_device_smooth",
            "eagle_post_raw_values", "eagle_op_smooth_tracks", "eagle_post_stabilise", "eagle_post_stabilise_values", "eagle_post_original_values",
            "eagle_post_device_stabilise", "eagle_op_stabilise", "eagle_linefit_params_default", "eagle_linefit_device_frames", "eagle_linefit_frames",
-           "eagle_op_linefit"]
+           "eagle_op_linefit", "eagle_flight_params_default", "eagle_post_ball_flights", "eagle_post_ball_flight_values", "eagle_post_ball_flight_records",
+           "eagle_post_ball_kicks", "eagle_post_device_ball_flights", "eagle_op_ball_flights"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 ECC_DTYPE = np.dtype([("ok", "<i4"), ("iters", "<i4"), ("rho", "<f8"), ("M", "<f4", (6,))], align=True)      # EagleEccResult
@@ -1289,6 +1323,37 @@ class Handle:
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._check(self.L.eagle_post_device_smooth(table._t, C.byref(a), C.byref(b), C.byref(c)), "post_device_smooth")
         return a.value, b.value, c.value
+
+    # --- ball flights (include/eagle.h, eagle_post_ball_flights) ------------------------------------------------------------
+    def ball_flights(self, table, params, cuts=None):
+        """Cuts the ball's pitch column of a PostTable of this handle into flights and kicks and keeps the result with the table (a later call replaces it)
+        -> {"seg": int32 [rows], "flags": uint8 [rows], "fitted", "velocity": float64 [rows][2], "flights": FLIGHT_DTYPE, "kicks": KICK_DTYPE, "totals":
+        FLIGHT_TOTALS_DTYPE [1]}; cuts: the ascending frame numbers that start a new shot."""
+        cuts = np.zeros(0, np.int32) if cuts is None else np.ascontiguousarray(cuts, np.int32)
+        self._check(self.L.eagle_post_ball_flights(self._h, table._t, C.byref(params), cuts.ctypes.data_as(C.c_void_p) if len(cuts) else None, len(cuts)), "post_ball_flights")
+        return self.ball_flight_values(table)
+
+    def ball_flight_values(self, table):
+        """What ball_flights kept with the table; an EagleError before the call."""
+        rows = len(table.rows)
+        out = {"seg": np.zeros(rows, np.int32), "flags": np.zeros(rows, np.uint8), "fitted": np.zeros((rows, 2), np.float64), "velocity": np.zeros((rows, 2), np.float64),
+               "totals": np.zeros(1, FLIGHT_TOTALS_DTYPE)}
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_post_ball_flight_values(table._t, *(_ptr(out[k], keep) for k in ("seg", "flags", "fitted", "velocity", "totals"))), "post_ball_flight_values")
+        n = C.c_int(0)
+        self._check(self.L.eagle_post_ball_flight_records(table._t, None, 0, C.byref(n)), "post_ball_flight_records")
+        out["flights"] = np.zeros(n.value, FLIGHT_DTYPE)
+        self._check(self.L.eagle_post_ball_flight_records(table._t, _ptr(out["flights"], keep), n.value, C.byref(n)), "post_ball_flight_records")
+        self._check(self.L.eagle_post_ball_kicks(table._t, None, 0, C.byref(n)), "post_ball_kicks")
+        out["kicks"] = np.zeros(n.value, KICK_DTYPE)
+        self._check(self.L.eagle_post_ball_kicks(table._t, _ptr(out["kicks"], keep), n.value, C.byref(n)), "post_ball_kicks")
+        return out
+
+    def ball_flights_device(self, table):
+        """(seg int32 [rows], flags uint8 [rows], fitted, velocity float64 [rows][2]) in HBM (None each before ball_flights)."""
+        p = [C.c_void_p() for _ in range(4)]
+        self._check(self.L.eagle_post_device_ball_flights(table._t, *(C.byref(v) for v in p)), "post_device_ball_flights")
+        return tuple(v.value for v in p)
 
     # --- stabilisation (include/eagle.h, eagle_post_stabilise) ------------------------------------------------------------
     def stabilise(self, table, params):
@@ -2307,6 +2372,43 @@ def op_smooth_tracks(values, frames, columns, params, device=0):
                                   *(_ptr(out[k], keep) for k in ("values", "vel", "acc", "flags", "count", "residual_q", "suspect", "totals")))
     if rc:
         raise EagleError(f"eagle_op_smooth_tracks failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return out
+
+
+def flight_params(fps, max_gap=None, max_rows=64, noise=0.25, penalty=16.0, spike=1.0, kick_dv=3.0, radius=2.0, still_speed=0.5, shot_speed=10.0, shot_range=40.0,
+                  shot_margin=2.0, layout=FLIGHT_LAYOUT_DEFAULT):
+    """EagleFlightParams; max_gap None: min(1024, max(1, round(fps))) frames.  The defaults are conventional choices, not fitted to data."""
+    fps = float(fps)
+    gap = min(1024, max(1, int(round(fps)))) if max_gap is None else int(max_gap)
+    return EagleFlightParams(fps, gap, int(max_rows), float(noise), float(penalty), float(spike), float(kick_dv), float(radius), float(still_speed), float(shot_speed),
+                             float(shot_range), float(shot_margin), int(layout), 0)
+
+
+def op_ball_flights(values, frames, columns, params, cuts=None, times=False, device=0):
+    """The ball-flight launches on a constructed table (include/eagle.h eagle_op_ball_flights): values float64 [cols][rows][2], frames int32 [rows] strictly
+    ascending, columns POSTCOL_DTYPE (or (kind, id, video) tuples), cuts ascending frame numbers -> {"seg": int32 [rows], "flags": uint8 [rows], "fitted",
+    "velocity": float64 [rows][2], "flights": FLIGHT_DTYPE, "kicks": KICK_DTYPE, "totals": FLIGHT_TOTALS_DTYPE [1]} and, with times, "times": a dict of
+    milliseconds per FLIGHT_TIMES name."""
+    L = load()
+    values, columns = _table_args("op_ball_flights", values, columns)
+    frames = np.ascontiguousarray(frames, np.int32)
+    cuts = np.zeros(0, np.int32) if cuts is None else np.ascontiguousarray(cuts, np.int32)
+    cols, rows = values.shape[:2]
+    if len(frames) != rows:
+        raise EagleError("op_ball_flights: one frame number per row")
+    out = {"seg": np.zeros(rows, np.int32), "flags": np.zeros(rows, np.uint8), "fitted": np.zeros((rows, 2), np.float64), "velocity": np.zeros((rows, 2), np.float64),
+           "flights": np.zeros(max(rows, 1), FLIGHT_DTYPE), "kicks": np.zeros(max(rows, 1), KICK_DTYPE), "totals": np.zeros(1, FLIGHT_TOTALS_DTYPE)}
+    tm = np.zeros(len(FLIGHT_TIMES), np.float32)
+    keep = np.zeros(8, np.float64)
+    nf, nk = C.c_int(0), C.c_int(0)
+    rc = L.eagle_op_ball_flights(device, _ptr(values, keep), _ptr(frames, keep), _ptr(columns, keep), rows, cols, _ptr(cuts, keep) if len(cuts) else None, len(cuts),
+                                 C.byref(params), *(_ptr(out[k], keep) for k in ("seg", "flags", "fitted", "velocity")), _ptr(out["flights"], keep), len(out["flights"]),
+                                 C.byref(nf), _ptr(out["kicks"], keep), len(out["kicks"]), C.byref(nk), _ptr(out["totals"], keep), tm.ctypes.data_as(C.c_void_p) if times else None)
+    if rc:
+        raise EagleError(f"eagle_op_ball_flights failed ({rc}): {L.eagle_last_error(None).decode()}")
+    out["flights"], out["kicks"] = out["flights"][:nf.value].copy(), out["kicks"][:nk.value].copy()
+    if times:
+        out["times"] = dict(zip(FLIGHT_TIMES, map(float, tm)))
     return out
 
 

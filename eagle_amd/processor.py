@@ -143,6 +143,13 @@ class Processor:
         from . import smooth as sm
         return sm.smooth_tracks(self.model.handle, table, fps, **kw)
 
+    def ball_flights(self, table, fps, cuts=None, **params):
+        """The ball's path of a processed table cut into straight flights of constant speed, the knots between them, the kicks among the knots and the
+        flights that would cross a goal line between the posts (max_gap, max_rows, noise, penalty, spike, kick_dv, radius, still_speed, shot_speed,
+        shot_range, shot_margin; cuts: the frames that start a new shot).  The table's positions are not changed: see eagle_amd/flights.py."""
+        from . import flights as fl
+        return fl.ball_flights(self.model.handle, table, fps, cuts, **params)
+
     def kinematics(self, table, fps, max_gap=None, speed_cap=12.0, keep=False):
         """Velocities of a processed table (computed on the GPU, kept with the table; keep=True: the ones it carries, as after smooth_tracks) plus per
         id distance covered and top speed: see eagle_amd/control.py."""

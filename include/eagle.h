@@ -1873,6 +1873,103 @@ int eagle_op_ecc_small(int device, const uint8_t* gray, int n, int h, int w, dou
 int eagle_op_ecc(int device, const uint8_t* small, int n, int h, int w, const uint8_t* carry /* h*w or NULL */, const int32_t* pairs /* 2*n_pairs */, int n_pairs,
                  int max_iter, double eps, EagleEccResult* out /* n_pairs */);
 
+/* ---- ball flights: the ball's path cut into straight lines of constant speed (own specification: tests/flights_ref.py defines every output bit) -----
+ * Opt-in; a table never asked is byte for byte what it was.  Between two touches a ball moves in a straight line at nearly constant speed on the pitch
+ * plane, and a touch is where that line breaks: the stage finds those lines (flights) and breaks (knots; a knot with a large change of velocity is a
+ * kick).  Integers wherever a sum is formed, float64 with single operations in the order written and no contraction, sqrt and division only.
+ * INPUT.  The table's one Ball pitch column (video == 0), the kept frame numbers f[r], the Player and Goalkeeper pitch columns, and `cuts`: sorted
+ * frame numbers at which a new shot starts (eagle_ball_track's).  A table without a ball column or flagged EAGLE_POST_NO_BALL gives no flight and no
+ * kick: seg -1, flags 0, NaN everywhere.  rows == 0 is success.
+ * PRESENCE.  eagle_post_smooth_tracks' rule: x and y finite and |x|, |y| <= 1024; q = rint(x * 1024) as int64, formed once.
+ * RUNS.  Row r starts a run when r == 0, the ball is absent at r or at r - 1, f[r] - f[r-1] > max_gap, or f[r] is a cut.  A run with fewer than two
+ * present rows has no segment.
+ * SPIKES.  An interior row r of a run (p = r - 1 and n = r + 1 in the same run) has D[r] = f[n] - f[p] and A[r] = the maximum over the two axes of
+ * |(q[r] - q[p]) D[r] - (q[n] - q[p]) (f[r] - f[p])|; A = 0 and D = 1 at a run's first and last row.  Row r is a spike when A[r] > T D[r] with T =
+ * rint(spike * 1024), A[r] D[r-1] > A[r-1] D[r] and A[r] D[r+1] >= A[r+1] D[r]: two adjacent rows are never both spikes, a tie goes to the earlier
+ * row, a run's ends are never spikes.  A spike is not "used": it enters no sum and is no knot; it receives the fitted values of the segment over it.
+ * SEGMENT [i, j], used rows of one run with j - i <= L = max_rows.  Over the used rows r' of [i, j]: t = f[r'] - f[i], per axis d = q[r'] - q[i];
+ * S0 = sum 1, S1 = sum t, S2 = sum t t, per axis B0 = sum d, B1 = sum t d, Q = sum d d (int64: t < 2^17, |d| <= 2^21, at most 129 terms, so
+ * S2 < 2^42, |B1| < 2^46, Q < 2^50 and S0 S2, S1 S1 < 2^50).  det = (double)(S0 S2 - S1 S1), a0 = ((double)S2 (double)B0 - (double)S1 (double)B1) /
+ * det, a1 = ((double)S0 (double)B1 - (double)S1 (double)B0) / det, sse = max(0, (double)Q - (a0 (double)B0 + a1 (double)B1)); cost = sse_x + sse_y,
+ * c(i, j) = (int64) rint(min(cost, 2^40)).
+ * DYNAMIC PROGRAM, per run: lam = rint(penalty ((noise 1024) (noise 1024))) <= 2^40; best[first] = 0, best[j] = min over used i < j with j - i <= L
+ * of best[i] + c(i, j) + lam, a tie to the smaller i; the path is read back from the run's last row.  Segments are numbered in row order over all
+ * runs; a knot is a row two consecutive segments of one run share.
+ * PER SEGMENT EagleBallFlight: fitted ends (((double)q[i] + a0) + a1 t) / 1024; vx = (a1x fps) / 1024, speed = sqrt(vx vx + vy vy); rms =
+ * sqrt((double)c / (double)used) / 1024; near = the used rows whose ball cell has a finite person cell within `radius` (eagle_post_possession's
+ * candidate arithmetic); kind STILL when speed < still_speed, else CARRIED when 2 near > used, else FREE.  SHOT, for a FREE flight with speed >=
+ * shot_speed and vx != 0: X = 105 for vx > 0, else 0; s = (X - x0) / vx, y_cross = y0 + vy s, reach = speed s; with 0 <= reach <= shot_range shot = 2
+ * when |y_cross - 34| <= 3.66, 1 when <= 3.66 + shot_margin, else 0; y_cross is NaN when not evaluated.
+ * PER KNOT: dv = sqrt(dvx dvx + dvy dvy) of the two flights' velocities; a kick when dv >= kick_dv.  EagleBallKick in row order: col = the nearest
+ * finite person cell within `radius` at the row (a tie to the earlier column), -1: a bounce, a post or an unseen player; cos_turn = (vin . vout) /
+ * (speed_in speed_out), NaN when a speed is 0.
+ * PER ROW: seg (the segment that starts at a knot owns the knot row; -1 when absent or in a run without a segment), flags, the fitted position and the
+ * segment's velocity (NaN where seg < 0).  Launches (csrc/flights.hip): prepare, cost, walk, path, fit, events. */
+#define EAGLE_FLIGHT_STILL 0
+#define EAGLE_FLIGHT_CARRIED 1
+#define EAGLE_FLIGHT_FREE 2
+#define EAGLE_FLIGHT_ROW_PRESENT 1     /* per-row flags */
+#define EAGLE_FLIGHT_ROW_USED 2
+#define EAGLE_FLIGHT_ROW_SPIKE 4
+#define EAGLE_FLIGHT_ROW_KNOT 8
+#define EAGLE_FLIGHT_ROW_KICK 16
+#define EAGLE_FLIGHT_CAPPED 1          /* EagleBallFlight.flags: row1 - row0 == max_rows */
+#define EAGLE_FLIGHT_CONTINUES 2       /* the knot at row1 is not a kick */
+#define EAGLE_FLIGHT_LAYOUT_DEFAULT 0  /* how c(i, j) lies in HBM: the measured choice, or one of the two (tools/flights_rate.py, docs/experiments.md) */
+#define EAGLE_FLIGHT_LAYOUT_END_MAJOR 1
+#define EAGLE_FLIGHT_LAYOUT_K_MAJOR 2
+#define EAGLE_FLIGHT_TIMES 7           /* times_ms: prepare, cost, walk, path, fit, events, the whole call */
+typedef struct EagleFlightParams {     /* 96 bytes; eagle_flight_params_default fills the conventional choices (not fitted to data) */
+    double fps;                    /* > 0, finite */
+    int32_t max_gap;               /* 1 .. 1024 frames */
+    int32_t max_rows;              /* L: 2 .. 128 (64) */
+    double noise;                  /* metres, 0 .. 1024 (0.25) */
+    double penalty;                /* >= 0 (16); penalty (noise 1024)^2 <= 2^40 */
+    double spike;                  /* metres, 0 .. 1024 (1.0) */
+    double kick_dv;                /* m/s, >= 0 (3) */
+    double radius;                 /* metres, (0, 1024] (2) */
+    double still_speed;            /* m/s, >= 0 (0.5) */
+    double shot_speed;             /* m/s, >= 0 (10) */
+    double shot_range;             /* metres, >= 0 (40) */
+    double shot_margin;            /* metres, >= 0 (2) */
+    int32_t layout;                /* EAGLE_FLIGHT_LAYOUT_* */
+    int32_t reserved;              /* 0 */
+} EagleFlightParams;
+typedef struct EagleBallFlight {       /* 112 bytes */
+    int32_t row0, row1, used, spikes;
+    int32_t near, kind, shot, flags;
+    double x0, y0, x1, y1, vx, vy, speed, rms, y_cross;
+    int64_t c;
+} EagleBallFlight;
+typedef struct EagleBallKick {         /* 48 bytes */
+    int32_t row, seg_in, seg_out, col;
+    double speed_in, speed_out, dv, cos_turn;
+} EagleBallKick;
+typedef struct EagleFlightTotals {     /* 64 bytes */
+    int32_t runs;                  /* runs with a present row */
+    int32_t flights, kinds[3], spikes, knots, kicks;
+    int32_t shots[3];              /* evaluated flights per shot value */
+    int32_t capped;
+    int64_t sum_c, reserved;
+} EagleFlightTotals;
+int eagle_flight_params_default(EagleFlightParams* p, double fps, int32_t max_gap);
+/* EAGLE_E_INVALID with a message, before any launch and leaving every output alone, for NULL pointers, values outside the ranges above or not finite,
+ * more than one Ball pitch column, a column of unknown kind, more than 2^20 rows, cuts that do not ascend, another handle's table.  The result is kept
+ * with the table until eagle_post_free; a later call replaces it.  It reads whatever ball column the table has (raw, ball-tracked, smoothed); being a
+ * derived result, eagle_post_stabilise and eagle_post_smooth_tracks refuse a table that carries it. */
+int eagle_post_ball_flights(EagleHandle* h, EaglePostTable* t, const EagleFlightParams* p, const int32_t* cuts, int n_cuts);
+/* Any pointer may be NULL.  seg int32 [rows], flags uint8 [rows], fitted and velocity float64 [rows][2].  EAGLE_E_INVALID before the call. */
+int eagle_post_ball_flight_values(EaglePostTable* t, int32_t* seg, uint8_t* flags, double* fitted, double* velocity, EagleFlightTotals* totals);
+int eagle_post_ball_flight_records(const EaglePostTable* t, EagleBallFlight* flights, int cap, int* n);
+int eagle_post_ball_kicks(const EaglePostTable* t, EagleBallKick* kicks, int cap, int* n);
+int eagle_post_device_ball_flights(const EaglePostTable* t, const int32_t** d_seg, const uint8_t** d_flags, const double** d_fitted,
+                                   const double** d_velocity);                    /* NULLs before the call */
+/* The launches on a constructed table in host memory (frames must ascend strictly); every output may be NULL; *n_flights and *n_kicks are the numbers
+ * found, of which at most cap_flights / cap_kicks are written; times_ms: EAGLE_FLIGHT_TIMES milliseconds from device events, or NULL. */
+int eagle_op_ball_flights(int device, const double* values, const int32_t* frames, const EaglePostColumn* columns, int rows, int cols, const int32_t* cuts,
+                          int n_cuts, const EagleFlightParams* p, int32_t* seg, uint8_t* flags, double* fitted, double* velocity, EagleBallFlight* flights,
+                          int cap_flights, int* n_flights, EagleBallKick* kicks, int cap_kicks, int* n_kicks, EagleFlightTotals* totals, float* times_ms);
+
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
  * Keys: "lk_threads" (64 | 256), "lk_dbg" (1 trace, 2 LDS guard words, 4 end-of-level verification, 8 L1-bypassing loads), "lk_excl_lds" (bytes), "lk_trace", "lk_counters". */
