@@ -29,7 +29,10 @@ zone, the total distance, the top speed, the high-speed runs, sprints, accelerat
 second, optical flow in between); ``--every-frame`` selects the stateless configuration (both on every frame).  ``--ball-flights`` (with
 ``--processed``) writes ``ball_flights.json``: the ball's path cut into straight flights of constant speed, the kicks between them, the shots and, with
 ``--possession``, per pass its kick, kicker and speed (eagle_amd/flights.py; ``--ball-flights-rows``, ``-noise``, ``-penalty``, ``-spike``, ``-kick``,
-``-shot`` set the rule, ``--ball-flights-cells`` adds the per-row arrays)."""
+``-shot`` set the rule, ``--ball-flights-cells`` adds the per-row arrays).  ``--goal-view`` (with ``--processed``) writes ``goal_view.json``: how much of
+the goal mouth every attacker sees past the other team, per id the totals, with ``--ball-flights`` per shot the ball's view and whether its lane was open,
+with ``--possession`` per pass the threat it added (eagle_amd/goalview.py; ``--goal-view-direction``, ``--goal-view-cells``); ``--goal-view-map`` also writes
+``goal_view.npy``, the value of every cell of the pitch per kept frame (``--goal-view-grid``, ``--goal-view-team``)."""
 import argparse
 import json
 import os
@@ -250,6 +253,18 @@ def main(argv=None):
     ap.add_argument("--ball-flights-kick", type=float, default=None, metavar="V", help="with --ball-flights: the change of velocity of a kick in m/s (default 3)")
     ap.add_argument("--ball-flights-shot", type=float, default=None, metavar="V", help="with --ball-flights: the least speed of a shot in m/s (default 10)")
     ap.add_argument("--ball-flights-cells", action="store_true", help="with --ball-flights: also write the per-row arrays into ball_flights.json")
+    ap.add_argument("--goal-view", action="store_true",
+                    help="with --processed: write <out>/goal_view.json: the open angle of the goal mouth that every attacker sees past the other team's players (discs of "
+                         "0.4 m) and keeper (1.0 m) in every kept frame, per id the totals, with --ball-flights per shot the ball's view and whether its lane was open, with "
+                         "--possession per pass the angle gained (eagle_amd/goalview.py; the constants are conventional choices, not fitted to data)")
+    ap.add_argument("--goal-view-direction", choices=["offside", "right", "left"], default=None,
+                    help="with --goal-view: the way the team with value 0 attacks, towards x = 105 (right) or x = 0 (left); offside (the default) takes what --offside settled")
+    ap.add_argument("--goal-view-cells", action="store_true", help="with --goal-view: also write the per-frame records into goal_view.json")
+    ap.add_argument("--goal-view-map", action="store_true",
+                    help="with --goal-view: also write <out>/goal_view.npy, uint8 [kept frames][68 R][105 R]: the open angle from every cell of the pitch, 256 per radian")
+    ap.add_argument("--goal-view-grid", type=int, choices=[1, 2, 4], default=None, metavar="R", help="with --goal-view-map: cells per metre, 1, 2 or 4 (default 1)")
+    ap.add_argument("--goal-view-team", choices=["0", "1", "possession"], default=None,
+                    help="with --goal-view-map: the attacking team of the map; possession (the default with --possession): per frame the team that owns the ball")
     ap.add_argument("--shots", action="store_true",
                     help="also write <out>/shots.json: the camera cuts, gradual transitions and photo flashes of the clip, its shots and which of them look at "
                          "the pitch, and put the shot count into metadata.json (the thresholds are conventional choices, not fitted to footage)")
@@ -514,6 +529,19 @@ def main(argv=None):
             _flights.resolve(a.fps, **a.ball_flights_set)
         except ValueError as e:
             ap.error(str(e))
+    if a.goal_view and not a.processed:
+        ap.error("--goal-view works on the processed table: it needs --processed")
+    if (a.goal_view_direction or a.goal_view_cells or a.goal_view_map) and not a.goal_view:
+        ap.error("--goal-view-direction, --goal-view-cells and --goal-view-map set the goal view: they need --goal-view")
+    if (a.goal_view_grid is not None or a.goal_view_team is not None) and not a.goal_view_map:
+        ap.error("--goal-view-grid and --goal-view-team set the map: they need --goal-view-map")
+    if a.goal_view:
+        a.goal_view_direction = a.goal_view_direction or "offside"
+        if a.goal_view_direction == "offside" and not a.offside:
+            ap.error("--goal-view takes the attacking direction from the offside result: it needs --offside, or --goal-view-direction right / left")
+        a.goal_view_team = a.goal_view_team or ("possession" if a.possession else "0")
+        if a.goal_view_map and a.goal_view_team == "possession" and not a.possession:
+            ap.error("--goal-view-team possession needs --possession")
     if a.smooth_tracks and not a.processed:
         ap.error("--smooth-tracks works on the processed table: it needs --processed")
     if (a.smooth_set or a.smooth_rows) and not a.smooth_tracks:
@@ -700,6 +728,19 @@ def main(argv=None):
             from . import offside as ofs
             with open(os.path.join(a.out, "offside.json"), "w") as f:
                 json.dump(ofs.to_json(ofs.offside(model.handle, table, a.offside_set[0], a.offside_set[1], not a.offside_no_assumed_keeper, per_row=a.offside_rows)), f)
+        if a.goal_view:                                                    # after the offside, possession and flight results it joins; changes nothing in the table
+            from . import goalview as gv
+            try:
+                res = gv.goal_view(model.handle, table, grid=a.goal_view_map, direction={"offside": 0, "right": 1, "left": 2}[a.goal_view_direction],
+                                   group={"0": 0, "1": 1, "possession": -1}[a.goal_view_team], cells_per_metre=a.goal_view_grid or 1)
+                out = gv.to_json(res, flights=model.handle.ball_flight_values(table)["flights"] if a.ball_flights else None,
+                                 events=model.handle.events(table) if a.possession else None, cells=a.goal_view_cells)
+            except ValueError as e:                                        # the offside vote settled no direction, or the table has no team mapping
+                res, out = None, {"error": str(e)}
+            with open(os.path.join(a.out, "goal_view.json"), "w") as f:
+                json.dump(out, f)
+            if a.goal_view_map and res is not None:
+                np.save(os.path.join(a.out, "goal_view.npy"), res["grid"])
         if a.offside_view:
             from . import ground as gr
             pics, info = gr.offside_view(model, frames, coordinates, table, out_format="i420", **a.offside_view_set)
@@ -739,6 +780,8 @@ def main(argv=None):
             meta["positions"] = "smoothed"                                 # the table's pitch positions are the fits' (smooth.json)
         if a.ball_flights:
             meta["ball_flights"] = True                                    # ball_flights.json
+        if a.goal_view:
+            meta["goal_view"] = True                                       # goal_view.json
         if a.ball_track:
             meta["ball"] = "ball_track"                                    # the table's ball is the tracked one (ball_track.json)
         if team_report is not None:

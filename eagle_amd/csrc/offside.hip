@@ -257,10 +257,8 @@ static int offside_check(const char* who, const EagleOffsideParams* p)
     return (int)floor(p->tolerance * 1024.0 + 0.5);
 }
 
-struct OfCols { std::vector<int4> list; std::vector<int32_t> gcols, member_of; std::vector<EagleOffsideTotals> init; EagleOffsideClip clip{}; int n0 = 0, n1 = 0, ball = -1; };
-
-// groups 0 and 1 are the team shape's (and its refusals); the keepers: the Goalkeeper pitch columns; the ball: the one Ball pitch column
-static OfCols offside_columns(const char* who, const EaglePostColumn* columns, int ncols, bool no_ball, const int32_t* team_ids, const int32_t* team_vals, size_t n_team,
+// (OfCols: runtime.h)  groups 0 and 1 are the team shape's (and its refusals); the keepers: the Goalkeeper pitch columns; the ball: the one Ball pitch column
+OfCols offside_columns(const char* who, const EaglePostColumn* columns, int ncols, bool no_ball, const int32_t* team_ids, const int32_t* team_vals, size_t n_team,
                               const EagleOffsideParams* p)
 {
     const ShapeCols sc = shape_columns(who, columns, ncols, team_ids, team_vals, n_team);

@@ -659,6 +659,7 @@ void eagle_post_free(EaglePostTable* t)
     if (t->d_raw) (void)hipFree(t->d_raw);
     if (t->d_smooth) (void)hipFree(t->d_smooth);
     if (t->d_flights) (void)hipFree(t->d_flights);
+    if (t->d_goalview) (void)hipFree(t->d_goalview);
     if (t->d_orig) (void)hipFree(t->d_orig);
     if (t->d_stab) (void)hipFree(t->d_stab);
     if (t->d_poss) (void)hipFree(t->d_poss);

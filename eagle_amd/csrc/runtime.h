@@ -328,6 +328,9 @@ struct EaglePostTable {
     std::vector<EagleBallFlight> flights;
     std::vector<EagleBallKick> kicks;
     EagleFlightTotals flight_totals{};
+    void* d_goalview = nullptr;          // goal view (eagle_post_goal_view): EagleGoalViewRow [rows][2] | open i32 | mask u64 | status u8 [goalview_members][rows] |
+    int goalview_members = 0;            // EagleGoalViewTotals [goalview_members] | grid u8 [goalview_grid_rows][68 R][105 R], each from a 256-byte boundary;
+    int goalview_grid_row0 = 0, goalview_grid_rows = 0, goalview_R = 0;   // nullptr before the first call, resident until eagle_post_free
 };
 
 namespace eagle {
@@ -394,6 +397,10 @@ void hull_check(const char* who, const EagleHullParams* p);
 // the two launches on stream s (h: timed under its profiling mode, or nullptr); returns when the records and vertices are complete
 void shape_run(EagleHandle* h, const ShapeCols& sc, const double2* d_values, int rows, EagleTeamShape* d_shapes, int32_t* d_hull, hipStream_t s);
 // rows row0 .. row0 + n - 1 -> edges [n][2][EAGLE_SHAPE_HULL_CAP] = {A, B} in the minimap's quantisation (x == MM_ABSENT: no edge); no synchronisation
+// offside.hip (K33): the members of groups 0 and 1, the keepers and the ball of a table; goalview.hip (K41) takes its groups from here too
+struct OfCols { std::vector<int4> list; std::vector<int32_t> gcols, member_of; std::vector<EagleOffsideTotals> init; EagleOffsideClip clip{}; int n0 = 0, n1 = 0, ball = -1; };
+OfCols offside_columns(const char* who, const EaglePostColumn* columns, int ncols, bool no_ball, const int32_t* team_ids, const int32_t* team_vals, size_t n_team,
+                       const EagleOffsideParams* p);
 void shape_edges_launch(const double2* values, int rows, const EagleTeamShape* shapes, const int32_t* hull, int row0, int n, int scale, int margin, int4* edges, hipStream_t s);
 }  // namespace eagle
 

@@ -402,7 +402,7 @@ int eagle_post_smooth_tracks(EagleHandle* h, EaglePostTable* t, const EagleSmoot
     if (t->has_smooth) fail(EAGLE_E_INVALID, "eagle_post_smooth_tracks: the table has been smoothed already (a second call is refused)");
     const char* derived = t->d_vel ? "velocities" : t->has_poss ? "a possession result" : t->has_occ ? "occupancy maps" : t->has_shape ? "team shapes" :
                           t->has_phys ? "a physical report" : t->has_roles ? "roles" : t->d_space ? "a space result" : t->d_offside ? "an offside result" :
-                          t->has_control ? "control parameters" : t->has_flights ? "ball flights" : nullptr;
+                          t->has_control ? "control parameters" : t->has_flights ? "ball flights" : t->d_goalview ? "a goal view" : nullptr;
     if (derived) fail(EAGLE_E_INVALID, "eagle_post_smooth_tracks: the table already carries %s derived from its positions; smoothing comes first", derived);
     std::vector<int32_t> colw;
     std::vector<uint8_t> person;

@@ -296,7 +296,7 @@ int eagle_post_stabilise(EagleHandle* h, EaglePostTable* t, const EagleStabParam
     if (t->has_stab) fail(EAGLE_E_INVALID, "eagle_post_stabilise: the table has been stabilised already (a second call is refused)");
     const char* derived = t->has_smooth ? "smoothed positions" : t->d_vel ? "velocities" : t->has_poss ? "a possession result" : t->has_occ ? "occupancy maps" :
                           t->has_shape ? "team shapes" : t->has_phys ? "a physical report" : t->has_roles ? "roles" : t->d_space ? "a space result" :
-                          t->d_offside ? "an offside result" : t->has_control ? "control parameters" : t->has_flights ? "ball flights" : nullptr;
+                          t->d_offside ? "an offside result" : t->has_control ? "control parameters" : t->has_flights ? "ball flights" : t->d_goalview ? "a goal view" : nullptr;
     if (derived) fail(EAGLE_E_INVALID, "eagle_post_stabilise: the table already carries %s derived from its positions; stabilising comes first", derived);
     std::vector<uint8_t> kind;
     stab_columns("eagle_post_stabilise", t->columns.data(), t->cols, kind);

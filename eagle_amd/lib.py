@@ -317,6 +317,29 @@ FLIGHT_TOTALS_DTYPE = np.dtype([("runs", "<i4"), ("flights", "<i4"), ("kinds", "
 assert C.sizeof(EagleFlightParams) == 96 and FLIGHT_DTYPE.itemsize == 112 and KICK_DTYPE.itemsize == 48 and FLIGHT_TOTALS_DTYPE.itemsize == 64
 
 
+class EagleGoalViewParams(C.Structure):
+    """include/eagle.h EagleGoalViewParams: the direction group 0 attacks (OFFSIDE_DIR_RIGHT / _LEFT; 0: the table's offside result's), the grid's attacking
+    group (0, 1, -1: the owner's), its cells per metre (1, 2, 4), the form of the grid kernel's weights (GOALVIEW_FORM_*), the grid's table rows (grid_rows 0:
+    no grid), the radii of an outfield player and a keeper (m), the least depth and the largest range of an evaluated point (m), the angle of a chance (rad)."""
+    _fields_ = [("direction", C.c_int32), ("group", C.c_int32), ("cells_per_metre", C.c_int32), ("form", C.c_int32), ("grid_row0", C.c_int32), ("grid_rows", C.c_int32),
+                ("radius", C.c_double), ("keeper_radius", C.c_double), ("min_depth", C.c_double), ("max_range", C.c_double), ("chance", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
+GOALVIEW_BLOCKERS, GOALVIEW_SLICES = 32, 64
+GOALVIEW_OK, GOALVIEW_TOO_MANY = 0, 1                                                                            # EagleGoalViewRow.status
+GOALVIEW_PT_OK, GOALVIEW_PT_ABSENT, GOALVIEW_PT_ROW, GOALVIEW_PT_NEAR_LINE, GOALVIEW_PT_FAR = 0, 1, 2, 3, 4      # a point's status
+GOALVIEW_PT_NAMES = ("ok", "absent", "too_many", "near_line", "far")
+GOALVIEW_FORM_DEFAULT, GOALVIEW_FORM_DIRECT, GOALVIEW_FORM_TABLE = 0, 1, 2
+GOALVIEW_TIMES = ("prepare", "points", "rows", "table", "grid", "total")                                         # times_ms of eagle_op_goal_view
+GOALVIEW_ROW_DTYPE = np.dtype([("status", "<i4"), ("n_blockers", "<i4"), ("ball_status", "<i4"), ("ball_open", "<i4"), ("ball_full", "<i4"), ("best_col", "<i4"),
+                               ("best_open", "<i4"), ("owner_col", "<i4"), ("owner_open", "<i4"), ("reserved", "<i4"), ("ball_mask", "<u8"),
+                               ("owner_mask", "<u8")])                                                            # EagleGoalViewRow (56 bytes)
+GOALVIEW_TOTALS_DTYPE = np.dtype([("col", "<i4"), ("group", "<i4"), ("rows", "<i4"), ("max_open", "<i4"), ("max_row", "<i4"), ("chance_rows", "<i4"),
+                                  ("sum_open", "<i8")])                                                           # EagleGoalViewTotals (32 bytes)
+assert C.sizeof(EagleGoalViewParams) == 72 and GOALVIEW_ROW_DTYPE.itemsize == 56 and GOALVIEW_TOTALS_DTYPE.itemsize == 32
+
+
 class EagleStabParams(C.Structure):
     """include/eagle.h EagleStabParams: frames per second, the half-width in frames, the degree (1, 2), the model (0 translation, 1 affine), the fewest
     voters of a row, the rounds, the trimming multiple (0: none), its floor (m), the least spread
@@ -630,6 +653,12 @@ def load():
     L.eagle_post_ball_kicks.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
     L.eagle_post_device_ball_flights.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.eagle_op_ball_flights.argtypes = [i32, vp, vp, vp, i32, i32, vp, i32, flp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int), vp, i32, C.POINTER(C.c_int), vp, vp]
+    gvp = C.POINTER(EagleGoalViewParams)
+    L.eagle_goal_view_params_default.argtypes = [gvp]
+    L.eagle_post_goal_view.argtypes = [vp, vp, gvp]
+    L.eagle_post_goal_view_values.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.eagle_post_device_goal_view.argtypes = [vp] + [C.POINTER(vp)] * 6 + [C.POINTER(C.c_int)] * 4
+    L.eagle_op_goal_view.argtypes = [i32, vp, vp, i32, i32, vp, vp, i32, vp, gvp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
     _lib = L
     return L
 
@@ -665,7 +694,8 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_post_raw_values", "eagle_op_smooth_tracks", "eagle_post_stabilise", "eagle_post_stabilise_values", "eagle_post_original_values",
            "eagle_post_device_stabilise", "eagle_op_stabilise", "eagle_linefit_params_default", "eagle_linefit_device_frames", "eagle_linefit_frames",
            "eagle_op_linefit", "eagle_flight_params_default", "eagle_post_ball_flights", "eagle_post_ball_flight_values", "eagle_post_ball_flight_records",
-           "eagle_post_ball_kicks", "eagle_post_device_ball_flights", "eagle_op_ball_flights"]
+           "eagle_post_ball_kicks", "eagle_post_device_ball_flights", "eagle_op_ball_flights", "eagle_goal_view_params_default", "eagle_post_goal_view",
+           "eagle_post_goal_view_values", "eagle_post_device_goal_view", "eagle_op_goal_view"]
 
 FLOWKP_DTYPE = np.dtype([("label", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4")], align=True)
 ECC_DTYPE = np.dtype([("ok", "<i4"), ("iters", "<i4"), ("rho", "<f8"), ("M", "<f4", (6,))], align=True)      # EagleEccResult
@@ -1348,6 +1378,35 @@ class Handle:
         out["kicks"] = np.zeros(n.value, KICK_DTYPE)
         self._check(self.L.eagle_post_ball_kicks(table._t, _ptr(out["kicks"], keep), n.value, C.byref(n)), "post_ball_kicks")
         return out
+
+    # --- goal view (include/eagle.h, eagle_post_goal_view) ------------------------------------------------------------------
+    def goal_view(self, table, params):
+        """How much of the goal mouth every member, the ball and (with params.grid_rows) every cell sees on a PostTable of this handle that has a team
+        mapping; kept with the table (a later call replaces it) -> goal_view_values(table)."""
+        self._check(self.L.eagle_post_goal_view(self._h, table._t, C.byref(params)), "post_goal_view")
+        return self.goal_view_values(table)
+
+    def goal_view_values(self, table):
+        """What goal_view kept with the table -> {"rows": GOALVIEW_ROW_DTYPE [rows, 2], "open": int32, "mask": uint64, "status": uint8 [members, rows],
+        "totals": GOALVIEW_TOTALS_DTYPE [members], "grid": uint8 [grid_rows, 68 R, 105 R], "grid_row0": int}; an EagleError before the call."""
+        d = self.goal_view_device(table)
+        if d[0] is None:
+            self._check(self.L.eagle_post_goal_view_values(table._t, None, None, None, None, None, None), "post_goal_view_values")
+        nm, row0, gr, R = d[6:]
+        rows = len(table.rows)
+        out = {"rows": np.zeros((rows, 2), GOALVIEW_ROW_DTYPE), "open": np.zeros((nm, rows), np.int32), "mask": np.zeros((nm, rows), np.uint64),
+               "status": np.zeros((nm, rows), np.uint8), "totals": np.zeros(nm, GOALVIEW_TOTALS_DTYPE), "grid": np.zeros((gr, 68 * R, 105 * R), np.uint8)}
+        keep = np.zeros(8, np.float64)
+        self._check(self.L.eagle_post_goal_view_values(table._t, *(_ptr(out[k], keep) for k in ("rows", "open", "mask", "status", "totals", "grid"))), "post_goal_view_values")
+        out["grid_row0"] = row0
+        return out
+
+    def goal_view_device(self, table):
+        """(records, open, mask, status, totals, grid in HBM, members, grid_row0, grid_rows, cells per metre); (None,) * 6 + (0,) * 4 before goal_view."""
+        d = [C.c_void_p() for _ in range(6)]
+        n = [C.c_int(0) for _ in range(4)]
+        self._check(self.L.eagle_post_device_goal_view(table._t, *[C.byref(x) for x in d], *[C.byref(x) for x in n]), "post_device_goal_view")
+        return tuple(x.value for x in d) + tuple(x.value for x in n)
 
     def ball_flights_device(self, table):
         """(seg int32 [rows], flags uint8 [rows], fitted, velocity float64 [rows][2]) in HBM (None each before ball_flights)."""
@@ -2882,6 +2941,52 @@ def op_offside(values, columns, team_mapping, params=None, events=None, frames=N
     if rc:
         raise EagleError(f"eagle_op_offside failed ({rc}): {L.eagle_last_error(None).decode()}")
     return rec, mg, totals, clip, ev
+
+
+def goal_view_params(direction=OFFSIDE_DIR_AUTO, group=0, cells_per_metre=1, form=GOALVIEW_FORM_DEFAULT, grid_row0=0, grid_rows=0, radius=0.4, keeper_radius=1.0,
+                     min_depth=1.0, max_range=40.0, chance=0.3):
+    """EagleGoalViewParams.  The radii, the range and the angle of a chance are conventional choices, not fitted to data."""
+    return EagleGoalViewParams(int(direction), int(group), int(cells_per_metre), int(form), int(grid_row0), int(grid_rows), float(radius), float(keeper_radius),
+                               float(min_depth), float(max_range), float(chance))
+
+
+def op_goal_view(values, columns, team_mapping, params, owner=None, times=False, device=0, fetch_grid=True):
+    """The goal-view launches on a constructed table (include/eagle.h eagle_op_goal_view): values float64 [cols][rows][2], columns [(kind, id, video)],
+    team_mapping as op_offside's, owner int32 [rows] (a column or -1) or None -> {"rows": GOALVIEW_ROW_DTYPE [rows, 2], "open": int32, "mask": uint64,
+    "status": uint8 [members, rows], "totals": GOALVIEW_TOTALS_DTYPE [members], "grid": uint8 [grid_rows, 68 R, 105 R]} and, with times, "times": a dict of
+    milliseconds per GOALVIEW_TIMES name.  fetch_grid=False leaves the grid on the device ("grid" is None): a measurement does not need the copy."""
+    L = load()
+    values, columns = _table_args("op_goal_view", values, columns)
+    cols, rows = values.shape[:2]
+    pairs = None if team_mapping is None else list(team_mapping.items() if isinstance(team_mapping, dict) else team_mapping)
+    ids = None if pairs is None else np.ascontiguousarray([int(k) for k, _ in pairs], np.int32)
+    vals = None if pairs is None else np.ascontiguousarray([int(v) for _, v in pairs], np.int32)
+    owner = None if owner is None else np.ascontiguousarray(owner, np.int32)
+    if owner is not None and owner.shape != (rows,):
+        raise EagleError("op_goal_view: one owner per row")
+    keep = np.zeros(16, np.float64)
+    nm = C.c_int(0)
+    args = (device, _ptr(values, keep), _ptr(columns, keep), rows, cols, _ptr(ids, keep), _ptr(vals, keep), 0 if pairs is None else len(pairs),
+            None if owner is None else _ptr(owner, keep), C.byref(params))
+    first = {}
+    for i, v in pairs or ():
+        first.setdefault(int(i), int(v))
+    n = sum(1 for k in columns if not k["video"] and int(k["kind"]) == POST_PLAYER and first.get(int(k["id"]), -1) >= 0)       # the members, as op_offside counts them
+    R = params.cells_per_metre if params.cells_per_metre in (1, 2, 4) else 1
+    out = {"rows": np.zeros((rows, 2), GOALVIEW_ROW_DTYPE), "open": np.zeros((n, rows), np.int32), "mask": np.zeros((n, rows), np.uint64),
+           "status": np.zeros((n, rows), np.uint8), "totals": np.zeros(n, GOALVIEW_TOTALS_DTYPE),
+           "grid": np.zeros((max(int(params.grid_rows), 0) if rows and fetch_grid else 0, 68 * R, 105 * R), np.uint8)}
+    tm = np.zeros(len(GOALVIEW_TIMES), np.float32)
+    if not fetch_grid:
+        out["grid"] = None
+    rc = L.eagle_op_goal_view(*args, *(_ptr(out[k], keep) for k in ("rows", "open", "mask", "status", "totals", "grid")), C.byref(nm), _ptr(tm, keep) if times else None)
+    if rc:
+        raise EagleError(f"eagle_op_goal_view failed ({rc}): {L.eagle_last_error(None).decode()}")
+    if nm.value != n:
+        raise EagleError(f"op_goal_view: the library counts {nm.value} members, the caller {n}")
+    if times:
+        out["times"] = dict(zip(GOALVIEW_TIMES, map(float, tm)))
+    return out
 
 
 def ball_track_params(fps, frame_w, speed=0.0, gap=0, reward=0.0, brk=0.0, max_bytes=0):

@@ -150,6 +150,12 @@ class Processor:
         from . import flights as fl
         return fl.ball_flights(self.model.handle, table, fps, cuts, **params)
 
+    def goal_view(self, table, grid=False, **params):
+        """How much of the goal mouth every attacker, the ball and (grid=True) every cell of the pitch sees past the other team on a processed table
+        (direction, group, cells_per_metre, radius, keeper_radius, min_depth, max_range, chance).  Nothing in the table changes: see eagle_amd/goalview.py."""
+        from . import goalview as gv
+        return gv.goal_view(self.model.handle, table, grid, **params)
+
     def kinematics(self, table, fps, max_gap=None, speed_cap=12.0, keep=False):
         """Velocities of a processed table (computed on the GPU, kept with the table; keep=True: the ones it carries, as after smooth_tracks) plus per
         id distance covered and top speed: see eagle_amd/control.py."""

@@ -1970,6 +1970,99 @@ int eagle_op_ball_flights(int device, const double* values, const int32_t* frame
                           int n_cuts, const EagleFlightParams* p, int32_t* seg, uint8_t* flags, double* fitted, double* velocity, EagleBallFlight* flights,
                           int cap_flights, int* n_flights, EagleBallKick* kicks, int cap_kicks, int* n_kicks, EagleFlightTotals* totals, float* times_ms);
 
+/* ---- goal view: how much of the goal mouth every attacker, the ball and every cell of the pitch sees past the other team (K41; own specification:
+ * tests/goalview_ref.py defines every output bit) ----
+ * Opt-in, after the table is built; nothing in the table changes.  ARITHMETIC: float64, one operation at a time and in the order written here, no
+ * contraction, correctly rounded division and sqrt; only + - * / sqrt, comparisons, floor/rint.  Sums are integers.
+ *   POSITIONS  K33's: groups 0 and 1 (the Player pitch columns with a mapping entry), the keepers (the Goalkeeper pitch columns), the ball (the one Ball
+ *              pitch column), present when x and y are finite and |x|, |y| <= 1024 m, q = floor(v * 1024 + 0.5); a position in metres is q / 1024, exact.
+ *   GOALS      the lines x_g = 0 and x_g = 105; the mouth y = 30.34 .. 37.66 cut into 64 slices of DY = 7.32 / 64, slice k with centre
+ *              yc_k = 30.34 + (k + 0.5) * DY.  direction: EAGLE_OFFSIDE_DIR_RIGHT (group 0 attacks x_g = 105, group 1 x_g = 0) or _LEFT; 0: the direction
+ *              the table's offside result settled (refused without one, or when it settled none, and by the operator entry).
+ *   BLOCKERS   of the attacking group g on a row: the present members of 1 - g with rho = radius and, with rho = keeper_radius, every present keeper that
+ *              K33 counts among g's defenders (depth u > U_HALF); in table order.  More than EAGLE_GOALVIEW_BLOCKERS: the row's record of g has status
+ *              TOO_MANY and nothing of g is evaluated on it.  n_blockers counts them all.
+ *   POINT      P with s = x_g - P.x: absent -> ABSENT; a TOO_MANY row -> ROW; |s| < min_depth -> NEAR_LINE; ex = x_g - P.x, ey = 34 - P.y,
+ *              ex ex + ey ey > max_range max_range -> FAR (open 0, mask 0); else OK.  Every other status: open -1, mask 0.
+ *   SHADOW     a blocker D counts when its centre lies between the point and the line: wx = D.x - P.x, gx = x_g - D.x; s > 0: wx > 0 and gx >= 0;
+ *              s < 0: wx < 0 and gx <= 0.  wy = D.y - P.y, d2 = wx wx + wy wy, r2 = rho rho.  d2 <= r2: all 64 slices.  Else l = sqrt(d2 - r2), the
+ *              tangents t+ = (l wx - rho wy, l wy + rho wx), t- = (l wx + rho wy, l wy - rho wx); a tangent t reaches the line at
+ *              y = P.y + (t.y s) / t.x when t.x has the sign of s, else at copysign(inf, t.y); lo and hi the smaller and the larger of the two; slice k
+ *              is blocked iff lo <= yc_k <= hi.  mask: bit k set = slice k blocked by any blocker.
+ *   ANGLE      w_k = rint(2^24 ((DY |s|) / (s s + (yc_k - P.y)^2))), int32 in units of 2^-24 rad (the midpoint rule of d theta / dy);
+ *              full = sum of all w_k, open = sum over the slices not blocked.  |s| >= min_depth >= 1 keeps full below 2^27.
+ *   RECORDS    [rows][2], the attacking group second: status (OK, TOO_MANY), n_blockers; the ball as a point (ball_status, ball_mask, ball_open,
+ *              ball_full; full is 0 unless OK); best_col / best_open: the OK member of g with the largest open, of equal ones the smaller column (-1, -1
+ *              without one); with an owner array whose entry of the row is a member of g: owner_col, owner_mask, owner_open (that member's), else -1, 0, -1.
+ *   MEMBERS    in group order (0, then 1; by column inside): open int32, mask uint64, status uint8, [members][rows] each.
+ *   TOTALS     per member over its OK rows: rows, sum_open, max_open and the earliest row attaining it (-1, -1 without a row), chance_rows =
+ *              #{open >= rint(2^24 chance)}.
+ *   GRID       optional (grid_rows > 0): uint8 [grid_rows][68 R][105 R] for table rows grid_row0 .., R = cells_per_metre; row 0 is y = 0, cell (j, i)'s
+ *              point is ((i + 0.5) / R, (j + 0.5) / R); group 0 or 1, or -1: the group of which the row's owner is a member (no such group: zeros).  The
+ *              byte is min(255, open >> 16) of an OK cell and 0 otherwise: one radian is 256.
+ * Players are discs at their foot point; height, the ball's loft, shot speed and a keeper's dive are not modelled; the radii and every constant are
+ * conventional choices, not fitted to data.  form chooses how the grid kernel gets a cell's weights: 64 divisions on the fly, or a prefix table
+ * int32 [2][68 R][105 R][65] built once per call; the results are equal integers (docs/experiments.md, "Goal view (K41)").
+ * EAGLE_E_INVALID with a message, before any launch and leaving every output and an earlier result alone: NULL pointers, values that are not finite,
+ * radii outside [0, 16], min_depth < 1, max_range <= min_depth or > 1024, chance outside [0, 4], cells_per_metre outside {1, 2, 4}, an unknown
+ * direction, group or form, direction 0 without a settled offside result, group -1 (with a grid) without a possession result / owner array, a table
+ * without a mapping, grid rows outside the table, non-zero reserved words, a device-memory need beyond the budget. */
+#define EAGLE_GOALVIEW_BLOCKERS 32
+#define EAGLE_GOALVIEW_SLICES 64
+#define EAGLE_GOALVIEW_OK 0        /* EagleGoalViewRow::status */
+#define EAGLE_GOALVIEW_TOO_MANY 1
+#define EAGLE_GOALVIEW_PT_OK 0     /* a point's status */
+#define EAGLE_GOALVIEW_PT_ABSENT 1
+#define EAGLE_GOALVIEW_PT_ROW 2    /* the row is TOO_MANY */
+#define EAGLE_GOALVIEW_PT_NEAR_LINE 3
+#define EAGLE_GOALVIEW_PT_FAR 4
+#define EAGLE_GOALVIEW_FORM_DEFAULT 0
+#define EAGLE_GOALVIEW_FORM_DIRECT 1
+#define EAGLE_GOALVIEW_FORM_TABLE 2
+#define EAGLE_GOALVIEW_TIMES 6     /* times_ms of eagle_op_goal_view: prepare, points, rows + totals, table, grid, total */
+typedef struct EagleGoalViewParams {
+    int32_t direction;             /* EAGLE_OFFSIDE_DIR_RIGHT, _LEFT; 0: the offside result's */
+    int32_t group;                 /* the grid's attacking group: 0, 1, -1 (the owner's) */
+    int32_t cells_per_metre;       /* 1, 2, 4 */
+    int32_t form;                  /* EAGLE_GOALVIEW_FORM_* */
+    int32_t grid_row0, grid_rows;  /* the grid's table rows; grid_rows == 0: no grid */
+    double radius, keeper_radius;  /* metres, [0, 16] (0.4, 1.0) */
+    double min_depth, max_range;   /* metres (1.0, 40.0) */
+    double chance;                 /* radians (0.3) */
+    int32_t reserved[2];           /* 0 */
+} EagleGoalViewParams;             /* 72 bytes */
+typedef struct EagleGoalViewRow {
+    int32_t status, n_blockers;
+    int32_t ball_status, ball_open, ball_full;
+    int32_t best_col, best_open;
+    int32_t owner_col, owner_open;
+    int32_t reserved;              /* 0 */
+    uint64_t ball_mask, owner_mask;
+} EagleGoalViewRow;                /* 56 bytes */
+typedef struct EagleGoalViewTotals {
+    int32_t col, group;
+    int32_t rows, max_open, max_row, chance_rows;
+    int64_t sum_open;
+} EagleGoalViewTotals;             /* 32 bytes */
+int eagle_goal_view_params_default(EagleGoalViewParams* p);
+/* The result is kept with the table until eagle_post_free; a call computes into a buffer of its own and replaces the earlier result when it is complete.
+ * The owner array is the table's possession result at the time of the call (none: no owner anywhere).  Being a derived result, eagle_post_stabilise
+ * and eagle_post_smooth_tracks refuse a table that carries it. */
+int eagle_post_goal_view(EagleHandle* h, EaglePostTable* t, const EagleGoalViewParams* p);
+/* To the host; any pointer may be NULL: rows_out [rows][2], open int32, mask uint64, status uint8 [members][rows], totals [members], grid uint8
+ * [grid_rows][68 R][105 R].  EAGLE_E_INVALID before the call. */
+int eagle_post_goal_view_values(EaglePostTable* t, EagleGoalViewRow* rows_out, int32_t* open, uint64_t* mask, uint8_t* status, EagleGoalViewTotals* totals,
+                                uint8_t* grid);
+/* In HBM; NULLs and zeros before the call (d_grid NULL without a grid).  The last four may be NULL. */
+int eagle_post_device_goal_view(const EaglePostTable* t, const EagleGoalViewRow** d_rows, const int32_t** d_open, const uint64_t** d_mask, const uint8_t** d_status,
+                                const EagleGoalViewTotals** d_totals, const uint8_t** d_grid, int* n_members, int* grid_row0, int* grid_rows, int* cells_per_metre);
+/* Operator entry (host buffers in / out, no handle) for constructed tables, as eagle_op_offside; owner int32 [rows] (a column or -1) or NULL; every
+ * output may be NULL; *n_members (may be NULL) is the number of members, written before anything else so that a caller can size its buffers with a
+ * first call that passes no output; times_ms: EAGLE_GOALVIEW_TIMES milliseconds from device events, or NULL. */
+int eagle_op_goal_view(int device, const double* values, const EaglePostColumn* columns, int rows, int cols, const int32_t* team_ids, const int32_t* team_vals,
+                       int n_team, const int32_t* owner, const EagleGoalViewParams* p, EagleGoalViewRow* rows_out, int32_t* open, uint64_t* mask, uint8_t* status,
+                       EagleGoalViewTotals* totals, uint8_t* grid, int* n_members, float* times_ms);
+
 /* Developer diagnostics (process-wide switches and read-backs used by tools/probe_lk_concurrency.py; not part of the data path).
  * Inert (EAGLE_E_STATE) unless the process environment has EAGLE_ENABLE_DEBUG=1: a production caller cannot flip them by accident.
  * Keys: "lk_threads" (64 | 256), "lk_dbg" (1 trace, 2 LDS guard words, 4 end-of-level verification, 8 L1-bypassing loads), "lk_excl_lds" (bytes), "lk_trace", "lk_counters". */
