@@ -87,6 +87,8 @@ inline int prec_tensor_fmt(int precision) { return precision == EAGLE_PREC_F32 ?
 inline bool prec_is_f16_kernels(int precision) { return precision == EAGLE_PREC_F16 || precision == EAGLE_PREC_F32S; }
 // plain_epilogue: pre_act none, post_act none/ReLU, at most one residual, fp16 output (what the weight-stationary kernel implements)
 ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_pad, int wo, bool plain_epilogue = false, bool second_residual = false);
+// rows of table `which` (EAGLE_CONV_TABLE_*, include/eagle.h) into rows[cap]; returns the table's row count (test surface, host only)
+int conv_table(int which, int32_t* rows, int cap);
 
 // ---- fused Bottleneck (bneck.hip; EAGLE_PREC_F32S): conv1 1x1 Cin->64 + ReLU, conv2 3x3 64->64 + ReLU, conv3 1x1 64->256 + residual + ReLU in one launch ----
 struct BneckLaunch {

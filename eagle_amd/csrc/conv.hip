@@ -307,6 +307,38 @@ ConvConfig conv_choose(int precision, int ks, int stride, int cin_pad, int cout_
     return choose_f16(c, wo, plain_epilogue, plain_epilogue && !second_residual);
 }
 
+// The tables the choice above is made from, for the tests (eagle_op_conv_table; host only).  Rows beyond `cap` ints are counted, not written.
+int conv_table(int which, int32_t* rows, int cap)
+{
+    int n = 0, used = 0;
+    auto put = [&](std::initializer_list<int> r) {
+        if (rows && used + (int)r.size() <= cap)
+            for (int v : r) rows[used++] = v;
+        ++n;
+    };
+    if (which == EAGLE_CONV_TABLE_INSTANCES) {
+        for (auto part : {conv_inst_part0, conv_inst_part1, conv_inst_part2, conv_inst_part3, conv_inst_split0, conv_inst_split1, conv_inst_split2}) {
+            int k = 0;
+            const Inst* t = part(&k);
+            for (int i = 0; i < k; ++i) put({t[i].prec, t[i].ks, t[i].s, t[i].kc, t[i].nt, t[i].variant});
+        }
+        return n;
+    }
+    if (which == EAGLE_CONV_TABLE_ADIRECT) {
+        for (const Form& f : g_forms)
+            if (f.kind == ADIRECT) {
+                ConvConfig c;
+                c.ks = 3; c.stride = (f.sform == S1 || f.sform == S1L) ? 1 : 2; c.kc = f.kc; c.nt = f.nt; c.variant = f.variant;
+                put({f.prec, f.variant, c.stride, f.kc, f.nt, f.rows, f.cols, (int)lds_bytes(f.prec, c)});
+            }
+        return n;
+    }
+    const Tuned* t = which == EAGLE_CONV_TABLE_TUNED_F16 ? g_tuned : which == EAGLE_CONV_TABLE_TUNED_F32 ? g_tuned_f32 : which == EAGLE_CONV_TABLE_TUNED_SPLIT ? g_tuned_split : nullptr;
+    if (!t) fail(EAGLE_E_INVALID, "conv_table: no table %d", which);
+    for (; t->ks; ++t) put({t->ks, t->s, t->cin, t->cout, t->wo, t->kc, t->nt, t->wx, t->variant});      // (the terminator row is all zeros)
+    return n;
+}
+
 size_t conv_weight_elems(int precision, const ConvConfig& c)
 {
     const int bn = c.nt * 16, nblk = c.cout_pad / bn, nch = c.cin / c.kc;

@@ -50,6 +50,37 @@ static void from_dev(const TView& v, int c, float* dst)
     }
 }
 
+// The channel padding of eagle_op_conv2d and conv_choose's pick for the padded layer: shared with eagle_op_conv_config, which reports what the former runs.
+static ConvConfig op_conv_choose(int precision, int ks, int stride, int cin, int cout, int wo, bool plain_epilogue, bool second_residual, int* cin_pad, int* cout_pad)
+{
+    const int g = precision == EAGLE_PREC_F32 ? 4 : 8;
+    *cin_pad = cin <= g ? g : (cin + 15) / 16 * 16; *cout_pad = (cout + 15) / 16 * 16;
+    return conv_choose(precision, ks, stride, *cin_pad, *cout_pad, wo, plain_epilogue, second_residual);
+}
+
+int eagle_op_conv_config(int precision, int ks, int stride, int cin, int cout, int wo, int plain_epilogue, int second_residual, int32_t out[8])
+{
+    EagleHandle* hh = nullptr;
+    API_BEGIN
+    if (precision < EAGLE_PREC_F16 || precision > EAGLE_PREC_F32S || (ks != 1 && ks != 3) || stride < 1 || cin < 1 || cout < 1 || wo < 1 || !out)
+        fail(EAGLE_E_INVALID, "eagle_op_conv_config: bad argument (ks 1 or 3)");
+    int cin_pad, cout_pad;
+    const ConvConfig c = op_conv_choose(precision, ks, stride, cin, cout, wo, plain_epilogue != 0, second_residual != 0, &cin_pad, &cout_pad);
+    int th = 0, tw = 0;
+    size_t lds = 0;
+    const bool inst = conv_supported(precision, c);
+    if (inst) { conv_tile_shape(precision, c, &th, &tw); lds = conv_lds_bytes(precision, c); }
+    const int r[8] = {c.kc, c.nt, c.wx, c.variant, th, tw, (int)lds, inst && lds <= 160 * 1024 ? 1 : 0};
+    for (int k = 0; k < 8; ++k) out[k] = r[k];
+    API_END(hh)
+}
+
+int eagle_op_conv_table(int which, int32_t* rows, int cap)
+{
+    try { return conv_table(which, rows, rows ? cap : 0); }
+    catch (const eagle::Err& e) { eagle::g_create_error = e.msg; return e.code; }
+}
+
 int eagle_op_conv2d(int device, int precision, const float* x, int n, int h, int w, int cin, const float* w_hwio,
                     const float* bias, int cout, int ks, int stride, int pre_act, const float* r1, const float* r2,
                     int post_act, float* y)
@@ -58,12 +89,11 @@ int eagle_op_conv2d(int device, int precision, const float* x, int n, int h, int
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
     Net net;
-    const int g = precision == EAGLE_PREC_F32 ? 4 : 8;
-    const int cin_pad = cin <= g ? g : (cin + 15) / 16 * 16, cout_pad = (cout + 15) / 16 * 16;
     const int ho = (h + 2 * (ks / 2) - ks) / stride + 1, wo = (w + 2 * (ks / 2) - ks) / stride + 1;
     ConvLaunch L;
+    int cin_pad, cout_pad;
+    L.cfg = op_conv_choose(precision, ks, stride, cin, cout, wo, pre_act == ACT_NONE && post_act <= ACT_RELU, r1 && r2, &cin_pad, &cout_pad);
     to_dev(net, precision, x, n, h, w, cin, cin_pad, L.x);
-    L.cfg = conv_choose(precision, ks, stride, cin_pad, cout_pad, wo, pre_act == ACT_NONE && post_act <= ACT_RELU, r1 && r2);
     if (!conv_supported(precision, L.cfg)) fail(EAGLE_E_NOKERNEL, "no kernel instance ks=%d s=%d kc=%d nt=%d", ks, stride, L.cfg.kc, L.cfg.nt);
     std::vector<char> tiled(conv_weight_elems(precision, L.cfg) * (precision == EAGLE_PREC_F32 ? 4 : 2));
     conv_tile_weights(precision, L.cfg, w_hwio, cin, cout, tiled.data(), &L.descale);

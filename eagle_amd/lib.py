@@ -479,6 +479,8 @@ def load():
                                        i32, i32, i32, i32, vp, fp, fp, C.POINTER(C.c_int32)]
     L.eagle_op_post.argtypes = [i32, i32, i32, i32, i32, fp, vp, vp, vp, i32, i32, C.c_double, C.c_double, i32, i32]
     L.eagle_op_conv2d_argmax.argtypes = [i32, i32, fp, i32, i32, i32, i32, fp, fp, i32, i32, i32, fp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.eagle_op_conv_config.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
+    L.eagle_op_conv_table.argtypes = [i32, C.POINTER(C.c_int32), i32]
     L.eagle_debug.argtypes = [C.c_char_p, i64, vp, i64]
     L.eagle_team_colors.argtypes = [vp, vp, i32, vp, i32, vp]
     L.eagle_track_open.argtypes = [vp, C.POINTER(EagleTrackParams)]
@@ -667,7 +669,7 @@ EXPORTS = ["eagle_abi_sizes", "eagle_default_config", "eagle_create", "eagle_des
            "eagle_finalize_weights", "eagle_process_frames", "eagle_process_device_frames", "eagle_device_alloc",
            "eagle_device_free", "eagle_device_upload", "eagle_host_alloc", "eagle_host_free", "eagle_reproject", "eagle_comm_id", "eagle_comm_init", "eagle_gather",
            "eagle_set_profiling", "eagle_get_timings", "eagle_get_kernel_times", "eagle_op_conv2d", "eagle_op_bottleneck", "eagle_op_stem", "eagle_op_fuse_sum", "eagle_op_preprocess", "eagle_op_preprocess_lb",
-           "eagle_op_find_homography", "eagle_op_detect_tail", "eagle_op_post", "eagle_op_conv2d_argmax", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
+           "eagle_op_find_homography", "eagle_op_detect_tail", "eagle_op_post", "eagle_op_conv2d_argmax", "eagle_op_conv_config", "eagle_op_conv_table", "eagle_clip_open", "eagle_clip_close", "eagle_clip_detect_objects", "eagle_clip_detect_keypoints", "eagle_clip_get_keypoints",
            "eagle_clip_set_keypoints", "eagle_clip_flow", "eagle_clip_run", "eagle_clip_fetch", "eagle_debug", "eagle_track_open", "eagle_track_frames", "eagle_track_frames_cmc", "eagle_clip_motion_ecc", "eagle_clip_motion", "eagle_team_colors",
            "eagle_reid_features", "eagle_track_frames_reid", "eagle_process_frames_yuv", "eagle_process_device_frames_yuv", "eagle_yuv_to_bgr",
            "eagle_op_yuv_to_bgr", "eagle_annotate_device_frames", "eagle_annotate_frames", "eagle_overlay_from_record", "eagle_op_annotate",
@@ -2021,6 +2023,37 @@ def conv2d_argmax_tiles(hw, cin, cout, ks=1, stride=1, precision=PREC_F32S):
     if rc:
         raise EagleError(f"eagle_op_conv2d_argmax failed ({rc}): {L.eagle_last_error(None).decode()}")
     return tiles.value, th.value, tw.value
+
+
+CONV_CONFIG_FIELDS = ("kc", "nt", "wx", "variant", "tile_h", "tile_w", "lds_bytes", "supported")
+CONV_TABLES = {"instances": (0, ("prec", "ks", "stride", "kc", "nt", "variant")),
+               "adirect": (1, ("prec", "variant", "stride", "kc", "nt", "tile_h", "tile_w", "lds_bytes")),
+               "tuned_f16": (2, ("ks", "stride", "cin", "cout", "wo", "kc", "nt", "wx", "variant")),
+               "tuned_f32": (3, ("ks", "stride", "cin", "cout", "wo", "kc", "nt", "wx", "variant")),
+               "tuned_split": (4, ("ks", "stride", "cin", "cout", "wo", "kc", "nt", "wx", "variant"))}      # include/eagle.h EAGLE_CONV_TABLE_*
+
+
+def conv_config(precision, ks, stride, cin, cout, wo, plain_epilogue=False, second_residual=False):
+    """The configuration op_conv2d runs for a layer of real channel counts cin / cout on an output map wo columns wide, as a dict of CONV_CONFIG_FIELDS
+    (include/eagle.h eagle_op_conv_config; no GPU involved).  EAGLE_CONV_FORCE / EAGLE_F32_FORCE are read from the environment as on every call."""
+    L = load()
+    out = (C.c_int32 * 8)()
+    rc = L.eagle_op_conv_config(precision, ks, stride, cin, cout, wo, int(bool(plain_epilogue)), int(bool(second_residual)), out)
+    if rc:
+        raise EagleError(f"eagle_op_conv_config failed ({rc}): {L.eagle_last_error(None).decode()}")
+    return dict(zip(CONV_CONFIG_FIELDS, (int(v) for v in out)))
+
+
+def conv_table(which):
+    """One of the tables the convolution choice is made from, as a list of tuples in CONV_TABLES[which][1]'s field order (eagle_op_conv_table; no GPU involved)."""
+    L = load()
+    code, fields = CONV_TABLES[which]
+    n = L.eagle_op_conv_table(code, None, 0)
+    if n < 0:
+        raise EagleError(f"eagle_op_conv_table failed ({n}): {L.eagle_last_error(None).decode()}")
+    buf = (C.c_int32 * (n * len(fields)))()
+    assert L.eagle_op_conv_table(code, buf, len(buf)) == n
+    return [tuple(int(v) for v in buf[k * len(fields):(k + 1) * len(fields)]) for k in range(n)]
 
 
 def op_conv2d_argmax(x, w_hwio, bias, stride=1, precision=PREC_F32S, device=0):

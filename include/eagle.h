@@ -1805,6 +1805,24 @@ int eagle_op_post(int device, int n, int hm_h, int hm_w, int chunks, const float
 int eagle_op_conv2d_argmax(int device, int precision, const float* x, int n, int h, int w, int cin, const float* w_hwio, const float* bias, int cout, int ks, int stride,
                            float* logits, EagleArgmaxPart* parts, int* tiles, int* tile_h, int* tile_w);
 
+/* ---- which convolution form a call runs, and the tables the choice is made from (tests/test_conv_forms_cpu.py, tests/test_gpu_conv_forms.py).  Test surface
+ * only, host only: no GPU is touched.
+ * eagle_op_conv_config: the configuration eagle_op_conv2d (and the network builder) runs for a layer of REAL channel counts cin / cout on an output map wo
+ * columns wide, after the entry's own channel padding, with EAGLE_CONV_FORCE / EAGLE_F32_FORCE read as on every call.  plain_epilogue: no activation before
+ * the residual adds, none / ReLU after them, 2-byte / split output; second_residual: two residual operands.
+ * out = {kc, nt, wx, variant, tile_h, tile_w, lds_bytes, supported}; supported = 1: the instance exists and its LDS fits the 160 KiB a workgroup can have. */
+int eagle_op_conv_config(int precision, int ks, int stride, int cin, int cout, int wo, int plain_epilogue, int second_residual, int32_t out[8]);
+/* eagle_op_conv_table: rows of `which`, at most cap / width of them written to rows (rows == NULL: none); returns the table's row count, or a negative
+ * EAGLE_E_* code.  INSTANCES: every compiled generic / weight-stationary instance, 6 ints (precision, ks, stride, kc, nt, variant).  ADIRECT: the A-direct
+ * forms, 8 ints (precision, variant, stride, kc, nt, tile_h, tile_w, lds_bytes).  TUNED_*: the tuned tables verbatim, 9 ints (ks, stride, cin, cout, wo,
+ * kc, nt, wx, variant), in the order the choice walks them. */
+#define EAGLE_CONV_TABLE_INSTANCES 0
+#define EAGLE_CONV_TABLE_ADIRECT 1
+#define EAGLE_CONV_TABLE_TUNED_F16 2
+#define EAGLE_CONV_TABLE_TUNED_F32 3
+#define EAGLE_CONV_TABLE_TUNED_SPLIT 4
+int eagle_op_conv_table(int which, int32_t* rows, int cap);
+
 /* ---- the OSNet (ReID) kernels one launch at a time (reid.hip; tests/test_gpu_reid_ops.py).  Test surface only: each entry calls the network's own launch
  * function.  Every activation operand is a slice view: its `c` channels start at channel `off` of a buffer with `cs` floats per pixel (c, cs, off multiples
  * of 4, off + c <= cs).  Inputs are given dense ([n][h][w][c]) and placed into such a buffer by the entry; everything outside a slice holds the quiet NaN

@@ -10,26 +10,23 @@ import functools
 import numpy as np
 import pytest
 
+import conv_form_cases as F
+
 pytestmark = pytest.mark.gpu
 
 F32S_TOL = 4e-6          # the split family's bound against the fp32 oracle (tests/test_gpu_ops.py)
-V21 = "16,12,21"
-LIN = {30: "16,12,27", 60: "16,12,27"}      # 60 columns: no linear form, the switch falls through
+V21, LIN = F.V21, F.LIN  # 60 columns: no linear form, the switch falls through (conv_form_cases.run_forced proves which of the two happened)
 
-# n, h, w, cin, cout
-SHAPES = [
-    (2, 17, 30, 32, 192),      # HRNet's 17 x 30 map: 510 pixels = 4 items, the last one 126 pixels
-    (3, 5, 30, 16, 384),       # 150 pixels: a partial last item, two Cout blocks, several frames
-    (1, 1, 30, 16, 192),       # a single row: 30 of 32 lanes of one block
-    (2, 9, 30, 48, 192),       # 270 pixels: items start in the middle of a row
-    (2, 34, 60, 32, 192),      # HRNet's 34 x 60 map (fall-through, see above)
-    (1, 3, 60, 16, 192),
-    (2, 7, 60, 48, 384),
-]
-# launches of more than 256 items run the RING = 3 instances (every shape above stays under 256 items: the deep ring, RING = 6)
-BIG = [
-    (70, 17, 30, 16, 192),     # 280 items
-]
+# n, h, w, cin, cout (conv_form_cases.LIN_SHAPES):
+#   (2, 17, 30, 32, 192)       HRNet's 17 x 30 map: 510 pixels = 4 items, the last one 126 pixels
+#   (3, 5, 30, 16, 384)        150 pixels: a partial last item, two Cout blocks, several frames
+#   (1, 1, 30, 16, 192)        a single row: 30 of 32 lanes of one block
+#   (2, 9, 30, 48, 192)        270 pixels: items start in the middle of a row
+#   (2, 34, 60, 32, 192)       HRNet's 34 x 60 map (fall-through, see above)
+#   (1, 3, 60, 16, 192), (2, 7, 60, 48, 384)
+SHAPES = F.LIN_SHAPES
+# launches of more than 256 items run the RING = 3 instances (every shape above stays under 256 items: the deep ring, RING = 6): (70, 17, 30, 16, 192) is 280 items
+BIG = F.LIN_BIG
 
 
 def _rand(shape, seed, scale=1.0):
@@ -64,16 +61,12 @@ _got = {}
 
 
 def _run(shape, nres, post, force, monkeypatch):
-    """the case through op_conv2d under EAGLE_CONV_FORCE = force (None: conv_choose's own pick); the switch is read on every call"""
-    from eagle_amd import lib
+    """the case through op_conv2d under EAGLE_CONV_FORCE = force (None: conv_choose's own pick); the switch is read on every call.  Variant 21 and, on a
+    30-column map, variant 27 must be what runs; the linear form's id at any other width must give conv_choose's own pick."""
     key = (shape, nres, post, force)
     if key not in _got:
-        if force is None:
-            monkeypatch.delenv("EAGLE_CONV_FORCE", raising=False)
-        else:
-            monkeypatch.setenv("EAGLE_CONV_FORCE", force)
         x, wt, b, r1, r2, _ = _case(shape, nres, post)
-        y = lib.op_conv2d(x, wt, b, 1, 0, r1, r2, post, lib.PREC_F32S)
+        y = F.run_forced(monkeypatch, "f32s", force, x, wt, b, 1, 0, r1, r2, post, expect="named" if force == V21 else F.lin_expect(shape[2]))
         y.setflags(write=False)
         _got[key] = y
     return _got[key]
@@ -121,7 +114,7 @@ def test_linear_form_shallow_ring(shape, monkeypatch):
     _oracle(shape, 1, 1, monkeypatch)
 
 
-@pytest.mark.parametrize("shape", [(2, 9, 45, 16, 192), (2, 9, 60, 16, 192), (2, 9, 31, 16, 384), (2, 9, 29, 16, 192)])
+@pytest.mark.parametrize("shape", F.LIN_OTHER_WIDTHS)
 def test_linear_form_falls_through_at_other_widths(shape, monkeypatch):
     """The linear form forced at a width it is not compiled for: conv_choose's own pick runs instead, without an error."""
     default = _run(shape, 1, 1, None, monkeypatch)

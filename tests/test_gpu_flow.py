@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import conv_form_cases
 import flow_cases
 from eagle_amd import lib, records, weights
 from eagle_amd.coordinate_model import CoordinateModel
@@ -181,16 +182,18 @@ def _oracle(frames, kint, hint, det_kp, det_obj):
     return res, st
 
 
-@pytest.mark.parametrize("force", [None, "16,1,0"])
-def test_lk_bit_exact_while_another_handle_runs_the_networks(model, force, state_dicts):
+@pytest.mark.parametrize("force", [None, conv_form_cases.FLOW_FORCE])
+def test_lk_bit_exact_while_another_handle_runs_the_networks(model, force, state_dicts, monkeypatch):
     """K12 + filters against the oracle WHILE a second handle keeps the GPU busy with the stateless path on another thread
     (round 1's open issue: next to the convolution kernels K12 returned different sub-pixel results — DESIGN.md §8c; the worst
-    co-runner found by tools/probe_lk_concurrency.py is the plain register-staged kernel at kc = 16, nt = 1, forced here)."""
+    co-runner found by tools/probe_lk_concurrency.py is the plain register-staged kernel at kc = 16, nt = 1, forced here: the
+    switch applies to every layer with Cin = 16 k, which is checked on the detector's first C2f bottleneck)."""
     import threading
     from eagle_amd import synth
     hs, ys = state_dicts
     if force:
         os.environ["EAGLE_CONV_FORCE"] = force
+        conv_form_cases.assert_form(monkeypatch, "f16", force, 3, 1, 16, 16, 160, False, False)
     try:
         co = CoordinateModel(precision="f16", batch=8, hrnet_state_dict=hs, detector_state_dict=ys)
     finally:

@@ -3,6 +3,8 @@ fp32 kernels must be BIT-EXACT (same fmaf chain as oracle/eo_prims.c); fp16 kern
 import numpy as np
 import pytest
 
+import conv_form_cases as F
+
 pytestmark = pytest.mark.gpu
 
 F16_TOL = 2e-3  # relative to max|y|: fp16 output rounding (2^-11) + reordered fp32 accumulation
@@ -72,19 +74,14 @@ def test_conv_parity(case, prec):
         assert err < F16_TOL, f"fp16 conv error {err}"
 
 
-@pytest.mark.parametrize("stack", ["1", "0"])
-@pytest.mark.parametrize("force", ["3,2,0", "3,1,0", "6,2,3", "3,1,3", "2,2,4", "1,1,4"])
-@pytest.mark.parametrize("shape,ks,st,cin,cout", [((5, 17, 30), 3, 1, 48, 96), ((4, 7, 45), 3, 1, 32, 48), ((3, 34, 61), 3, 2, 48, 96), ((6, 12, 20), 1, 1, 64, 96),
-                                                  ((7, 1, 1), 3, 1, 16, 48), ((2, 33, 37), 3, 2, 3, 48), ((50, 17, 30), 3, 1, 32, 48)])
+@pytest.mark.parametrize("shape,ks,st,cin,cout,force,stack", [c[1:] for c in F.f32_tiling_cases()], ids=[c[0] for c in F.f32_tiling_cases()])
 def test_conv_f32_every_tiling_is_bit_exact(shape, ks, st, cin, cout, force, stack, monkeypatch):
     """The exact family's tilings (round 4): full / half / quarter tiles (variants 0 / 3 / 4), 16 x 16 or 8 x 32 sub-tile arrangement, and the
     batch tiled as ONE image of N (H + 1) rows for stride-1 layers (a tile may straddle several frames; the virtual zero row between two
     frames is both frames' padding).  The K order of every output is the canonical one whatever the tiling: bit-equal to the oracle, with
-    residual and ReLU, on maps whose rows do not divide the tile (17, 7, 1) and batches of 2 - 7 frames."""
-    from eagle_amd import lib
+    residual and ReLU, on maps whose rows do not divide the tile (17, 7, 1) and batches of 2 - 7 frames.  The cases are
+    conv_form_cases.f32_tiling_cases: tilings x layers x stacking, each with a string the layer has an instance for."""
     from oracle import prims as P
-    monkeypatch.setenv("EAGLE_F32_FORCE", force)
-    monkeypatch.setenv("EAGLE_F32_STACK", stack)
     n, h, w = shape
     x = _rand((n, h, w, cin), 61)
     wt = _rand((ks, ks, cin, cout), 62, (2.0 / (cin * ks * ks)) ** 0.5)
@@ -93,19 +90,16 @@ def test_conv_f32_every_tiling_is_bit_exact(shape, ks, st, cin, cout, force, sta
     wo = (w + 2 * (ks // 2) - ks) // st + 1
     r1 = _rand((n, ho, wo, cout), 64)
     ref = P.conv2d(x, wt, b, stride=st, pre=0, r1=r1, r2=None, post=1)
-    got = lib.op_conv2d(x, wt, b, st, 0, r1, None, 1, lib.PREC_F32)
+    got = F.run_forced(monkeypatch, "f32", force, x, wt, b, st, 0, r1, None, 1, stack=stack)
     assert np.array_equal(ref, got), f"fp32 conv tiling {force} stack {stack} not bit-exact: max|d|={np.abs(ref - got).max()}"
 
 
-@pytest.mark.parametrize("force,cin,cout", [("48,3,6", 48, 48), ("48,3,7", 48, 48), ("96,3,7", 96, 96), ("96,3,6", 96, 96),
-                                            ("64,4,7", 64, 64), ("96,2,7", 96, 32)])
-@pytest.mark.parametrize("shape", [(3, 37, 45), (2, 5, 70), (1, 16, 16)])
+@pytest.mark.parametrize("force,cin,cout", F.WS_FORMS)
+@pytest.mark.parametrize("shape", F.WS_MAPS)
 def test_conv_weight_stationary_variants(force, cin, cout, shape, monkeypatch):
     """The persistent weight-stationary 3x3 kernels (conv.hip variants 6/7), forced through EAGLE_CONV_FORCE, against the
     oracle on ragged maps (partial tiles, more workgroup slots than tiles, several tiles per workgroup)."""
-    from eagle_amd import lib
     from oracle import prims as P
-    monkeypatch.setenv("EAGLE_CONV_FORCE", force)
     n, h, w = shape
     x = _rand((n, h, w, cin), 11)
     wt = _rand((3, 3, cin, cout), 12, (2.0 / (cin * 9)) ** 0.5)
@@ -113,7 +107,7 @@ def test_conv_weight_stationary_variants(force, cin, cout, shape, monkeypatch):
     r1 = _rand((n, h, w, cout), 14)
     q = P.round_f16
     ref = P.conv2d(q(x), q(wt), b, stride=1, pre=0, r1=q(r1), r2=None, post=1, f16_out=True)
-    got = lib.op_conv2d(x, wt, b, 1, 0, r1, None, 1, lib.PREC_F16)
+    got = F.run_forced(monkeypatch, "f16", force, x, wt, b, 1, 0, r1, None, 1)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F16_TOL, f"fp16 weight-stationary conv error {err}"
 
@@ -158,25 +152,22 @@ def _a_direct_case(cin, cout, shape, res, post, stride):
     assert err < F16_TOL, f"fp16 A-direct conv error {err}"
 
 
-@pytest.mark.parametrize("force", ["16,1,0", "16,2,0", "16,3,0", "16,4,0", "32,3,0", "32,4,0", "16,6,3", "32,6,3", "16,4,3", "32,2,3"])
-@pytest.mark.parametrize("cin,cout,ks,stride", [(96, 96, 3, 1), (64, 192, 3, 2), (192, 96, 1, 1)])
+@pytest.mark.parametrize("cin,cout,ks,stride,force", [c[1:] for c in F.split_variant_cases()], ids=[c[0] for c in F.split_variant_cases()])
 def test_conv_split_variants(force, cin, cout, ks, stride, monkeypatch):
     """Every (kc, nt, tile) instance class of the split family through EAGLE_CONV_FORCE, on a ragged map with two residuals and ReLU,
-    against the fp32 oracle."""
-    from eagle_amd import lib
+    against the fp32 oracle.  The cases are conv_form_cases.split_variant_cases: forces x layers, with the stride-2 layer's chunk of 32 (no such
+    instance can run) replaced by its chunk of 8."""
     from oracle import prims as P
-    kc, nt, _ = (int(v) for v in force.split(","))
-    if cout % (16 * nt) or cin % kc or (ks == 1 and kc == 8):
+    if not F.split_variant_fits(force, cin, cout, ks, stride):
         pytest.skip("shape does not fit this instance")
-    monkeypatch.setenv("EAGLE_CONV_FORCE", force)
-    n, h, w = 2, 19, 45
+    n, h, w = F.SPLIT_MAP
     ho, wo = (h + 2 * (ks // 2) - ks) // stride + 1, (w + 2 * (ks // 2) - ks) // stride + 1
     x = _rand((n, h, w, cin), 31)
     wt = _rand((ks, ks, cin, cout), 32, (2.0 / (cin * ks * ks)) ** 0.5)
     b = _rand((cout,), 33, 0.1)
     r1, r2 = _rand((n, ho, wo, cout), 34), _rand((n, ho, wo, cout), 35)
     ref = P.conv2d(x, wt, b, stride=stride, pre=0, r1=r1, r2=r2, post=1)
-    got = lib.op_conv2d(x, wt, b, stride, 0, r1, r2, 1, lib.PREC_F32S)
+    got = F.run_forced(monkeypatch, "f32s", force, x, wt, b, stride, 0, r1, r2, 1)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F32S_TOL, f"split conv error {err}"
 
@@ -205,10 +196,10 @@ def test_conv_split_a_direct(cin, cout, shape, res, post, monkeypatch):
     assert err < F32S_TOL, f"split A-direct conv error {err}"
 
 
-@pytest.mark.parametrize("cin,cout", [(96, 96), (192, 192), (48, 192), (384, 384), (64, 96), (16, 192), (32, 288), (144, 96)])
-@pytest.mark.parametrize("shape", [(3, 37, 45), (2, 5, 70), (1, 16, 16), (5, 17, 30), (1, 68, 120), (1, 1, 1), (2, 9, 33), (2, 34, 60), (1, 7, 65)])
-@pytest.mark.parametrize("res,post", [(True, 1), (False, 1), (False, 0), (2, 1)])
-@pytest.mark.parametrize("tile", ["rows", "wide64"])
+@pytest.mark.parametrize("cin,cout", F.M32_LAYERS)
+@pytest.mark.parametrize("shape", F.M32_MAPS)
+@pytest.mark.parametrize("res,post", F.RES_POST_4)
+@pytest.mark.parametrize("tile", F.M32_TILES)
 def test_conv_split_a_direct_m32(cin, cout, shape, res, post, tile, monkeypatch):
     """Round 5: the A-direct kernels of the split family on v_mfma_f32_32x32x16_f16 (conv_ad_split32.inc; variant 21: BN = 192, tile 4 x 32; variant 22:
     BN = 96, tile 8 x 32; wave tile 96 channels x 2 rows x 32 pixels), forced through EAGLE_CONV_FORCE, against the fp32 oracle: ragged maps, partial tiles in
@@ -219,8 +210,8 @@ def test_conv_split_a_direct_m32(cin, cout, shape, res, post, tile, monkeypatch)
     if shape[1] * shape[2] > 4000 and (cin > 96 or not res):
         pytest.skip("large map: one representative case")
     # tile "rows": the wave's two 32-pixel blocks in two rows (variants 21 / 22: tiles 4 x 32 / 8 x 32); "wide64": side by side (variants 23 / 24: tiles 2 x 64 / 4 x 64)
-    v = (21 if cout % 192 == 0 else 22) + (2 if tile == "wide64" else 0)
-    monkeypatch.setenv("EAGLE_CONV_FORCE", f"16,{12 if cout % 192 == 0 else 6},{v}")
+    force = F.m32_force(cout, tile)
+    v = int(force.split(",")[2])
     n, h, w = shape
     x = _rand((n, h, w, cin), 51)
     wt = _rand((3, 3, cin, cout), 52, (2.0 / (cin * 9)) ** 0.5)
@@ -228,21 +219,20 @@ def test_conv_split_a_direct_m32(cin, cout, shape, res, post, tile, monkeypatch)
     r1 = _rand((n, h, w, cout), 54) if res else None
     r2 = _rand((n, h, w, cout), 55) if res == 2 else None
     ref = P.conv2d(x, wt, b, stride=1, pre=0, r1=r1, r2=r2, post=post)
-    got = lib.op_conv2d(x, wt, b, 1, 0, r1, r2, post, lib.PREC_F32S)
+    got = F.run_forced(monkeypatch, "f32s", force, x, wt, b, 1, 0, r1, r2, post)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F32S_TOL, f"split A-direct 32x32x16 conv (variant {v}) error {err}"
 
 
-@pytest.mark.parametrize("shape", [(3, 37, 45), (1, 16, 16), (2, 135, 240)])
-@pytest.mark.parametrize("res,post", [(True, 1), (False, 0), (2, 1)])
-@pytest.mark.parametrize("form", ["12", "13", "19"])
+@pytest.mark.parametrize("shape", F.K48_MAPS)
+@pytest.mark.parametrize("res,post", F.RES_POST_3)
+@pytest.mark.parametrize("form", F.K48_FORMS)
 def test_conv_split_a_direct_k_split_48(shape, res, post, form, monkeypatch):
     """The Cout = 48 forms of the split A-direct kernel: variant 12 (K split over wave pairs, partial accumulators exchanged through LDS) and
     variant 13 (four pixel groups, 16 x 32 tile, one halo buffer), variant 19 (the same tile with the two-deep halo ring, persistent), forced through
     EAGLE_CONV_FORCE."""
     from eagle_amd import lib
     from oracle import prims as P
-    monkeypatch.setenv("EAGLE_CONV_FORCE", f"16,3,{form}")
     n, h, w = shape
     x = _rand((n, h, w, 48), 61)
     wt = _rand((3, 3, 48, 48), 62, (2.0 / (48 * 9)) ** 0.5)
@@ -250,14 +240,14 @@ def test_conv_split_a_direct_k_split_48(shape, res, post, form, monkeypatch):
     r1 = _rand((n, h, w, 48), 64) if res else None
     r2 = _rand((n, h, w, 48), 65) if res == 2 else None
     ref = P.conv2d(x, wt, b, stride=1, pre=0, r1=r1, r2=r2, post=post)
-    got = lib.op_conv2d(x, wt, b, 1, 0, r1, r2, post, lib.PREC_F32S)
+    got = F.run_forced(monkeypatch, "f32s", f"16,3,{form}", x, wt, b, 1, 0, r1, r2, post)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F32S_TOL, f"split K-split conv error {err}"
 
 
-@pytest.mark.parametrize("cin,cout", [(48, 96), (96, 192), (256, 96), (192, 384), (48, 192), (96, 96), (32, 96)])
-@pytest.mark.parametrize("shape", [(3, 37, 45), (2, 5, 70), (1, 16, 16), (2, 135, 240), (1, 1, 1)])
-@pytest.mark.parametrize("res,post", [(True, 1), (False, 0), (2, 1)])
+@pytest.mark.parametrize("cin,cout", F.S2D_LAYERS)
+@pytest.mark.parametrize("shape", F.S2D_MAPS)
+@pytest.mark.parametrize("res,post", F.RES_POST_3)
 def test_conv_split_a_direct_stride2(cin, cout, shape, res, post, monkeypatch):
     """The stride-2 form of the split A-direct kernel (variants 10 / 11: space-to-depth image gathered by the LDS-DMA addressing, 6 K-steps per
     16-channel chunk), forced through EAGLE_CONV_FORCE: odd and even input sizes, partial tiles, a 1 x 1 input, 0 - 2 residual operands."""
@@ -265,7 +255,6 @@ def test_conv_split_a_direct_stride2(cin, cout, shape, res, post, monkeypatch):
     from oracle import prims as P
     if shape[1] * shape[2] > 4000 and (cin > 96 or not res):
         pytest.skip("large map: one representative case")
-    monkeypatch.setenv("EAGLE_CONV_FORCE", "16,12,10" if cout % 192 == 0 else "16,6,11")
     n, h, w = shape
     ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
     x = _rand((n, h, w, cin), 71)
@@ -274,14 +263,14 @@ def test_conv_split_a_direct_stride2(cin, cout, shape, res, post, monkeypatch):
     r1 = _rand((n, ho, wo, cout), 74) if res else None
     r2 = _rand((n, ho, wo, cout), 75) if res == 2 else None
     ref = P.conv2d(x, wt, b, stride=2, pre=0, r1=r1, r2=r2, post=post)
-    got = lib.op_conv2d(x, wt, b, 2, 0, r1, r2, post, lib.PREC_F32S)
+    got = F.run_forced(monkeypatch, "f32s", F.s2d_force(cout), x, wt, b, 2, 0, r1, r2, post)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F32S_TOL, f"split stride-2 A-direct conv error {err}"
 
 
-@pytest.mark.parametrize("cin,cout", [(96, 192), (48, 192), (192, 384), (48, 384), (144, 192), (48, 96), (96, 96), (48, 288)])
-@pytest.mark.parametrize("shape", [(3, 37, 45), (2, 5, 70), (1, 16, 16), (2, 68, 120), (1, 1, 1), (2, 130, 129), (1, 9, 200)])
-@pytest.mark.parametrize("res,post", [(True, 1), (False, 0), (2, 1)])
+@pytest.mark.parametrize("cin,cout", F.S2T_LAYERS)
+@pytest.mark.parametrize("shape", F.S2T_MAPS)
+@pytest.mark.parametrize("res,post", F.RES_POST_3)
 def test_conv_split_a_direct_true_stride2(cin, cout, shape, res, post, monkeypatch):
     """Variants 14 / 15: the stride-1 A-direct kernel over an even / odd column-plane halo (true stride 2, no space-to-depth padding; Cin = 48 k;
     Cout = 192 k: four Cout groups; Cout = 96 k: two Cout groups with the K dimension split over wave pairs), forced through EAGLE_CONV_FORCE: odd and even input sizes, partial tiles in both directions, several tiles per row (the 65-column
@@ -290,7 +279,6 @@ def test_conv_split_a_direct_true_stride2(cin, cout, shape, res, post, monkeypat
     from oracle import prims as P
     if shape[1] * shape[2] > 4000 and (cin > 96 or not res):
         pytest.skip("large map: one representative case")
-    monkeypatch.setenv("EAGLE_CONV_FORCE", "16,12,14" if cout % 192 == 0 else "16,6,15")
     n, h, w = shape
     ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
     x = _rand((n, h, w, cin), 81)
@@ -299,19 +287,18 @@ def test_conv_split_a_direct_true_stride2(cin, cout, shape, res, post, monkeypat
     r1 = _rand((n, ho, wo, cout), 84) if res else None
     r2 = _rand((n, ho, wo, cout), 85) if res == 2 else None
     ref = P.conv2d(x, wt, b, stride=2, pre=0, r1=r1, r2=r2, post=post)
-    got = lib.op_conv2d(x, wt, b, 2, 0, r1, r2, post, lib.PREC_F32S)
+    got = F.run_forced(monkeypatch, "f32s", F.s2t_force(cout), x, wt, b, 2, 0, r1, r2, post)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F32S_TOL, f"split true-stride-2 A-direct conv error {err}"
 
 
-@pytest.mark.parametrize("shape", [(3, 37, 45), (1, 16, 16), (2, 135, 240), (2, 9, 100), (1, 8, 48), (1, 1, 1)])
-@pytest.mark.parametrize("res,post", [(True, 1), (False, 0), (2, 1)])
+@pytest.mark.parametrize("shape", F.T48_MAPS)
+@pytest.mark.parametrize("res,post", F.RES_POST_3)
 def test_conv_split_8x48_tile(shape, res, post, monkeypatch):
     """Variant 18 of the generic split kernel: six 16-pixel sub-tiles per wave, 8 x 48 output tiles (HRNet's 240-pixel-wide 48-channel branch: 240 = 5 x 48),
     forced through EAGLE_CONV_FORCE: exact and partial tiles in both directions, 0 - 2 residual operands."""
     from eagle_amd import lib
     from oracle import prims as P
-    monkeypatch.setenv("EAGLE_CONV_FORCE", "16,3,18")
     n, h, w = shape
     x = _rand((n, h, w, 48), 101)
     wt = _rand((3, 3, 48, 48), 102, (2.0 / (48 * 9)) ** 0.5)
@@ -319,7 +306,7 @@ def test_conv_split_8x48_tile(shape, res, post, monkeypatch):
     r1 = _rand((n, h, w, 48), 104) if res else None
     r2 = _rand((n, h, w, 48), 105) if res == 2 else None
     ref = P.conv2d(x, wt, b, stride=1, pre=0, r1=r1, r2=r2, post=post)
-    got = lib.op_conv2d(x, wt, b, 1, 0, r1, r2, post, lib.PREC_F32S)
+    got = F.run_forced(monkeypatch, "f32s", "16,3,18", x, wt, b, 1, 0, r1, r2, post)
     err = np.abs(ref - got).max() / max(np.abs(ref).max(), 1e-6)
     assert err < F32S_TOL, f"split 8x48-tile conv error {err}"
 

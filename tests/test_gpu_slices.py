@@ -15,6 +15,7 @@ import functools
 import numpy as np
 import pytest
 
+import conv_form_cases as F
 import slice_cases as S
 from eagle_amd import lib
 from test_gpu_ops import F16_TOL, F32S_TOL
@@ -48,6 +49,13 @@ def _check_oracle(fmt, got, ref):
         assert err < (F16_TOL if fmt == "f16" else F32S_TOL), f"{fmt} conv error {err}"
 
 
+def _forced(monkeypatch, fmt, force, ks, st, cin, cout, shape, pre, post, stack=None):
+    """the force switches for the dense and the sliced call of one case (both see the same channel counts, one residual), and the proof that the form they
+    name is what conv_choose gives: a string that does not apply is ignored without a word"""
+    F.set_force(monkeypatch, fmt, force, stack)
+    F.assert_form(monkeypatch, fmt, force, ks, st, cin, cout, F.out_size(shape[1], shape[2], ks, st)[1], pre == 0 and post <= 1, False)
+
+
 def _sliced_conv(fmt, ks, st, mode, G, shape, cin, cout, pre, post, force=None, stack=None):
     n, h, w = shape
     ho, wo = (h + 2 * (ks // 2) - ks) // st + 1, (w + 2 * (ks // 2) - ks) // st + 1
@@ -75,15 +83,14 @@ def test_conv_on_slices(fmt, ks, st, mode, g, shape, monkeypatch):
 @pytest.mark.parametrize("stack", ["1", "0"])
 @pytest.mark.parametrize("force", S.FORCE_F32)
 def test_conv_f32_every_tiling_on_slices(force, stack, shape, monkeypatch):
-    monkeypatch.setenv("EAGLE_F32_FORCE", force)
-    monkeypatch.setenv("EAGLE_F32_STACK", stack)
+    _forced(monkeypatch, "f32", force, 3, 1, 48, 48, shape, SILU, 0, stack)
     _sliced_conv("f32", 3, 1, "r_in_x", S.GEOMS["c48"], shape, 48, 48, SILU, 0, force, stack)
 
 
 @pytest.mark.parametrize("shape", S.FORCE_MAPS, ids=str)
 @pytest.mark.parametrize("fmt,force", [("f16", f) for f in S.FORCE_F16] + [("f32s", f) for f in S.FORCE_SPLIT])
 def test_conv_f16_and_split_every_tiling_on_slices(fmt, force, shape, monkeypatch):
-    monkeypatch.setenv("EAGLE_CONV_FORCE", force)
+    _forced(monkeypatch, fmt, force, 3, 1, 48, 48, shape, SILU, 0)
     _sliced_conv(fmt, 3, 1, "r_in_x", S.GEOMS["c48"], shape, 48, 48, SILU, 0, force)
 
 
@@ -91,7 +98,7 @@ def test_conv_f16_and_split_every_tiling_on_slices(fmt, force, shape, monkeypatc
 def test_conv_a_direct_and_weight_stationary_forms_on_slices(fmt, force, st, cin, cout, monkeypatch):
     """The plain-epilogue forms (HRNet's, which runs them dense): sliced input, output and residual, the residual in the output buffer.  ConvLaunch takes any
     TView, so these forms honour slices like the generic ones: (a) - (c) as above."""
-    monkeypatch.setenv("EAGLE_CONV_FORCE", force)
+    _forced(monkeypatch, fmt, force, 3, st, cin, cout, S.AD_MAP, 0, 1)
     _sliced_conv(fmt, 3, st, "c2f_x", S.ad_geom(cin, cout), S.AD_MAP, cin, cout, 0, 1, force)
 
 
