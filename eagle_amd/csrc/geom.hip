@@ -19,7 +19,10 @@ namespace eagle {
 
 #define POST_T 256
 #define RANSAC_WIN (POST_T * 6)
-#define RNG_N 65536        // precomputed draws of cv::RNG(-1): the stream does not depend on the data
+#define RNG_N 65536        // precomputed draws of cv::RNG(-1): the stream does not depend on the data.  The table ends with the generator's carry after its last draw
+                           // (entry RNG_N); an input that draws past it (no consensus and mostly degenerate subsets; real frames stay far below) is served by
+                           // one lane continuing the multiply-with-carry sequence from there, window by window: slow, and the oracle's draws to the last one
+#define RNG_A 4164903690ULL
 #define DEPS 2.220446049250313e-16
 
 // Ordering point between the lanes of ONE wave working on shared LDS data: the LDS operations of a wave execute in issue order, so all that is needed is that the
@@ -231,6 +234,8 @@ struct HomoShared {
     double lm_r[2 * EAGLE_MAX_KP], lm_rn[2 * EAGLE_MAX_KP], lm_J[16 * EAGLE_MAX_KP];
     double lm_A[8][8], lm_g[8], lm_h[8], lm_hn[8], lm_M[8][9], lm_d[8];
     double lm_S;
+    unsigned long long rng_state;      // past the table: the generator's state in front of draw max(pos, RNG_N) ...
+    unsigned long long rng_ck[(RANSAC_WIN + 256) / 64];      // ... and in front of every 64th draw this round generated, for the round's end to pick the next start from
     int lm_lambda, lm_flag;            // flag: 0 = solve failed (retry), 1 = candidate ready, 2 = improved, 3 = stop
     alignas(16) unsigned char code[POST_T];   // per attempt: 255 degenerate subset (rejected), 254 model failed, else inlier count
     unsigned char mask[EAGLE_MAX_KP];
@@ -239,7 +244,7 @@ struct HomoShared {
     int wlive[POST_T / 64];            // attempts of the round per wave
     alignas(4) unsigned char draw[RANSAC_WIN + 256];   // the round's slice of the random stream, already reduced modulo the point count
     unsigned tuple[RANSAC_WIN];        // 4 packed point indices of the sampling attempt starting at window position w
-    unsigned char len[RANSAC_WIN];     // draws it consumes (0 = stream exhausted)
+    unsigned char len[RANSAC_WIN];     // draws it consumes (0 = none: it repeats indices for 250 draws)
     int start[POST_T];
 };
 
@@ -472,7 +477,18 @@ __device__ void find_homography_block(HomoShared& S, const unsigned* __restrict_
         for (int ei = 0; ei < NDRAW; ++ei) {      // one coalesced pass over the stream, one modulo per draw
             const int e = tid + ei * POST_T, j = S.pos + e;
             const unsigned raw = have_pre ? pre[ei] : (j < RNG_N ? rng_raw[j] : 0u);
-            S.draw[e] = j < RNG_N ? (unsigned char)(raw % (unsigned)n) : (unsigned char)0;
+            if (j < RNG_N) S.draw[e] = (unsigned char)(raw % (unsigned)n);
+        }
+        const int pos0 = S.pos;
+        const bool past = pos0 + RANSAC_WIN + 256 > RNG_N;       // (uniform) the window reaches beyond the table: lane 0 generates those draws
+        if (past && tid == 0) {
+            const int P = pos0 > RNG_N ? pos0 : RNG_N;
+            unsigned long long st = pos0 > RNG_N ? S.rng_state : (((unsigned long long)rng_raw[RNG_N] << 32) | rng_raw[RNG_N - 1]);
+            for (int j = P; j < pos0 + RANSAC_WIN + 256; ++j) {
+                if (((j - P) & 63) == 0) S.rng_ck[(j - P) >> 6] = st;
+                st = (unsigned long long)(unsigned)st * RNG_A + (unsigned)(st >> 32);
+                S.draw[j - pos0] = (unsigned char)((unsigned)st % (unsigned)n);
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -480,11 +496,11 @@ __device__ void find_homography_block(HomoShared& S, const unsigned* __restrict_
             const int w = tid + wi * POST_T;
             // Eight draws of the window from LDS as three aligned words, parsed in registers without a branch (each draw against the up to three indices accepted before it);
             // the draw-by-draw loop (one dependent LDS byte read per draw: 0.5 - 0.65 ms of the 2.3-ms kernel until round 5) only continues the rare attempts
-            // that repeat indices five times in eight draws, and serves the end of the stream.
+            // that repeat indices five times in eight draws.
             int j = S.pos + w, cnt = 0;
             const int j0 = j;
             unsigned tuple = 0;
-            if (j0 + 8 <= RNG_N) {
+            {
                 const unsigned* dw = (const unsigned*)(S.draw + (w & ~3));
                 const unsigned long long lo = (unsigned long long)dw[0] | ((unsigned long long)dw[1] << 32), hi = dw[2];
                 const int sh = 8 * (w & 3);
@@ -504,7 +520,7 @@ __device__ void find_homography_block(HomoShared& S, const unsigned* __restrict_
             }
             if (cnt < 4) {
                 int idx[4] = {(int)(tuple & 255), (int)((tuple >> 8) & 255), (int)((tuple >> 16) & 255), (int)(tuple >> 24)};
-                while (cnt < 4 && j < RNG_N && j - j0 < 250) {
+                while (cnt < 4 && j - j0 < 250) {
                     const int v = (int)S.draw[j++ - S.pos];
                     bool dup = false;
 #pragma unroll
@@ -523,7 +539,7 @@ __device__ void find_homography_block(HomoShared& S, const unsigned* __restrict_
         __syncthreads();
         RT(tA)
         // (b) the attempt chain: attempt k starts where attempt k-1 stopped drawing, s_0 = 0, s_k+1 = next(s_k) with next(w) = w + len[w].  A position without
-        //     an attempt (len 0: stream exhausted) or beyond the window is absorbing.  Until round 5 one wave walked the chain with a guess-and-check per 64
+        //     an attempt (len 0) or beyond the window is absorbing.  Until round 5 one wave walked the chain with a guess-and-check per 64
         //     attempts (0.56 - 0.63 ms of the kernel at ~5.3 draws per attempt); now pointer doubling: next^4, next^16 and next^64 for every window position,
         //     three passes of four dependent reads, and thread k reaches s_k in at most twelve hops along the base-4 digits of k.
         {
@@ -573,6 +589,12 @@ __device__ void find_homography_block(HomoShared& S, const unsigned* __restrict_
 #pragma unroll
             for (int ei = 0; ei < NDRAW; ++ei) { const int j = np + tid + ei * POST_T; pre[ei] = j < RNG_N ? rng_raw[j] : 0u; }
             have_pre = true;
+            if (past && tid == 0 && np > RNG_N) {          // the generator's state in front of the next round's first draw: from the checkpoint below it
+                const int P = pos0 > RNG_N ? pos0 : RNG_N;
+                unsigned long long st = S.rng_ck[(np - P) >> 6];
+                for (int r = (np - P) & 63; r > 0; --r) st = (unsigned long long)(unsigned)st * RNG_A + (unsigned)(st >> 32);
+                S.rng_state = st;
+            }
         }
         if (tid < natt) {                           // (c) degeneracy test, 4-point model and its support, in parallel
             const unsigned tp = S.tuple[S.start[tid]];
@@ -602,7 +624,7 @@ __device__ void find_homography_block(HomoShared& S, const unsigned* __restrict_
             // (only a run that starts at the cursor can get there).  The segment up to and including the first event is folded in one step, then the masks are
             // rebuilt behind it.  Until round 5 one lane walked the codes (16 at a time where nothing could happen): 0.22 - 0.29 ms of the kernel.
             int iter = S.iter, fail_run = S.fail_run, niters = S.niters, max_good = S.max_good, stop = 0;
-            if (natt == 0) stop = 1;                  // precomputed stream exhausted
+            if (natt == 0) stop = 1;                  // an attempt of 250 draws or more (4/5 ^ 240 at best: never drawn)
             for (int base = 0; base < natt && !stop && iter < niters; base += 64) {
                 const int k = base + tid;
                 const int code = k < natt ? (int)S.code[k] : 255;
@@ -1262,12 +1284,13 @@ static const unsigned* ransac_rng_table()
     HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> g(m);
     if (!tab[dev]) {
-        std::vector<unsigned> h(RNG_N);
+        std::vector<unsigned> h(RNG_N + 1);
         unsigned long long st = 0xffffffffffffffffULL;
         for (int i = 0; i < RNG_N; ++i) { st = (unsigned long long)(unsigned)st * 4164903690ULL + (unsigned)(st >> 32); h[i] = (unsigned)st; }
+        h[RNG_N] = (unsigned)(st >> 32);        // the carry behind the last draw: where the kernel takes the sequence up
         unsigned* d = nullptr;
-        HIP_CHECK(hipMalloc((void**)&d, sizeof(unsigned) * RNG_N));
-        HIP_CHECK(hipMemcpy(d, h.data(), sizeof(unsigned) * RNG_N, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMalloc((void**)&d, sizeof(unsigned) * (RNG_N + 1)));
+        HIP_CHECK(hipMemcpy(d, h.data(), sizeof(unsigned) * (RNG_N + 1), hipMemcpyHostToDevice));
         tab[dev] = d;
     }
     return tab[dev];

@@ -547,8 +547,9 @@ static int eo_solve8(double A[8][8], double b[8], double x[8])
 static const double EO_P10[33] = {1e-16, 1e-15, 1e-14, 1e-13, 1e-12, 1e-11, 1e-10, 1e-9, 1e-8, 1e-7, 1e-6, 1e-5,
                                    1e-4, 1e-3, 1e-2, 1e-1, 1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10,
                                    1e11, 1e12, 1e13, 1e14, 1e15, 1e16};
-void eo_lm_refine(const double* src, const double* dst, int n, double* H, int max_iters)
+static int eo_lm_refine_count(const double* src, const double* dst, int n, double* H, int max_iters)
 {
+    int accepted = 0;
     double* r = (double*)malloc(sizeof(double) * 2 * n);
     double* rn = (double*)malloc(sizeof(double) * 2 * n);
     double* J = (double*)malloc(sizeof(double) * 2 * n * 8);
@@ -573,7 +574,7 @@ void eo_lm_refine(const double* src, const double* dst, int n, double* H, int ma
             double Sn = 0; for (int i = 0; i < 2 * n; ++i) Sn += rn[i] * rn[i];
             if (Sn < S) {
                 for (int k = 0; k < 8; ++k) h[k] = hn[k];
-                S = Sn; improved = 1;
+                S = Sn; improved = 1; ++accepted;
                 lambdaLg10 = lambdaLg10 - 1 < -16 ? -16 : lambdaLg10 - 1;
             } else {
                 lambdaLg10 = lambdaLg10 + 1 > 16 ? 16 : lambdaLg10 + 1;
@@ -585,12 +586,44 @@ void eo_lm_refine(const double* src, const double* dst, int n, double* H, int ma
     for (int k = 0; k < 8; ++k) H[k] = h[k];
     H[8] = 1.0;
     free(r); free(rn); free(J);
+    return accepted;
 }
+void eo_lm_refine(const double* src, const double* dst, int n, double* H, int max_iters) { eo_lm_refine_count(src, dst, n, H, max_iters); }
 
-/* src (image) / dst (world) float32 [n,2]; returns 1 and fills H[9] (double), mask[n] on success. */
-int eo_find_homography_ransac(const float* srcf, const float* dstf, int n, double thresh, int max_iters,
-                              double confidence, int refine_iters, double* H, uint8_t* mask)
+/* What the RANSAC loop below did on one input (eo_find_homography_ransac_trace; oracle/prims.py mirrors the layout, every field int64).  An ATTEMPT is one
+ * drawn subset of 4 (counted from 0 over the whole call); a counted ITERATION is an attempt whose subset passed the check.  Draw positions count the
+ * generator's outputs consumed so far, so an attempt "at draw d" drew its last index with the d-th output. */
+#define EO_TRACE_IMPROVEMENTS 32
+enum { EO_END_BOUND = 0, EO_END_REJECT_ITER0 = 1, EO_END_REJECT_LATER = 2, EO_END_NITERS_ZERO = 3, EO_END_NO_LOOP = 4 };
+typedef struct {
+    int64_t draws;                /* generator outputs consumed */
+    int64_t iterations;           /* counted iterations */
+    int64_t attempts;             /* subsets drawn */
+    int64_t end;                  /* EO_END_*: bound reached, 1000 rejections at iteration 0, 1000 rejections later, niters cut to 0, n <= 4 */
+    int64_t improvements;         /* new best models (all of them, also beyond the list's cap) */
+    int64_t imp_attempt[EO_TRACE_IMPROVEMENTS], imp_draw[EO_TRACE_IMPROVEMENTS], imp_niters[EO_TRACE_IMPROVEMENTS], imp_good[EO_TRACE_IMPROVEMENTS],
+            imp_iter[EO_TRACE_IMPROVEMENTS];      /* per improvement: its attempt, the draws consumed with it, the bound it set, its inliers, the iterations counted with it */
+    int64_t last_imp_attempt, last_imp_draw;      /* of the last improvement (-1: none), also when the list overflowed */
+    int64_t longest_reject_run;   /* most consecutive rejected subsets */
+    int64_t longest_run_attempt;  /* ordinal of that run's first attempt */
+    int64_t longest_run_draw;     /* draws consumed before that attempt */
+    int64_t max_attempt_draws;    /* most draws one attempt needed */
+    int64_t solve_failures;       /* subsets that passed the check but whose 4-point solve failed */
+    int64_t min_model_support;    /* fewest inliers any solved 4-point model had (n + 1: none solved) */
+    int64_t inliers;              /* inlier count of the returned mask (0: failure) */
+    int64_t lm_accepted;          /* LM steps accepted */
+    int64_t final_niters;         /* the adaptive bound when the loop ended */
+    int64_t ties;                 /* later models with exactly the best's inlier count (none replaces it) */
+} eo_ransac_trace;
+
+/* src (image) / dst (world) float32 [n,2]; returns 1 and fills H[9] (double), mask[n] on success.  tr: optional record of what happened. */
+static int eo_ransac_body(const float* srcf, const float* dstf, int n, double thresh, int max_iters,
+                          double confidence, int refine_iters, double* H, uint8_t* mask, eo_ransac_trace* tr)
 {
+    eo_ransac_trace dummy;
+    if (!tr) tr = &dummy;
+    memset(tr, 0, sizeof(*tr));
+    tr->end = EO_END_NO_LOOP; tr->last_imp_attempt = tr->last_imp_draw = -1; tr->min_model_support = n + 1; tr->final_niters = max_iters;
     if (n < 4) return 0;
     double* src = (double*)malloc(sizeof(double) * 2 * n);
     double* dst = (double*)malloc(sizeof(double) * 2 * n);
@@ -606,32 +639,50 @@ int eo_find_homography_ransac(const float* srcf, const float* dstf, int n, doubl
         uint64_t rng = 0xffffffffffffffffULL;
         int niters = max_iters, max_good = 0;
         const float t2 = (float)(thresh * thresh);
+        int64_t run = 0, run_attempt = 0, run_draw = 0;
+        tr->end = max_iters > 0 ? EO_END_BOUND : EO_END_NITERS_ZERO;
         for (int iter = 0; iter < niters; ++iter) {
             int idx[4], found = 0;
             for (int attempt = 0; attempt < 1000 && !found; ++attempt) {
+                const int64_t d0 = tr->draws;
                 for (int i = 0; i < 4; ++i) {
                     int v, dup;
                     do {
-                        v = (int)(eo_rng_next(&rng) % (uint32_t)n);
+                        v = (int)(eo_rng_next(&rng) % (uint32_t)n); ++tr->draws;
                         dup = 0;
                         for (int j = 0; j < i; ++j) dup |= (idx[j] == v);
                     } while (dup);
                     idx[i] = v;
                 }
                 found = eo_check_subset4(src, dst, idx);
+                if (tr->draws - d0 > tr->max_attempt_draws) tr->max_attempt_draws = tr->draws - d0;
+                if (!found) {
+                    if (run == 0) { run_attempt = tr->attempts; run_draw = d0; }
+                    if (++run > tr->longest_reject_run) { tr->longest_reject_run = run; tr->longest_run_attempt = run_attempt; tr->longest_run_draw = run_draw; }
+                } else run = 0;
+                ++tr->attempts;
             }
-            if (!found) { if (iter == 0) { ok = 0; goto done; } break; }
+            if (!found) { tr->end = iter == 0 ? EO_END_REJECT_ITER0 : EO_END_REJECT_LATER; if (iter == 0) { ok = 0; goto done; } break; }
+            ++tr->iterations;
             double Hc[9];
-            if (!eo_h4_homography(src, dst, idx, Hc)) continue;
+            if (!eo_h4_homography(src, dst, idx, Hc)) { ++tr->solve_failures; continue; }
             eo_reproj_err(src, dst, n, Hc, err);
             int good = 0;
             for (int i = 0; i < n; ++i) { m[i] = err[i] <= t2; good += m[i]; }
+            if (good < tr->min_model_support) tr->min_model_support = good;
             if (good > (max_good > 3 ? max_good : 3)) {
                 memcpy(mask, m, n); memcpy(best, Hc, sizeof(best));
                 max_good = good;
                 niters = eo_ransac_update_iters(confidence, (double)(n - good) / n, 4, niters);
-            }
+                if (tr->improvements < EO_TRACE_IMPROVEMENTS) {
+                    const int k = (int)tr->improvements;
+                    tr->imp_attempt[k] = tr->attempts - 1; tr->imp_draw[k] = tr->draws; tr->imp_niters[k] = niters; tr->imp_good[k] = good; tr->imp_iter[k] = tr->iterations;
+                }
+                ++tr->improvements; tr->last_imp_attempt = tr->attempts - 1; tr->last_imp_draw = tr->draws;
+                if (niters == 0) tr->end = EO_END_NITERS_ZERO;
+            } else if (max_good > 0 && good == max_good) ++tr->ties;
         }
+        tr->final_niters = niters;
         ok = max_good > 0;
         if (ok) {
             /* compress to inliers, DLT on all of them, then LM polish */
@@ -642,16 +693,30 @@ int eo_find_homography_ransac(const float* srcf, const float* dstf, int n, doubl
             double Hr[9];
             if (eo_dlt_homography(s2, d2, 0, ni, Hr)) {
                 memcpy(best, Hr, sizeof(best));
-                if (refine_iters > 0) eo_lm_refine(s2, d2, ni, best, refine_iters);
+                if (refine_iters > 0) tr->lm_accepted = eo_lm_refine_count(s2, d2, ni, best, refine_iters);
             }
+            tr->inliers = ni;
             free(sel); free(s2); free(d2);
         }
     }
 done:
     if (ok) memcpy(H, best, sizeof(best));
+    if (ok && n == 4) tr->inliers = 4;
     free(src); free(dst); free(err); free(m);
     return ok;
 }
+int eo_find_homography_ransac(const float* srcf, const float* dstf, int n, double thresh, int max_iters,
+                              double confidence, int refine_iters, double* H, uint8_t* mask)
+{
+    return eo_ransac_body(srcf, dstf, n, thresh, max_iters, confidence, refine_iters, H, mask, 0);
+}
+/* the same call, and what its loop did */
+int eo_find_homography_ransac_trace(const float* srcf, const float* dstf, int n, double thresh, int max_iters,
+                                    double confidence, int refine_iters, double* H, uint8_t* mask, eo_ransac_trace* tr)
+{
+    return eo_ransac_body(srcf, dstf, n, thresh, max_iters, confidence, refine_iters, H, mask, tr);
+}
+int eo_ransac_trace_size(void) { return (int)sizeof(eo_ransac_trace); }
 
 /* ---------------------------------------------------------------------------------------------------- */
 /* Second CPU mode: the solver OpenCV 4.11 itself uses (parity unpinned: cv2 is absent; restated from the published

@@ -178,6 +178,38 @@ def find_homography_ransac(src, dst, thresh=5.0, max_iters=2000, confidence=0.99
     return H.reshape(3, 3), mask[:n]
 
 
+TRACE_IMPROVEMENTS = 32
+END_BOUND, END_REJECT_ITER0, END_REJECT_LATER, END_NITERS_ZERO, END_NO_LOOP = range(5)
+
+
+class RansacTrace(C.Structure):
+    """eo_prims.c eo_ransac_trace: what the RANSAC loop did on one input (attempt = one drawn subset, counted from 0; iteration = an attempt whose
+    subset passed the check; draw positions count the generator outputs consumed)."""
+    _fields_ = [("draws", C.c_int64), ("iterations", C.c_int64), ("attempts", C.c_int64), ("end", C.c_int64), ("improvements", C.c_int64),
+                ("imp_attempt", C.c_int64 * TRACE_IMPROVEMENTS), ("imp_draw", C.c_int64 * TRACE_IMPROVEMENTS),
+                ("imp_niters", C.c_int64 * TRACE_IMPROVEMENTS), ("imp_good", C.c_int64 * TRACE_IMPROVEMENTS), ("imp_iter", C.c_int64 * TRACE_IMPROVEMENTS),
+                ("last_imp_attempt", C.c_int64), ("last_imp_draw", C.c_int64),
+                ("longest_reject_run", C.c_int64), ("longest_run_attempt", C.c_int64), ("longest_run_draw", C.c_int64),
+                ("max_attempt_draws", C.c_int64), ("solve_failures", C.c_int64), ("min_model_support", C.c_int64),
+                ("inliers", C.c_int64), ("lm_accepted", C.c_int64), ("final_niters", C.c_int64), ("ties", C.c_int64)]
+
+
+def find_homography_ransac_trace(src, dst, thresh=5.0, max_iters=2000, confidence=0.995, refine_iters=10):
+    """find_homography_ransac and what its loop did -> (H | None, mask | None, trace dict; the imp_* lists hold the first TRACE_IMPROVEMENTS improvements)"""
+    src = _f32(src).reshape(-1, 2)
+    dst = _f32(dst).reshape(-1, 2)
+    n = src.shape[0]
+    H = np.empty(9, np.float64)
+    mask = np.zeros(max(n, 1), np.uint8)
+    tr = RansacTrace()
+    assert lib().eo_ransac_trace_size() == C.sizeof(RansacTrace)
+    ok = lib().eo_find_homography_ransac_trace(_p(src), _p(dst), n, C.c_double(thresh), int(max_iters), C.c_double(confidence),
+                                               int(refine_iters), _p(H, C.c_double), _p(mask, C.c_uint8), C.byref(tr))
+    k = min(int(tr.improvements), TRACE_IMPROVEMENTS)
+    t = {name: (list(getattr(tr, name))[:k] if name.startswith("imp_") else int(getattr(tr, name))) for name, _ in RansacTrace._fields_}
+    return (H.reshape(3, 3), mask[:n], t) if ok else (None, None, t)
+
+
 def perspective_transform(pts, H):
     pts = _f32(pts).reshape(-1, 2)
     H = np.ascontiguousarray(H, np.float64).reshape(9)
